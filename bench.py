@@ -5,11 +5,23 @@ A "step" is one generation of main.rs:429-464 (fitness-weighted parent draw, par
 both matrices, core mutation, accessory gain/loss, HR, HGT) on BASELINE.json configs[1]:
 --pop_size 1000 --core_size 1200000 --pan_genes 6000 (defaults otherwise), state resident in HBM.
 
-The default line (N = 1) also carries `other_configs`: short runs of the other BASELINE configurations on the same
-GPU -- cfg3 (HR = HGT = 0.5), the cfg5 population (N = 8192: sweep + the all-pairs distance phase at P = 2^25),
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what its headline figure needs: it sets up, settles,
+warms up, times the N steps, writes the outputs of the last step if `--dump-outputs DIR` is given, and prints the result
+line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the sweep's roofline from the same steps).
+Everything else this file measures runs only with `--full`: the distance phase, the CPU baseline, the other
+configurations and, with several ranks, the north-star workloads.
+
+With `--full` the default line (N = 1) also carries `other_configs`: short runs of the other BASELINE configurations on
+the same GPU -- cfg3 (HR = HGT = 0.5), the cfg5 population (N = 8192: sweep + the all-pairs distance phase at P = 2^25),
 cfg4 (N = 65536) as one rank of 8 (`--emulate-shard 8`) and whole on one GPU -- each with generations/s, the
 sweep's roofline fraction and the distance phase.  `--config NAME` makes one of them the main workload (that is
 how the per-config rocprofv3 summaries under profiles/ are collected).
+
+`--dump-outputs DIR` writes what a caller of the timed path holds after its last step, as DIR/<name>.npy: the parents
+drawn in that generation (float64) and both genome matrices (float32; a matrix of more than DUMP_WHOLE_CELLS cells as a
+fixed, seeded sample of DUMP_SAMPLE_CELLS cells, `<name>_sample.npy`, with its flat indices in `<name>_sample_index.npy`).
+The same arguments give the same inputs and the same number of generations before the timed ones on every run, so two
+builds can be compared output for output.
 
 Multi-GPU (one process per GPU, launched by torch.distributed.run): the core genome is sharded
 BY SITE.  The driver's contract line is WEAK scaling of cfg2: every rank holds 1.2 M sites of a core
@@ -24,12 +36,12 @@ whole simulation's generations/s).
 `--emulate-shard K` (one GPU): this process runs shard 0 of K -- 1/K of the sites, its share of the accessory
 chain and the host half of the parent draw -- i.e. what one rank of a K-GPU strong-scaling run does per generation.
 
-Before anything is timed the sweep is run in untimed batches until its per-launch time is stable (clock ramp and
-first touch on a cold box), independently of --warmup; with several ranks the decision to stop is shared, so that
-every rank runs the same number of generations.
+Before anything is timed the sweep is run in SETTLE_BATCHES untimed batches (clock ramp and first touch on a cold box),
+independently of --warmup; the count is fixed, so that every rank and every run reaches the timed steps at the same
+generation.  `settle_sweep_ms` records the per-launch time of each batch.
 
 The JSON line also carries `roofline` (fused sweep: algorithmic bytes / HIP-event launch time against
-8 TB/s, PMC traffic from profiles/), `distance_roofline` (the distance phase priced against the roofline of the
+8 TB/s, PMC traffic from profiles/); with `--full` also `distance_roofline` (the distance phase priced against the roofline of the
 kernel form that ran), `cpu_baseline` (the reference algorithm restated in C on the host cores: all cores, one
 thread, and its distance phase), `mpairs_per_s` / `distance_ms` / `pair_sites_per_s` for the whole distance phase.
 """
@@ -45,6 +57,13 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s
 MFMA_I8_PEAK_TOPS = 5000.0   # MI355X_MICROARCH.md, Matrix cores: I8 = 2x BF16 per clock, BF16 ~2.5 PFLOP/s dense
 MFMA_FP4_PEAK_TOPS = 10000.0  # the same table: FP4 (block-scaled) = 4x BF16 per clock, ~10 PFLOP/s dense
+
+SETTLE_BATCHES = 3             # untimed batches of ~30 ms before the warm-up (where the adaptive loop this replaces nearly always stopped)
+DUMP_WHOLE_CELLS = 1 << 22     # --dump-outputs: an array up to this many cells is written whole ...
+DUMP_SAMPLE_CELLS = 1 << 20    # ... a larger one as this many cells drawn with DUMP_SEED
+DUMP_SEED = 20250101
+DUMP_MAX_BYTES = 64 << 20
+CORE_READ_LIMIT = 16 << 30     # the core matrix is read back for the dump only up to this many bytes (cfg4 holds 78.6 GB)
 
 CONFIGS = {
     # name: (simulation parameters, P, shard emulation, default steps, default warmup, BASELINE label)
@@ -398,9 +417,50 @@ def _with_chain(r, exchange, chain):
     return r
 
 
-def measure(ctx, kw, P, steps, warmup, shard_rank, shard_count, seed=0, want_pairs=False, exchange=None, xchg=None, chain=None):
+def read_outputs(sim):
+    """what a caller of the timed path holds after its last generation: the parents drawn in it and both genome matrices
+    (this process's sites of the core matrix, and only while a host copy of them stays within CORE_READ_LIMIT bytes)"""
+    out = {"parents": sim.last_parents(), "pan_genome": sim.pan_genome.read_matrix()}
+    if sim.core_genome.size * sim.core_genome.ncols <= CORE_READ_LIMIT:
+        out["core_genome"] = sim.core_genome.read_matrix()
+    return out
+
+
+def dump_arrays(raw):
+    """the arrays --dump-outputs writes: integers wider than 16 bits as float64, the rest as float32; an array of more than
+    DUMP_WHOLE_CELLS cells as DUMP_SAMPLE_CELLS cells at sorted flat indices drawn with DUMP_SEED (`<name>_sample`), and
+    those indices (`<name>_sample_index`, float64)"""
+    import numpy as np
+    out = {}
+    for name, a in raw.items():
+        a = np.ascontiguousarray(a)
+        ftype = np.float64 if a.dtype.itemsize > 2 else np.float32
+        if a.size <= DUMP_WHOLE_CELLS:
+            out[name] = a.astype(ftype)
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, a.size, DUMP_SAMPLE_CELLS, dtype=np.int64))
+            out[name + "_sample"] = a.reshape(-1)[idx].astype(ftype)
+            out[name + "_sample_index"] = idx.astype(np.float64)
+    return out
+
+
+def save_outputs(path, arrays):
+    """DIR/<name>.npy for every array of dump_arrays(); returns {name: shape} for the result line"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
+def measure(ctx, kw, P, steps, warmup, shard_rank, shard_count, seed=0, want_pairs=False, exchange=None, xchg=None, chain=None,
+            distances=True, dump=False):
     """One workload: create the simulation (this rank's shard), settle, warm up, time exactly `steps` generations
-    between barriers (max over ranks), then the distance phase.  Returns a dict of raw measurements.
+    between barriers (max over ranks), then (`distances`) the distance phase.  Returns a dict of raw measurements, with
+    `outputs` (dump_arrays of read_outputs after the last timed generation) when `dump` is set.
     `exchange` names the per-generation exchange step of a strong-scaling run (HGT donors sharded over the ranks, deltas
     ORed across them): "rccl" / "torch" = the provider object `xchg` that pick_exchange built and probed (the caller owns
     it); "emulate" = this process plays shard 0 of shard_count and device-local copies of the same volume stand in for
@@ -410,7 +470,10 @@ def measure(ctx, kw, P, steps, warmup, shard_rank, shard_count, seed=0, want_pai
         if xchg is None and exchange != "emulate":
             exchange = None
         r = importlib.import_module(os.environ["PANSIM_BENCH_STUB"]).measure(ctx, kw, P, steps, warmup, shard_rank, shard_count,
-                                                                            exchange=exchange, want_pairs=want_pairs)
+                                                                            exchange=exchange, want_pairs=want_pairs,
+                                                                            distances=distances, dump=dump)
+        if dump:
+            r["outputs"] = dump_arrays(r["outputs"])
         return _with_chain(r, exchange, chain)
     import pansim_amd as pa
     torch, dist, world = ctx.torch, ctx.dist, ctx.world
@@ -428,20 +491,15 @@ def measure(ctx, kw, P, steps, warmup, shard_rank, shard_count, seed=0, want_pai
         exchange, xchg = None, None
     sim.enable_timing(True)
     est_gen_ms = 2.0 * N * sim.core_genome.ncols / 4e9            # sweep at ~4 TB/s
-    settle, prev, batch = [], None, int(max(5, min(50, 30.0 / max(est_gen_ms, 1e-3))))
-    for _ in range(40):
+    settle, batch = [], int(max(5, min(50, 30.0 / max(est_gen_ms, 1e-3))))
+    # a fixed number of batches: every rank (the parents and the accessory mutations are keyed on the generation number)
+    # and every run with the same arguments reaches the timed steps at the same generation
+    for _ in range(SETTLE_BATCHES):
         sim.sweep_timing(reset=True)
         sim.run(batch)
         sim.sync()
         n, ms, _b = sim.sweep_timing(reset=True)
-        cur = ms / max(n, 1)
-        settle.append(round(cur, 4))
-        stable = prev is not None and abs(cur - prev) <= 0.01 * prev and len(settle) >= 3
-        # every rank must leave the loop after the same number of generations (the parents and the accessory
-        # mutations are keyed on the generation number): stop only when every rank is stable
-        if ctx.reduce(0.0 if stable else 1.0, "max") == 0.0:
-            break
-        prev = cur
+        settle.append(round(ms / max(n, 1), 4))
     sim.run(warmup)
     sim.sync()
     sim.sweep_timing(reset=True)
@@ -468,11 +526,12 @@ def measure(ctx, kw, P, steps, warmup, shard_rank, shard_count, seed=0, want_pai
     host_n, host_wait, host_weights, host_draw = sim.host_timing(reset=True)
     sim.enable_timing(False)
     sweep_form = sim.core_genome.last_sweep_form()
+    outputs = dump_arrays(read_outputs(sim)) if dump else None
 
     # distance phase (main.rs:467-482): P sampled pairs, core Hamming + accessory Jaccard.
     # Site-sharded: integer partial counts are summed over ranks (RCCL all-reduce).
-    dist_kernel_ms = None
-    if world == 1:
+    dist_kernel_ms, dist_dt = None, None
+    if distances and world == 1:
         # one process holds every site it will ever hold: the library's own distance phase (both matrices'
         # kernels enqueued together, pinned numerators, main.rs:467-470).  A first call builds the scratch
         # buffers (2-bit copy of the matrix, partial counts); the timed call is the steady state of --print_dist.
@@ -483,7 +542,7 @@ def measure(ctx, kw, P, steps, warmup, shard_rank, shard_count, seed=0, want_pai
         ctx.barrier()
         dist_dt = time.perf_counter() - t1
         dist_kernel_ms = sim.distance_timing()
-    else:
+    elif distances:
         cnt = torch.zeros(P, dtype=torch.int32, device="cuda")
         sim.core_genome.pairwise_counts_device(sim.range1, sim.range2, cnt.data_ptr())      # builds the scratch buffers
         ctx.barrier()
@@ -494,7 +553,7 @@ def measure(ctx, kw, P, steps, warmup, shard_rank, shard_count, seed=0, want_pai
         core_d = (cnt.cpu().numpy().astype("uint32") // 2) / float(kw["core_size"])
         ctx.barrier()
         dist_dt = ctx.reduce(time.perf_counter() - t1, "max")
-    assert core_d.shape == acc_d.shape
+    assert dist_dt is None or core_d.shape == acc_d.shape
     avg_ms = sweep_ms / max(launches, 1)
     r = {"dt": dt, "steps": steps, "warmup": warmup, "launches": launches, "sweep_avg_ms": avg_ms,
          "sweep_avg_ms_max_over_ranks": ctx.reduce(avg_ms, "max"), "sweep_avg_ms_min_over_ranks": ctx.reduce(avg_ms, "min"),
@@ -518,6 +577,8 @@ def measure(ctx, kw, P, steps, warmup, shard_rank, shard_count, seed=0, want_pai
                                        "ONE link (round 4's figure)" if ring else ""))
     if want_pairs:
         r["pairs"] = (sim.range1, sim.range2)
+    if dump:
+        r["outputs"] = outputs
     sim.close()
     return r
 
@@ -612,8 +673,13 @@ def main():
     ap.add_argument("--HR_rate", type=float, default=None)
     ap.add_argument("--HGT_rate", type=float, default=None)
     ap.add_argument("--max_distances", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the distance phase, the CPU baseline, the other "
+                         "BASELINE configurations (default workload, one GPU) and the north-star workloads (several ranks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short runs of the other BASELINE configurations")
     ap.add_argument("--emulate-shard", type=int, default=None, metavar="K",
                     help="one GPU only: run shard 0 of K of a strong-scaling run (1/K of --core_size, its share of the accessory chain)")
     ap.add_argument("--competition_strength", type=float, default=0.0)
@@ -621,6 +687,10 @@ def main():
                     help="weak (default, the driver's contract): --core_size sites PER GPU; strong: --core_size is the "
                          "whole genome, split by site over the ranks (BASELINE configs[3]: --pop_size 65536 --scaling strong)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -809,8 +879,10 @@ def rank_main(args):
             xmode = "emulate"
         elif world > 1:
             xmode, xchg, chain = pick_exchange(ctx, rank, world, os.environ.get("PANSIM_BENCH_EXCHANGE"))
-    r = measure(ctx, kw, P, steps, warmup, 0 if emu else rank, emu if emu else world, want_pairs=True, exchange=xmode, xchg=xchg,
-                chain=chain)
+    dump = args.dump_outputs is not None and rank == 0
+    r = measure(ctx, kw, P, steps, warmup, 0 if emu else rank, emu if emu else world, want_pairs=args.full, exchange=xmode,
+                xchg=xchg, chain=chain, distances=args.full, dump=dump)
+    dumped = save_outputs(args.dump_outputs, r.pop("outputs")) if dump else None
 
     out = None
     if rank == 0:
@@ -846,10 +918,6 @@ def rank_main(args):
                                    "sharded %d-way" % (wl_label, kw["pop_size"], kw["core_size"], kw["pan_genes"], kw["HR_rate"],
                                                        kw["HGT_rate"], world),
                        "parallelism": "site-shard x%d" % world},
-            "mpairs_per_s": P / r["dist_dt"] / 1e6,
-            "distance_ms": 1e3 * r["dist_dt"],
-            "pair_sites_per_s": P * float(L_local if emu else kw["core_size"]) / r["dist_dt"],
-            "distance_roofline": droof,
             "host_half_ms": host_half(r),
             "settle_sweep_ms": r["settle"],
             "exchange": r["exchange"],
@@ -857,20 +925,27 @@ def rank_main(args):
             "data_plane": ctx.data_plane, "control_plane": "gloo" if world > 1 else "none (one rank)",
             # ranks that answered the probe collective of the RCCL group (0: no such group -- one rank, or the gloo data plane)
             "rccl_ranks_seen": ctx.rccl_ranks_seen,
+            "full": args.full,
         }
+        if r["dist_dt"] is not None:
+            out.update({"mpairs_per_s": P / r["dist_dt"] / 1e6, "distance_ms": 1e3 * r["dist_dt"],
+                        "pair_sites_per_s": P * float(L_local if emu else kw["core_size"]) / r["dist_dt"],
+                        "distance_roofline": droof})
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if ctx.notes:
             out["notes"] = list(ctx.notes)
         if world > 1:
             out["sweep_avg_ms_over_ranks"] = {"min": r["sweep_avg_ms_min_over_ranks"], "max": r["sweep_avg_ms_max_over_ranks"]}
-        if world == 1 and not args.no_cpu_baseline and not emu:
+        if args.full and world == 1 and not args.no_cpu_baseline and not emu:
             out["cpu_baseline"] = cpu_baseline(kw, 0, r["pairs"], budget_s=20.0 if kw["pop_size"] <= 1000 else 30.0,
                                                also_threads=4 if args.config == "authors" else None)
         if emu:
             out["emulated_shards"] = emu
             out["config"]["workload"] += "; THIS LINE: shard 0 of %d emulated on one GPU (%d sites)" % (emu, L_local)
 
-    # ---- the other BASELINE configurations, short runs on the same GPU (N = 1, default workload only)
-    if default_wl and world == 1 and not args.no_other_configs:
+    # ---- the other BASELINE configurations, short runs on the same GPU (--full, N = 1, default workload only)
+    if args.full and default_wl and world == 1 and not args.no_other_configs:
         others = {}
         for name in ("cfg3", "authors", "cfg5pop", "cfg4_shard8", "cfg4"):
             okw, oP, oemu, osteps, owarm, olabel = CONFIGS[name]
@@ -894,11 +969,11 @@ def rank_main(args):
             others["cfg2_print_dist"] = {"error": str(e)[:300]}
         out["other_configs"] = others
 
-    # ---- the north-star's scaling workload at this world size: --pop_size 65536, 1.2 M core sites split over the ranks.
+    # ---- (--full) the north-star's scaling workload at this world size: --pop_size 65536, 1.2 M core sites split over the ranks.
     # The contract line is complete at this point: rank 0 prints it NOW, so that whatever happens in the second workload
     # (a hang inside a collective, a kill from outside) a parseable line exists; the same line, extended, is printed again
     # at the end (`line`: "final").  The bare form's launcher relays only the last one.
-    if default_wl and world > 1:
+    if args.full and default_wl and world > 1:
         okw, oP, _e, osteps, owarm, olabel = CONFIGS["cfg4"]
         if os.environ.get("PANSIM_BENCH_NS_CORE_SIZE"):      # (smoke runs of the launch path: a shorter genome, labelled as such)
             okw = dict(okw, core_size=int(os.environ["PANSIM_BENCH_NS_CORE_SIZE"]))

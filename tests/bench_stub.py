@@ -47,7 +47,7 @@ def providers(ctx, rank, world):
     return {"rccl": rccl, "torch": lambda: _GlooOr(ctx, broken=(MODE == "no_torch"))}
 
 
-def measure(ctx, kw, P, steps, warmup, shard_rank, shard_count, exchange=None, want_pairs=False):
+def measure(ctx, kw, P, steps, warmup, shard_rank, shard_count, exchange=None, want_pairs=False, distances=True, dump=False):
     second = kw["pop_size"] == 65536            # (bench.py's north-star workload)
     third = kw["pop_size"] == 8192              # (... and its configs[4] distance workload)
     if MODE == "hang_all" and ctx.rank == 1 and os.environ.get("PANSIM_BENCH_BACKEND") != "gloo":
@@ -67,11 +67,21 @@ def measure(ctx, kw, P, steps, warmup, shard_rank, shard_count, exchange=None, w
     ms = 0.5 + 0.01 * ctx.rank
     r = {"dt": dt, "steps": steps, "warmup": warmup, "launches": steps, "sweep_avg_ms": ms,
          "sweep_avg_ms_max_over_ranks": ctx.reduce(ms, "max"), "sweep_avg_ms_min_over_ranks": ctx.reduce(ms, "min"),
-         "bytes_per_launch": 2.0 * kw["pop_size"] * L_local, "host": (steps, 0.0, 0.0, 0.0), "settle": [ms], "dist_dt": 0.002,
+         "bytes_per_launch": 2.0 * kw["pop_size"] * L_local, "host": (steps, 0.0, 0.0, 0.0), "settle": [ms],
+         "dist_dt": 0.002 if distances else None,
          "dist_kernel_ms": None, "pair_form": 0, "L_local": L_local, "sweep_form": 1 if kw["pop_size"] <= 1024 else 3,
          "G_acc": kw["pan_genes"] - 2000, "P": P, "N": kw["pop_size"], "kw": kw,
          "exchange": {"mode": exchange or "none (accessory chain replicated on every rank)", "calls": 0,
                       "bytes_sent_plus_received_per_generation": 0.0}}
     if want_pairs:
         r["pairs"] = (None, None)
+    if dump:
+        # the engine's outputs in their native types, a function of the arguments only; the core matrix is larger than
+        # bench.DUMP_WHOLE_CELLS so that the sampled form is exercised
+        import numpy as np
+        rng = np.random.default_rng(kw["pop_size"] + steps + warmup)
+        N = min(kw["pop_size"], 1000)
+        r["outputs"] = {"parents": rng.integers(0, N, N).astype(np.uint32),
+                        "pan_genome": rng.integers(0, 2, (N, 400)).astype(np.uint8),
+                        "core_genome": rng.integers(0, 4, (N, 5000)).astype(np.uint8)}
     return r

@@ -26,7 +26,7 @@ def _run(extra_env, *args, timeout=240):
 
 
 def test_bare_form_launches_its_own_ranks():
-    p, lines = _run({}, "--gpus", "2", "--steps", "20", "--warmup", "5")
+    p, lines = _run({}, "--gpus", "2", "--steps", "20", "--warmup", "5", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1, "the bare form prints exactly one JSON line"
     d = json.loads(lines[0])
@@ -47,7 +47,7 @@ def test_bare_form_launches_its_own_ranks():
 
 
 def test_three_ranks_and_every_provider_failing():
-    p, lines = _run({"PANSIM_BENCH_STUB_MODE": "no_torch"}, "--gpus", "3", "--steps", "5", "--warmup", "1")
+    p, lines = _run({"PANSIM_BENCH_STUB_MODE": "no_torch"}, "--gpus", "3", "--steps", "5", "--warmup", "1", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads(lines[-1])
     assert d["n_gpus"] == 3 and d["north_star_generations_per_s"] > 0, "the figure is filled even without a provider"
@@ -56,7 +56,7 @@ def test_three_ranks_and_every_provider_failing():
 
 
 def test_second_workload_raising_keeps_the_contract_line():
-    p, lines = _run({"PANSIM_BENCH_STUB_MODE": "raise_ns"}, "--gpus", "2", "--steps", "5", "--warmup", "1")
+    p, lines = _run({"PANSIM_BENCH_STUB_MODE": "raise_ns"}, "--gpus", "2", "--steps", "5", "--warmup", "1", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads(lines[-1])
     assert d["value"] > 0 and d["line"] == "final" and "second workload failed" in d["north_star_scaling"]["error"]
@@ -64,7 +64,8 @@ def test_second_workload_raising_keeps_the_contract_line():
 
 
 def test_second_workload_hanging_is_cut_by_the_watchdog():
-    p, lines = _run({"PANSIM_BENCH_STUB_MODE": "hang_ns", "PANSIM_BENCH_NS_TIMEOUT": "6"}, "--gpus", "2", "--steps", "5", "--warmup", "1")
+    p, lines = _run({"PANSIM_BENCH_STUB_MODE": "hang_ns", "PANSIM_BENCH_NS_TIMEOUT": "6"}, "--gpus", "2", "--steps", "5", "--warmup", "1",
+                    "--full")
     assert len(lines) == 1, (p.returncode, p.stderr[-2000:])
     d = json.loads(lines[0])
     assert d["value"] > 0 and d["n_gpus"] == 2
@@ -74,7 +75,8 @@ def test_second_workload_hanging_is_cut_by_the_watchdog():
 
 
 def test_third_workload_hanging_keeps_the_first_two():
-    p, lines = _run({"PANSIM_BENCH_STUB_MODE": "hang_nd", "PANSIM_BENCH_NS_TIMEOUT": "6"}, "--gpus", "2", "--steps", "5", "--warmup", "1")
+    p, lines = _run({"PANSIM_BENCH_STUB_MODE": "hang_nd", "PANSIM_BENCH_NS_TIMEOUT": "6"}, "--gpus", "2", "--steps", "5", "--warmup", "1",
+                    "--full")
     assert len(lines) == 1, (p.returncode, p.stderr[-2000:])
     d = json.loads(lines[0])
     assert d["value"] > 0 and d["north_star_generations_per_s"] > 0 and d["north_star_scaling"]["scaling"] == "strong"
@@ -99,7 +101,8 @@ def test_budgets_fit_the_drivers_limit():
 
 
 def test_a_rank_dying_in_the_second_workload_keeps_the_contract_line():
-    p, lines = _run({"PANSIM_BENCH_STUB_MODE": "die_ns", "PANSIM_BENCH_NS_TIMEOUT": "30"}, "--gpus", "2", "--steps", "5", "--warmup", "1")
+    p, lines = _run({"PANSIM_BENCH_STUB_MODE": "die_ns", "PANSIM_BENCH_NS_TIMEOUT": "30"}, "--gpus", "2", "--steps", "5", "--warmup", "1",
+                    "--full")
     assert len(lines) == 1, (p.returncode, p.stderr[-2000:])
     d = json.loads(lines[0])
     assert d["value"] > 0 and d["n_gpus"] == 2 and d["launcher"]["attempts"][0]["json_lines"] >= 1
@@ -115,7 +118,8 @@ def test_under_torchrun_rank0_prints_the_contract_line_first():
     port = s.getsockname()[1]
     s.close()
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1"],
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1",
+                        "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]

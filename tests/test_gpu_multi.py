@@ -304,7 +304,7 @@ def test_bench_bare_form_two_ranks_one_gpu(pa):
     env = dict(os.environ, PANSIM_BENCH_NS_CORE_SIZE="120000")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PANSIM_BENCH_BACKEND", "PANSIM_BENCH_STUB"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
