@@ -133,7 +133,9 @@ int ps_sample_weights(const int32_t *num_genes, const double *logw, uint64_t n, 
 int ps_draw_parents(const double *weights, uint64_t n, uint64_t seed, uint32_t generation,
                     uint32_t *out_idx);
 
-/* Population::average_distance (population.rs:753-784) */
+/* Population::average_distance (population.rs:753-784), for both matrices.  Core: population.rs:132-137 over all sites, in
+ * output order; a site-shard handle (ncols != global_cols) cannot finish the sum and fails with
+ * PS_ERR_INVALID -- ps_multi_average_distance sums the shards. */
 int ps_average_distance(ps_population *p, double *out);
 /* Rows [first, first + count) of average_distance (count values): what one rank of a row-sharded D-avg computes -- every
  * individual's mean is a sum over ALL others in ascending order (:770), so the rows are independent and a run splits
@@ -200,6 +202,9 @@ int ps_sync(ps_population *p);
  * shards and for 8192 < pop_size <= 53248), "davg_nb" (matrix-core forms: 32-individual fragments per wave, 0 = choose, 1, 2, or --
  * two-phase form only; the one-kernel form then chooses by itself -- 4), "davg_ib" (two-phase form: individuals per workgroup of the
  * division + fold phase, 0 = choose, 16 or 32),
+ * "core_davg_form" (average_distance of the core matrix: 0 = choose, 1 = whole matrix -- FP4 all-pairs triangle, then the fold --,
+ * 2 = banded -- FP4 rectangle of a band of rows, then the fold --, 3 = generic; matrices that are not one-hot always take 3),
+ * "core_davg_band" (banded forms: rows per band, rounded up to a multiple of 256; 0 = choose),
  * "hgt_mode" (accessory recombination: 0 = choose, 1 = one atomic per event, 2 = two passes: bin
  * by recipient partition, OR in LDS images), "hgt_slices" (binned HGT: event slices, 0 = choose), "hgt_list_in_global" (0/1: donor gene lists in
  * global scratch instead of LDS; "hgt_bin_list_in_global": the same for the bin pass of the binned form),
@@ -385,6 +390,9 @@ int ps_multi_sync(ps_multi *m);
 int ps_multi_pairwise_counts(ps_multi *m, uint32_t *out_core);
 /* main.rs:467-470: core and accessory distances of the run's pair list (P values each) */
 int ps_multi_pairwise_distances(ps_multi *m, double *core_out, double *acc_out);
+/* population.rs:753-784 of the run's core matrix (core != 0: every shard counts its sites, shard 0 adds and folds; the tuning
+ * keys of shard 0's core handle apply) or of its accessory matrix (core == 0: shard 0's replica).  out: pop_size values. */
+int ps_multi_average_distance(ps_multi *m, int core, double *out);
 /* main.rs:550-553: <outpref>_core_genome.csv (lines assembled from the shards' columns) and _pangenome.csv */
 int ps_multi_write(ps_multi *m, const char *outpref);
 

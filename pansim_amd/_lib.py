@@ -135,6 +135,7 @@ SIGNATURES = {
     "ps_multi_sync": (_int, [_vp]),
     "ps_multi_pairwise_counts": (_int, [_vp, _u32p]),
     "ps_multi_pairwise_distances": (_int, [_vp, _f64p, _f64p]),
+    "ps_multi_average_distance": (_int, [_vp, _int, _f64p]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }
 

@@ -1870,9 +1870,11 @@ __global__ void core_pair_lookup_kernel(const uint32_t *H, uint32_t N, const uin
 // PLANES (with BLOCKED; the signed all-pairs kernel): the 16 bytes of a lane hold bit PLANES instead of 2-bit codes -- the high
 // code bits of its first and second 32 sites, then the low code bits of the same sites (lane (h, r): sites [64 h, 64 h + 64)
 // of the chunk's 128).
-template <bool NIB, bool BLOCKED = false, bool PLANES = false>
+// SLOT (core D-avg on a simulation's handle): string k is internal column slot[k], i.e. the strings are in output order
+//  and so is everything computed from them; each byte is then gathered on its own.
+template <bool NIB, bool BLOCKED = false, bool PLANES = false, bool SLOT = false>
 __global__ void __launch_bounds__(256) core_packT_kernel(const uint8_t *state, uint32_t N, uint32_t pitch, uint32_t rows,
-                                                         uint32_t *packT, uint32_t WT)
+                                                         uint32_t *packT, uint32_t WT, const uint32_t *slot = nullptr)
 {
     constexpr uint32_t SPW = NIB ? 8u : 16u;          // sites per dword
     constexpr uint32_t RS = PS_PT_IB + 4u;            // LDS row stride in dwords (16-byte aligned, banks shifted by 4 per word)
@@ -1891,9 +1893,21 @@ __global__ void __launch_bounds__(256) core_packT_kernel(const uint8_t *state, u
         const uint32_t col = min(i0 + 4u * qd, pitch - 4u);       // (columns beyond N are padding zeros or unused)
         const uint8_t *base = state + (size_t)sb * pitch + col;
         uint32_t v[SPW];
+        if (SLOT) {
+            // (individuals past N read column 0: their strings are zeroed or never stored below)
+            uint32_t c4[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) c4[k] = i0 + 4u * qd + k < N ? slot[i0 + 4u * qd + k] : 0u;
+#pragma unroll
+            for (uint32_t b = 0; b < SPW; b++) {
+                const uint8_t *r = state + (size_t)(sb + min(b, rows - 1u - sb)) * pitch;
+                v[b] = (uint32_t)r[c4[0]] | ((uint32_t)r[c4[1]] << 8) | ((uint32_t)r[c4[2]] << 16) | ((uint32_t)r[c4[3]] << 24);
+            }
+        } else {
 #pragma unroll
         for (uint32_t b = 0; b < SPW; b++)
             v[b] = *(const uint32_t *)(base + (size_t)min(b, rows - 1u - sb) * pitch);
+        }
         if (!item_valid || sb + SPW > rows) {
 #pragma unroll
             for (uint32_t b = 0; b < SPW; b++)
@@ -2143,6 +2157,9 @@ __global__ void __launch_bounds__(512) core_allpairs_mfma_kernel(const uint32_t 
 // i8 at 2x).  {0, 1} products and f32 sums of at most 2^24 matches are exact, so the integers equal the i8 form's.
 // Table: byte (4 sites) -> 8 bytes (4 sites x 4 nibbles), stored 32 times (64 KB): a lane reads copy (lane & 31), and the
 // 32 lanes a ds_read_b64 serves together cover all 64 banks exactly once.  Two table reads per operand fragment and step.
+// BAND (core D-avg): the grid walks the rectangle (row tiles band_tile0 .. , every column tile) instead of the
+// triangle, and a range's counts of row i go to row i - 256 band_tile0 of its slice (slice_words apart, row pitch ld) for
+// the rows i < band_end only.
 typedef int ps_v8i __attribute__((ext_vector_type(8)));
 typedef float ps_v16f __attribute__((ext_vector_type(16)));
 
@@ -2160,8 +2177,11 @@ __device__ __forceinline__ uint2 ps_mf_lut_read64(uint32_t raw, uint32_t colofs,
     return make_uint2(v.x, v.y);
 }
 
+template <bool BAND>
 __global__ void __launch_bounds__(512) core_allpairs_mfma_fp4_kernel(const uint32_t *packT, uint32_t WT, uint32_t N, uint32_t *H,
-                                                                     uint32_t chunks_per_range, uint32_t n_chunks, uint32_t ntile)
+                                                                     uint32_t chunks_per_range, uint32_t n_chunks, uint32_t ntile,
+                                                                     uint32_t band_tile0 = 0, uint32_t band_end = 0, uint64_t ld = 0,
+                                                                     uint64_t slice_words = 0)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lut[];      // 256 entries x 32 copies x 8 bytes = 64 KB, at LDS offset 0
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2173,9 +2193,15 @@ __global__ void __launch_bounds__(512) core_allpairs_mfma_fp4_kernel(const uint3
         *(uint2 *)(lut + (size_t)x * 8u) = v;        // x = e * 32 + copy
     }
     const uint32_t colofs = (lane & 31u) << 3;
-    uint32_t ti = 0, rem = blockIdx.x;
+    uint32_t ti = 0, tj;
+    if (BAND) {
+        ti = band_tile0 + blockIdx.x / ntile;
+        tj = blockIdx.x % ntile;
+    } else {
+    uint32_t rem = blockIdx.x;
     while (rem >= ntile - ti) { rem -= ntile - ti; ti++; }
-    const uint32_t tj = ti + rem;
+    tj = ti + rem;
+    }
     const uint32_t wi = wave >> 2, wj = wave & 3u;
     const uint32_t r = lane & 31u, h = lane >> 5;
     const uint32_t *src[6];
@@ -2240,7 +2266,7 @@ __global__ void __launch_bounds__(512) core_allpairs_mfma_fp4_kernel(const uint3
     // pair and range into a single N x N array was 47 of the kernel's 51 ms at N = 8192: device-scope atomics do not run in
     // the L2 of an XCD)
     const uint32_t sites = (c_hi - c_lo) * PS_MF_CHUNK_DW * 16u;
-    uint32_t *Hs = H + (size_t)blockIdx.y * N * N;
+    uint32_t *Hs = BAND ? H + blockIdx.y * slice_words : H + (size_t)blockIdx.y * N * N;
 #pragma unroll
     for (int a = 0; a < 4; a++)
 #pragma unroll
@@ -2250,6 +2276,9 @@ __global__ void __launch_bounds__(512) core_allpairs_mfma_fp4_kernel(const uint3
             for (int v = 0; v < 16; v++) {
                 const uint32_t i = ti * PS_MF_TILE + wi * 128u + (uint32_t)a * 32u + (uint32_t)((v & 3) + 8 * (v >> 2)) + 4u * h;
                 const uint32_t mism = sites - (uint32_t)acc[a][b][v];
+                if (BAND) {
+                    if (i < band_end && j < N) Hs[(size_t)(i - band_tile0 * PS_MF_TILE) * ld + j] = 2u * mism;
+                } else
                 if (i < N && j < N) Hs[(size_t)i * N + j] = 2u * mism;
             }
         }
@@ -2430,6 +2459,114 @@ __global__ void __launch_bounds__(256) u32_add_kernel(uint32_t *dst, const uint3
 {
     const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) dst[k] += src[k];
+}
+
+// ---------------------------------------------------------------------------
+// Core D-avg (population.rs:753-784 with the core branch of get_distance, :132-137).  Phase 1 leaves the
+// Hamming numerators h(i, j) (distances.rs:22-52) of the rows to fold as u32 counts in output order; phase 2 is the fold:
+//   d(i, j) = (double)(h(i, j) / 2) / L over j = 0 .. N-1 without j == i, added left to right in f64, / (N - 1),
+//   0.0 -> f64::MIN_POSITIVE.
+// Workgroup = 16 rows: 256 threads turn a chunk of 64 columns x 16 rows of counts into f64 terms and park them in LDS
+// (the next chunk's counts already in registers) while one wave adds the previous chunk, one dependent chain per row.
+// Terms past N and the self term are parked as +0.0: adding +0.0 to a sum of non-negative terms changes nothing.
+// TRI (the whole-matrix form): the counts are the 2^TSH-tiles ti <= tj of an N x N matrix (core_allpairs_mfma_fp4_kernel:
+// 256-tiles; core_allpairs_kernel: 128-tiles).  Left of the row block's tile the fold reads column block H[j][ib .. ib + 15]
+// instead -- 64 contiguous bytes per j, transposed on the way into LDS.  Otherwise the counts are a band: row i at row
+// i - c_lo of C, every column.  Rows [i_lo, i_lo + i_cnt) are folded, into out[i - i_lo].
+// ---------------------------------------------------------------------------
+#define PS_CD_IB 16u     // rows per workgroup
+#define PS_CD_JB 64u     // columns per parked chunk
+
+template <bool TRI, uint32_t TSH>
+__device__ __forceinline__ void ps_core_davg_fold(const uint32_t *C, uint64_t ld, uint32_t N, uint32_t c_lo, uint32_t i_lo,
+                                                  uint32_t i_cnt, double L, double *out)
+{
+    __shared__ double S[2][PS_CD_JB * (PS_CD_IB + 1u)];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t ib = (i_lo & ~(PS_CD_IB - 1u)) + blockIdx.x * PS_CD_IB;    // (16-aligned: inside one tile)
+    const uint32_t nch = (N + PS_CD_JB - 1u) / PS_CD_JB;
+    const bool folder = tid >= 256u;                                          // (wave-uniform)
+    auto row_ok = [&](uint32_t i) { return i >= i_lo && i - i_lo < i_cnt; };
+    // item q of a thread: (jj, ii) of the chunk; transposed below the computed triangle
+    auto below = [&](uint32_t jb) { return TRI && (jb >> TSH) < (ib >> TSH); };
+    auto item = [&](uint32_t jb, uint32_t q, uint32_t &jj, uint32_t &ii) {
+        if (below(jb)) { ii = tid & 15u; jj = (tid >> 4) + 16u * q; }
+        else { ii = tid >> 4; jj = (tid & 15u) + 16u * q; }
+    };
+    auto load = [&](uint32_t c, uint32_t (&v)[4]) {
+        const uint32_t jb = c * PS_CD_JB;
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; q++) {
+            uint32_t jj, ii;
+            item(jb, q, jj, ii);
+            const uint32_t i = ib + ii, j = jb + jj;
+            v[q] = 0u;
+            if (j < N && row_ok(i)) v[q] = below(jb) ? C[(size_t)j * ld + i] : C[(size_t)(i - c_lo) * ld + j];
+        }
+    };
+    double sum = 0.0;
+    uint32_t cur[4], nxt[4];
+    if (!folder) load(0u, cur);
+    for (uint32_t c = 0; c <= nch; c++) {
+        if (!folder) {
+            if (c < nch) {
+                if (c + 1u < nch) load(c + 1u, nxt);
+                double *Sb = S[c & 1u];
+                const uint32_t jb = c * PS_CD_JB;
+#pragma unroll
+                for (uint32_t q = 0; q < 4u; q++) {
+                    uint32_t jj, ii;
+                    item(jb, q, jj, ii);
+                    // population.rs:136 (integer / 2), :137 (f64 division by the full core width)
+                    Sb[jj * (PS_CD_IB + 1u) + ii] = jb + jj == ib + ii ? 0.0 : (double)(cur[q] >> 1) / L;
+                }
+#pragma unroll
+                for (uint32_t q = 0; q < 4u; q++) cur[q] = nxt[q];
+            }
+        } else if (c > 0u && tid - 256u < PS_CD_IB) {
+            const double *Sb = S[(c - 1u) & 1u] + (tid - 256u);
+#pragma unroll 16
+            for (uint32_t jj = 0; jj < PS_CD_JB; jj++) sum += Sb[jj * (PS_CD_IB + 1u)];       // :770, ascending j
+        }
+        __syncthreads();
+    }
+    if (folder && tid - 256u < PS_CD_IB) {
+        const uint32_t i = ib + (tid - 256u);
+        if (row_ok(i)) {
+            double fd = sum / (double)(N - 1u);                                     // :771
+            if (fd == 0.0) fd = 2.2250738585072014e-308;                            // f64::MIN_POSITIVE, :774-776
+            out[i - i_lo] = fd;
+        }
+    }
+}
+
+template <uint32_t TSH>
+__global__ void __launch_bounds__(320) core_average_from_h_kernel(const uint32_t *H, uint32_t N, uint32_t i_lo, uint32_t i_cnt,
+                                                                  double L, double *out)
+{
+    ps_core_davg_fold<true, TSH>(H, N, N, 0u, i_lo, i_cnt, L, out);
+}
+
+__global__ void __launch_bounds__(320) core_average_from_counts_kernel(const uint32_t *C, uint64_t ld, uint32_t N, uint32_t c_lo,
+                                                                       uint32_t i_lo, uint32_t i_cnt, double L, double *out)
+{
+    ps_core_davg_fold<false, 8u>(C, ld, N, c_lo, i_lo, i_cnt, L, out);
+}
+
+// generic band counts (any byte values, either row order): C[r][j] = h(c_lo + r, j) over this handle's sites, one thread
+// per pair (the reference's byte popcount, distances.rs:22-52)
+__global__ void __launch_bounds__(256) core_band_counts_simple(const uint8_t *state, uint32_t pitch, uint32_t sites, uint32_t N,
+                                                               const uint32_t *slot, uint32_t c_lo, uint32_t *C, uint64_t ld)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x, r = blockIdx.y;
+    if (j >= N) return;
+    const uint32_t a = slot ? slot[c_lo + r] : c_lo + r, b = slot ? slot[j] : j;
+    uint32_t h = 0;
+    for (uint32_t s = 0; s < sites; s++) {
+        const uint8_t *row = state + (size_t)s * pitch;
+        h += __popc((uint32_t)(row[a] ^ row[b]));
+    }
+    C[(size_t)r * ld + j] = h;
 }
 
 // distances.rs:22-52 / :55-77 on two byte slices already in device memory

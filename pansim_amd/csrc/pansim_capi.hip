@@ -261,6 +261,10 @@ struct ps_population {
     uint32_t davg_ib = 0;            // two-phase D-avg: individuals per workgroup of phase 2 (0 = choose, 16 or 32)
     bool davg_plain_division = false; // matrix-core D-avg: the compiler's f64 division in the epilogue ("davg_plain_division": A/B, tests)
     uint64_t H_cap = 0;
+    int core_davg_form = 0;          // core D-avg: 0 = choose, 1 = whole matrix (triangle in d_H), 2 = banded, 3 = generic
+    uint32_t core_davg_band = 0;     // core D-avg, banded forms: rows per band (rounded up to 256-tiles), 0 = choose
+    uint32_t *d_cdavg = nullptr;     // core D-avg: u32 counts of one band (x chunk ranges)
+    uint64_t cdavg_cap = 0;          // (words)
     int pair_mode = 0;               // 0 auto, 1 sampled kernel, 2 all-pairs kernel (tuning/tests)
     int last_pair_form = 0;          // kernel form of the last core pair-count call (ps_last_pair_form)
     uint32_t pair_ranges = 0;        // tests: site ranges of the tiled sampled-pair kernels (0 = choose); the 16-bit cap still applies
@@ -329,7 +333,7 @@ extern "C" void ps_population_destroy(ps_population *p)
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     void *ptrs[] = { p->d_row_slot, p->state, p->state2, p->d_delta, p->hgt_ovf_img, p->G[0], p->G[1], p->I[0], p->I[1], p->I_snap, p->d_ptab[0], p->d_ptab[1], p->hgt_scratch, p->cnt, p->d_idx, p->d_idxT, p->d_work,
-                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part };
+                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (p->h_flag) (void)hipHostFree(p->h_flag);
@@ -541,6 +545,13 @@ extern "C" int ps_set_tuning(ps_population *p, const char *key, int64_t value)
         if (value < 0 || value > 3)
             return ps_fail(PS_ERR_INVALID, "davg_form must be 0 (choose), 1 (LDS-tile popcount kernels), 2 (matrix cores, one kernel) or 3 (matrix cores, two phases)");
         p->davg_form = (int)value;
+    } else if (k == "core_davg_form") {
+        if (value < 0 || value > 3)
+            return ps_fail(PS_ERR_INVALID, "core_davg_form must be 0 (choose), 1 (whole matrix), 2 (banded) or 3 (generic)");
+        p->core_davg_form = (int)value;
+    } else if (k == "core_davg_band") {
+        if (value < 0 || value > (1ll << 31)) return ps_fail(PS_ERR_INVALID, "core_davg_band must be 0 (choose)..2^31 rows");
+        p->core_davg_band = (uint32_t)value;
     } else if (k == "davg_plain_division") {
         p->davg_plain_division = value != 0;
     } else if (k == "davg_ib") {
@@ -1989,6 +2000,28 @@ static bool core_pairs_take_a_tiled_kernel(const ps_population *p, uint64_t P)
     return !pp.use_rows && !pp.use_all && pp.W != 0u;
 }
 
+// (tile, chunk range) workgroups of the all-pairs matrix-core kernels, one 8-wave workgroup per CU at a time (242 VGPRs): the
+// number of ranges that minimises rounds x (time of a workgroup + its fixed cost) -- whole rounds of 256 workgroups, e.g.
+// N = 8192: 528 tiles x 16 ranges = 33 rounds exactly, where 3 ranges left the 7th round 19 % full
+static uint32_t mfma_allpairs_ranges(uint32_t N, uint32_t n_chunks, uint32_t tile_pairs)
+{
+    uint32_t ranges = 1;
+    const double cu_rate = 7.0e14 / 256.0, fixed = 10.0e-6;
+    double best = 1.0e300;
+    // (every range stores its own N x N slice of partial counts: at most ~8 GB of them)
+    const uint32_t r_mem = (uint32_t)std::max<uint64_t>(1, (8ull << 30) / ((uint64_t)N * N * 4));
+    const uint32_t r_hi = std::min(std::min(n_chunks, r_mem), std::max(1u, (256u * 64u) / tile_pairs));
+    for (uint32_t r = 1; r <= r_hi; r++) {
+        const uint32_t c = (n_chunks + r - 1u) / r, rr = (n_chunks + c - 1u) / c;     // ranges actually launched
+        const double blocks = (double)tile_pairs * rr;
+        // rounds x (a workgroup's chunks + table, stores) + the slices written and read once more
+        const double t = std::ceil(blocks / 256.0) * (65536.0 * (double)c * PS_MF_CHUNK_DW * 16.0 / cu_rate + fixed)
+                         + (rr > 1u ? (double)rr * N * N * 4.0 * 1.5 / 4.0e12 : 0.0);
+        if (t < best) { best = t; ranges = rr; }
+    }
+    return ranges;
+}
+
 static int pair_counts_device(ps_population *p, uint64_t P, const uint32_t *d_r1, const uint32_t *d_r2,
                               const uint32_t *d_perm, uint32_t *d_a, uint32_t *d_b, hipStream_t st)
 {
@@ -2042,25 +2075,7 @@ static int pair_counts_device(ps_population *p, uint64_t P, const uint32_t *d_r1
             const uint32_t ntile = (N + PS_MF_TILE - 1u) / PS_MF_TILE;
             const uint32_t tile_pairs = ntile * (ntile + 1u) / 2u;
             const uint32_t n_chunks = WT / PS_MF_CHUNK_DW;
-            // (tile, chunk range) workgroups, one 8-wave workgroup per CU at a time (242 VGPRs): the number of ranges that
-            // minimises rounds x (time of a workgroup + its fixed cost) -- whole rounds of 256 workgroups, e.g. N = 8192:
-            // 528 tiles x 16 ranges = 33 rounds exactly, where 3 ranges left the 7th round 19 % full
-            uint32_t ranges = 1;
-            {
-                const double cu_rate = 7.0e14 / 256.0, fixed = 10.0e-6;
-                double best = 1.0e300;
-                // (every range stores its own N x N slice of partial counts: at most ~8 GB of them)
-                const uint32_t r_mem = (uint32_t)std::max<uint64_t>(1, (8ull << 30) / ((uint64_t)N * N * 4));
-                const uint32_t r_hi = std::min(std::min(n_chunks, r_mem), std::max(1u, (256u * 64u) / tile_pairs));
-                for (uint32_t r = 1; r <= r_hi; r++) {
-                    const uint32_t c = (n_chunks + r - 1u) / r, rr = (n_chunks + c - 1u) / c;     // ranges actually launched
-                    const double blocks = (double)tile_pairs * rr;
-                    // rounds x (a workgroup's chunks + table, stores) + the slices written and read once more
-                    const double t = std::ceil(blocks / 256.0) * (65536.0 * (double)c * PS_MF_CHUNK_DW * 16.0 / cu_rate + fixed)
-                                     + (rr > 1u ? (double)rr * N * N * 4.0 * 1.5 / 4.0e12 : 0.0);
-                    if (t < best) { best = t; ranges = rr; }
-                }
-            }
+            uint32_t ranges = mfma_allpairs_ranges(N, n_chunks, tile_pairs);
             const uint32_t cpr = (n_chunks + ranges - 1u) / ranges;
             ranges = (n_chunks + cpr - 1u) / cpr;          // (every range holds at least one chunk: every slice is written)
             if (p->H_cap < (uint64_t)N * N * ranges) {
@@ -2085,8 +2100,8 @@ static int pair_counts_device(ps_population *p, uint64_t P, const uint32_t *d_r1
                 p->last_pair_form = PS_PAIR_FORM_ALLPAIRS_MFMA_SIGNED;
             } else
             if (fp4) {
-                HIPCHK(hipFuncSetAttribute((const void *)core_allpairs_mfma_fp4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(core_allpairs_mfma_fp4_kernel, dim3(tile_pairs, ranges), dim3(512), lds, st, p->d_pack2, WT, N, p->d_H, cpr, n_chunks, ntile);
+                HIPCHK(hipFuncSetAttribute((const void *)core_allpairs_mfma_fp4_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL(core_allpairs_mfma_fp4_kernel<false>, dim3(tile_pairs, ranges), dim3(512), lds, st, p->d_pack2, WT, N, p->d_H, cpr, n_chunks, ntile);
                 p->last_pair_form = PS_PAIR_FORM_ALLPAIRS_MFMA_FP4;
             } else {
             HIPCHK(hipFuncSetAttribute((const void *)core_allpairs_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2296,11 +2311,247 @@ extern "C" int ps_pairwise_distances(ps_population *p, uint64_t P, const uint32_
     return PS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Core D-avg (population.rs:753-784 with get_distance :132-137).  Everything is in OUTPUT order: the strings
+// are packed through the row slot, so the counts, the order of every row's fold and the result need no permutation.
+//   form 1, whole matrix: the all-pairs FP4 contraction's triangle into d_H (the cap of pair_counts_device), then
+//           core_average_from_h_kernel;
+//   form 2, banded: the contraction over (rows of a band) x (all columns) into band counts, then core_average_from_counts_kernel
+//           -- large populations, row shards and ps_multi (the shards' band counts are added on shard 0 first);
+//   form 3, generic (matrices that are not one-hot): the xor + popcount all-pairs tiles and the whole-matrix fold for
+//           nibble matrices in internal order, else core_band_counts_simple and the banded fold.
+// ---------------------------------------------------------------------------
+static const uint64_t PS_CDAVG_SCRATCH = 1ull << 30;     // words of band counts (4 GB; a cfg4 core handle already holds 157 GB)
+
+// rows [c0, c_end) of the output order in bands of `band` rows (c0 and band: whole 256-tiles), counts row pitch ld
+struct core_davg_bands { uint32_t c0, c_end, band; uint64_t ld; };
+
+static core_davg_bands core_davg_plan_bands(const ps_population *p, uint64_t first, uint64_t count)
+{
+    const uint64_t N = p->cfg.pop_size;
+    core_davg_bands b;
+    b.c0 = (uint32_t)(first & ~255ull);
+    b.c_end = (uint32_t)(first + count);
+    b.ld = (N + 63) & ~63ull;
+    const uint64_t span = ((uint64_t)(b.c_end - b.c0) + 255) & ~255ull;
+    // (sized from the rows the call serves; at most 65280 rows: the generic kernel's grid.y)
+    const uint64_t band = p->core_davg_band ? ((uint64_t)p->core_davg_band + 255) & ~255ull
+                                            : std::max<uint64_t>(256, (PS_CDAVG_SCRATCH / b.ld) & ~255ull);
+    b.band = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(band, span), 65280);
+    return b;
+}
+
+// the blocked 2-bit strings of core_allpairs_mfma_fp4_kernel, in output order when d_slot is given
+static int core_davg_pack(ps_population *p, const uint32_t *d_slot, hipStream_t st, uint32_t *WT_out)
+{
+    const uint32_t N = (uint32_t)p->cfg.pop_size, rows = (uint32_t)p->cfg.ncols;
+    const uint32_t WT = ((rows + 15u) / 16u + PS_PT_WB - 1u) / PS_PT_WB * PS_PT_WB;
+    const uint64_t need = (uint64_t)((N + 31u) / 32u * 32u) * WT;
+    if (p->pack2_cap < need) {
+        if (p->d_pack2) HIPCHK(hipFree(p->d_pack2));
+        p->d_pack2 = nullptr;
+        p->pack2_cap = 0;
+        HIPCHK(hipMalloc(&p->d_pack2, need * sizeof(uint32_t)));
+        p->pack2_cap = need;
+    }
+    const uint64_t ptiles = (uint64_t)((N + PS_PT_IB - 1u) / PS_PT_IB) * (WT / PS_PT_WB);
+    if (ptiles > 0x7FFFFFFFull) return ps_fail(PS_ERR_INVALID, "matrix too large for the transposed distance form");
+    if (d_slot) core_packT_kernel<false, true, false, true><<<dim3((uint32_t)ptiles), 256, 0, st>>>(p->state, N, p->pitch, rows, p->d_pack2, WT, d_slot);
+    else core_packT_kernel<false, true><<<dim3((uint32_t)ptiles), 256, 0, st>>>(p->state, N, p->pitch, rows, p->d_pack2, WT);
+    HIPCHK(hipGetLastError());
+    *WT_out = WT;
+    return PS_OK;
+}
+
+static int ensure_H(ps_population *p, uint64_t words)
+{
+    if (p->H_cap >= words) return PS_OK;
+    if (p->d_H) HIPCHK(hipFree(p->d_H));
+    p->d_H = nullptr;
+    p->H_cap = 0;
+    HIPCHK(hipMalloc(&p->d_H, words * sizeof(uint32_t)));
+    p->H_cap = words;
+    return PS_OK;
+}
+
+// form 1 (one-hot) and form 3 on nibble matrices in internal order: the triangle of tiles into d_H, then the fold
+static int core_davg_whole(ps_population *p, bool onehot, const uint32_t *d_slot, uint64_t first, uint64_t count, double *d_out,
+                           hipStream_t st)
+{
+    const uint32_t N = (uint32_t)p->cfg.pop_size, rows = (uint32_t)p->cfg.ncols;
+    const double L = (double)p->cfg.global_cols;
+    const uint32_t grid = (uint32_t)(((first & 15u) + count + 15u) / 16u);
+    if (onehot) {
+        uint32_t WT = 0;
+        PSCHK(core_davg_pack(p, d_slot, st, &WT));
+        const uint32_t ntile = (N + PS_MF_TILE - 1u) / PS_MF_TILE, tile_pairs = ntile * (ntile + 1u) / 2u, n_chunks = WT / PS_MF_CHUNK_DW;
+        uint32_t ranges = mfma_allpairs_ranges(N, n_chunks, tile_pairs);
+        const uint32_t cpr = (n_chunks + ranges - 1u) / ranges;
+        ranges = (n_chunks + cpr - 1u) / cpr;
+        PSCHK(ensure_H(p, (uint64_t)N * N * ranges));
+        const uint32_t lds = 256u * 16u * 16u;
+        // (FP4 while a range holds fewer than 2^24 sites -- exact f32 sums --, else the i8 form: exact i32)
+        if ((uint64_t)cpr * PS_MF_CHUNK_DW * 16u < (1u << 24)) {
+            HIPCHK(hipFuncSetAttribute((const void *)core_allpairs_mfma_fp4_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(core_allpairs_mfma_fp4_kernel<false>, dim3(tile_pairs, ranges), dim3(512), lds, st, p->d_pack2, WT, N, p->d_H, cpr, n_chunks, ntile);
+        } else {
+            HIPCHK(hipFuncSetAttribute((const void *)core_allpairs_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(core_allpairs_mfma_kernel, dim3(tile_pairs, ranges), dim3(512), lds, st, p->d_pack2, WT, N, p->d_H, cpr, n_chunks, ntile);
+        }
+        if (ranges > 1u) core_allpairs_sum_slices_kernel<<<N, 256, 0, st>>>(p->d_H, N, ranges);
+        core_average_from_h_kernel<8u><<<grid, 320, 0, st>>>(p->d_H, N, (uint32_t)first, (uint32_t)count, L, d_out);
+    } else {
+        const uint32_t WA = 32u, ntile = (N + 127u) / 128u;
+        const uint32_t lds = 2u * 128u * ((WA >> 2) + 1u) * 16u;
+        PSCHK(ensure_H(p, (uint64_t)N * N));
+        HIPCHK(hipMemsetAsync(p->d_H, 0, (uint64_t)N * N * sizeof(uint32_t), st));
+        const uint32_t tile_pairs = ntile * (ntile + 1u) / 2u;
+        const uint32_t n_chunks = (rows + WA * 8u - 1u) / (WA * 8u);
+        uint32_t ranges = std::max(1u, std::min(n_chunks, (256u * 16u + tile_pairs - 1u) / tile_pairs));
+        const uint32_t cpr = (n_chunks + ranges - 1u) / ranges;
+        ranges = (n_chunks + cpr - 1u) / cpr;
+        core_allpairs_kernel<<<dim3(tile_pairs, ranges), 256, lds, st>>>(p->state, N, p->pitch, rows, p->d_H, WA, cpr, ntile);
+        core_average_from_h_kernel<7u><<<grid, 320, 0, st>>>(p->d_H, N, (uint32_t)first, (uint32_t)count, L, d_out);
+    }
+    HIPCHK(hipGetLastError());
+    return PS_OK;
+}
+
+// phase 1 of one handle's sites for a banded call, prepared once: the strings (one-hot matrices) and the chunk ranges, or the
+// generic kernel's row slot; the band counts' scratch (x ranges) allocated
+struct core_davg_src { bool fp4; uint32_t WT, n_chunks, ranges, cpr; const uint32_t *slot; };
+
+static int core_davg_prepare(ps_population *p, const core_davg_bands &b, bool fp4, const uint32_t *d_slot, hipStream_t st,
+                             core_davg_src *o)
+{
+    const uint32_t N = (uint32_t)p->cfg.pop_size, rows = (uint32_t)p->cfg.ncols;
+    *o = core_davg_src{ fp4 && rows > 0, 0, 0, 1, 0, d_slot };
+    const uint64_t slice = (uint64_t)b.band * b.ld;
+    if (o->fp4) {
+        PSCHK(core_davg_pack(p, d_slot, st, &o->WT));
+        o->n_chunks = o->WT / PS_MF_CHUNK_DW;
+        // chunk ranges: at least 4 workgroups per CU, each range below 2^24 sites (exact f32 sums), scratch permitting
+        const uint32_t ntile = (N + PS_MF_TILE - 1u) / PS_MF_TILE, blocks = b.band / PS_MF_TILE * ntile;
+        const uint32_t rmin = (o->n_chunks + 131070u) / 131071u;
+        uint32_t r = std::min(o->n_chunks, std::max(rmin, (1024u + blocks - 1u) / blocks));
+        r = std::max(rmin, std::min(r, (uint32_t)std::max<uint64_t>(1, PS_CDAVG_SCRATCH / slice)));
+        o->cpr = (o->n_chunks + r - 1u) / r;
+        o->ranges = (o->n_chunks + o->cpr - 1u) / o->cpr;
+    }
+    const uint64_t need = slice * o->ranges;
+    if (p->cdavg_cap < need) {
+        if (p->d_cdavg) HIPCHK(hipFree(p->d_cdavg));
+        p->d_cdavg = nullptr;
+        p->cdavg_cap = 0;
+        HIPCHK(hipMalloc(&p->d_cdavg, need * sizeof(uint32_t)));
+        p->cdavg_cap = need;
+    }
+    return PS_OK;
+}
+
+// h(i, j) over this handle's sites for rows [lo, lo + nrows) x all N columns, into p->d_cdavg (row pitch b.ld)
+static int core_davg_band_counts(ps_population *p, const core_davg_src &src, const core_davg_bands &b, uint32_t lo, uint32_t nrows,
+                                 hipStream_t st)
+{
+    const uint32_t N = (uint32_t)p->cfg.pop_size, rows = (uint32_t)p->cfg.ncols;
+    uint32_t *C = p->d_cdavg;
+    const uint64_t n = (uint64_t)nrows * b.ld, slice = (uint64_t)b.band * b.ld;
+    if (rows == 0) {
+        HIPCHK(hipMemsetAsync(C, 0, n * sizeof(uint32_t), st));
+    } else if (src.fp4) {
+        const uint32_t ntile = (N + PS_MF_TILE - 1u) / PS_MF_TILE, rtiles = (nrows + PS_MF_TILE - 1u) / PS_MF_TILE;
+        const uint32_t lds = 256u * 16u * 16u;
+        HIPCHK(hipFuncSetAttribute((const void *)core_allpairs_mfma_fp4_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(core_allpairs_mfma_fp4_kernel<true>, dim3(rtiles * ntile, src.ranges), dim3(512), lds, st, p->d_pack2, src.WT, N,
+                           C, src.cpr, src.n_chunks, ntile, lo / PS_MF_TILE, lo + nrows, b.ld, slice);
+        for (uint32_t r = 1; r < src.ranges; r++)
+            u32_add_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(C, C + r * slice, n);
+    } else {
+        core_band_counts_simple<<<dim3((N + 255u) / 256u, nrows), 256, 0, st>>>(p->state, p->pitch, rows, N, src.slot, lo, C, b.ld);
+    }
+    HIPCHK(hipGetLastError());
+    return PS_OK;
+}
+
+// phase 2 of a band: rows [max(first, lo), lo + nrows) of the call's [first, ...) into d_out
+static int core_davg_band_fold(const uint32_t *C, const core_davg_bands &b, uint32_t N, uint32_t lo, uint32_t nrows, uint64_t first,
+                               double L, double *d_out, hipStream_t st)
+{
+    const uint32_t i_lo = std::max<uint32_t>((uint32_t)first, lo), i_cnt = lo + nrows - i_lo;
+    core_average_from_counts_kernel<<<((i_lo & 15u) + i_cnt + 15u) / 16u, 320, 0, st>>>(C, b.ld, N, lo, i_lo, i_cnt, L, d_out + (i_lo - first));
+    HIPCHK(hipGetLastError());
+    return PS_OK;
+}
+
+// the form of a call (core_davg_form; 0 = choose): one-hot matrices take the whole-matrix form where the N x N counts fit
+// pair_counts_device's cap and every row is wanted, else the banded form; other matrices the generic form
+static int core_davg_form_of(const ps_population *p, uint64_t count)
+{
+    const uint64_t N = p->cfg.pop_size;
+    const bool fits = N * N * 4 <= (8ull << 30);
+    if (!p->onehot_safe || p->cfg.ncols == 0) return 3;
+    switch (p->core_davg_form) {
+    case 1: return fits ? 1 : 2;
+    case 2: return 2;
+    case 3: return 3;
+    default: return fits && count == N ? 1 : 2;
+    }
+}
+
+// rows [first, first + count) of the core D-avg of this handle (all sites: ncols == global_cols) into d_out (count values)
+static int core_average_distance_device(ps_population *p, uint64_t first, uint64_t count, double *d_out, hipStream_t st)
+{
+    const uint32_t N = (uint32_t)p->cfg.pop_size;
+    const double L = (double)p->cfg.global_cols;
+    const uint32_t *slot = nullptr;
+    PSCHK(rows_current(p, &slot));
+    const uint32_t *d_slot = slot ? p->d_row_slot : nullptr;
+    int form = core_davg_form_of(p, count);
+    // (form 3 on a one-hot matrix is the generic path as well: the tests force it)
+    const bool onehot = p->onehot_safe && p->cfg.ncols > 0;
+    if (form == 1) return core_davg_whole(p, true, d_slot, first, count, d_out, st);
+    if (form == 3 && p->nibble_safe && !d_slot && p->cfg.ncols > 0 && (uint64_t)N * N * 4 <= (8ull << 30))
+        return core_davg_whole(p, false, nullptr, first, count, d_out, st);
+    const core_davg_bands b = core_davg_plan_bands(p, first, count);
+    core_davg_src src;
+    PSCHK(core_davg_prepare(p, b, onehot && form == 2, d_slot, st, &src));
+    for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) {
+        const uint32_t nrows = std::min(b.band, b.c_end - lo);
+        PSCHK(core_davg_band_counts(p, src, b, lo, nrows, st));
+        PSCHK(core_davg_band_fold(p->d_cdavg, b, N, lo, nrows, first, L, d_out, st));
+    }
+    return PS_OK;
+}
+
+static int core_davg_check(const ps_population *p)
+{
+    if (p->cfg.pop_size < 2) return ps_fail(PS_ERR_INVALID, "average_distance needs pop_size >= 2");
+    if (p->cfg.ncols != p->cfg.global_cols)
+        return ps_fail(PS_ERR_INVALID, "average_distance of the core matrix sums over all %llu sites; this handle is one site shard "
+                                       "([%llu, %llu)): use ps_multi_average_distance", (unsigned long long)p->cfg.global_cols,
+                       (unsigned long long)p->cfg.col_offset, (unsigned long long)(p->cfg.col_offset + p->cfg.ncols));
+    return PS_OK;
+}
+
+static int core_average_distance_rows(ps_population *p, uint64_t first, uint64_t count, double *out)
+{
+    PSCHK(use_device(p));
+    double *d_out = nullptr;
+    HIPCHK(hipMalloc(&d_out, count * sizeof(double)));
+    PSCHK(core_average_distance_device(p, first, count, d_out, p->stream));
+    HIPCHK(hipMemcpyAsync(out, d_out, count * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipFree(d_out));
+    return PS_OK;
+}
+
 extern "C" int ps_average_distance(ps_population *p, double *out)
 {
     if (!p || !out) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (p->cfg.core)
-        return ps_fail(PS_ERR_INVALID, "average_distance is only reached on the accessory matrix (main.rs:439)");
+    if (p->cfg.core) {
+        PSCHK(core_davg_check(p));
+        return core_average_distance_rows(p, 0, p->cfg.pop_size, out);
+    }
     if (p->cfg.pop_size < 2) return ps_fail(PS_ERR_INVALID, "average_distance needs pop_size >= 2");
     PSCHK(use_device(p));
     double *d_out = nullptr;
@@ -2320,12 +2571,14 @@ extern "C" int ps_average_distance(ps_population *p, double *out)
 extern "C" int ps_average_distance_rows(ps_population *p, uint64_t first, uint64_t count, double *out)
 {
     if (!p || !out) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (p->cfg.core)
-        return ps_fail(PS_ERR_INVALID, "average_distance is only reached on the accessory matrix (main.rs:439)");
     const uint64_t N = p->cfg.pop_size;
     if (N < 2) return ps_fail(PS_ERR_INVALID, "average_distance needs pop_size >= 2");
     if (count < 1 || first >= N || count > N - first) return ps_fail(PS_ERR_INVALID, "rows [%llu, +%llu) outside the population",
                                                                      (unsigned long long)first, (unsigned long long)count);
+    if (p->cfg.core) {
+        PSCHK(core_davg_check(p));
+        return core_average_distance_rows(p, first, count, out);
+    }
     if (p->d.G == 0) {
         // no accessory genes: every pair is 1 - core_genes / core_genes (get_distance, population.rs:144-145)
         std::vector<double> all(N);
@@ -4058,6 +4311,77 @@ extern "C" int ps_multi_pairwise_distances(ps_multi *m, double *core_out, double
     }
     ps_sim *s0 = m->shard[0];
     return ps_pairwise_distances(s0->acc, P, s0->r1.data(), s0->r2.data(), acc_out);
+}
+
+// Population::average_distance (population.rs:753-784) of the run's core matrix (core != 0) or of its accessory matrix.  Core:
+// band by band, every shard counts its own sites (in output order, through its own row slot), shard 0's device adds the
+// shards' counts as multi_core_counts adds the pair numerators and folds with L = core_size.  The tuning keys
+// of shard 0's core handle apply.  Accessory: the replicas are identical, shard 0's handle answers.
+extern "C" int ps_multi_average_distance(ps_multi *m, int core, double *out)
+{
+    if (!m || !out) return ps_fail(PS_ERR_INVALID, "null argument");
+    if (!core) return ps_average_distance(m->shard[0]->acc, out);
+    const size_t K = m->shard.size();
+    if (K == 1) return ps_average_distance(m->shard[0]->core, out);
+    ps_population *c0 = m->shard[0]->core;
+    const uint32_t N = (uint32_t)m->prm.pop_size;
+    if (N < 2) return ps_fail(PS_ERR_INVALID, "average_distance needs pop_size >= 2");
+    PSCHK(ps_multi_sync(m));
+    const core_davg_bands b = core_davg_plan_bands(c0, 0, N);
+    // (one-hot on every shard: the banded FP4 form on each; otherwise the generic kernel on each)
+    bool onehot = true;
+    for (size_t k = 0; k < K; k++) onehot = onehot && m->shard[k]->core->onehot_safe && c0->core_davg_form != 3;
+    std::vector<core_davg_src> src(K);
+    PSCHK(multi_for_each(m, [&](size_t k) {
+        ps_population *c = m->shard[k]->core;
+        PSCHK(use_device(c));
+        const uint32_t *slot = nullptr;
+        PSCHK(rows_current(c, &slot));
+        return core_davg_prepare(c, b, onehot, slot ? c->d_row_slot : nullptr, c->stream, &src[k]);
+    }));
+    PSCHK(use_device(c0));
+    double *d_out = nullptr;
+    uint32_t *d_land = nullptr;         // (without peer access: a peer's band counts copied over first)
+    HIPCHK(hipMalloc(&d_out, (uint64_t)N * sizeof(double)));
+    if (!m->peers_ok) HIPCHK(hipMalloc(&d_land, (uint64_t)b.band * b.ld * sizeof(uint32_t)));
+    int rc = PS_OK;
+    for (uint32_t lo = b.c0; rc == PS_OK && lo < b.c_end; lo += b.band) {
+        const uint32_t nrows = std::min(b.band, b.c_end - lo);
+        const uint64_t n = (uint64_t)nrows * b.ld;
+        rc = multi_for_each(m, [&](size_t k) {
+            ps_population *c = m->shard[k]->core;
+            PSCHK(use_device(c));
+            PSCHK(core_davg_band_counts(c, src[k], b, lo, nrows, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            return (int)PS_OK;
+        });
+        if (rc != PS_OK) break;
+        rc = [&]() -> int {
+            PSCHK(use_device(c0));
+            for (size_t k = 1; k < K; k++) {
+                ps_population *c = m->shard[k]->core;
+                if (m->peers_ok) {
+                    u32_add_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, c0->stream>>>(c0->d_cdavg, c->d_cdavg, n);
+                } else {
+                    HIPCHK(hipMemcpyPeerAsync(d_land, c0->device, c->d_cdavg, c->device, n * sizeof(uint32_t), c0->stream));
+                    u32_add_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, c0->stream>>>(c0->d_cdavg, d_land, n);
+                }
+                HIPCHK(hipGetLastError());
+            }
+            PSCHK(core_davg_band_fold(c0->d_cdavg, b, N, lo, nrows, 0, (double)m->prm.core_size, d_out, c0->stream));
+            // (the shards' counts are read: the next band may overwrite them)
+            HIPCHK(hipStreamSynchronize(c0->stream));
+            return PS_OK;
+        }();
+    }
+    if (rc == PS_OK) {
+        PSCHK(use_device(c0));
+        HIPCHK(hipMemcpy(out, d_out, (uint64_t)N * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    (void)hipSetDevice(c0->device);
+    (void)hipFree(d_out);
+    if (d_land) (void)hipFree(d_land);
+    return rc;
 }
 
 // Population::write for both matrices (main.rs:550-553): every line of <outpref>_core_genome.csv is the

@@ -234,6 +234,12 @@ class MultiSimulation:
         check(self._lib.ps_multi_pairwise_distances(self._h, core, acc))
         return core, acc
 
+    def average_distance(self, core=True):
+        """population.rs:753-784 of the run's core matrix (the shards' counts summed) or of its accessory matrix"""
+        out = np.zeros(self.params.pop_size, np.float64)
+        check(self._lib.ps_multi_average_distance(self._h, int(bool(core)), out))
+        return out
+
     def write(self, outpref):
         check(self._lib.ps_multi_write(self._h, str(outpref).encode()))
 
