@@ -94,6 +94,29 @@ int ps_read_matrix(ps_population *p, uint8_t *rows);
 int ps_set_rates(ps_population *p, int n_comp, const double *lam_mut, const double *lam_rec,
                  const uint64_t *comp_begin, const uint64_t *comp_end);
 
+/* The same rates with the reference's WEIGHT VECTORS instead of ranges: mutate_alleles draws the column of
+ * every event from `weighted_dist[c]` (population.rs:467-471, :503, :527), recombine the accessory gene of an HGT event from
+ * `locus_weights[c]` restricted to the donor's present genes (:544-549, :636-680).  w_mut / w_rec: n_comp x global_cols f32,
+ * row-major, over the GLOBAL columns even on a site shard (normalisation is global: a shard equals its columns of the whole
+ * run bit for bit); n_comp 1..PS_MAX_SITE_COMP.  Column s mutates at rate sum_c lam_mut[c] w_mut[c][s] / W_c (overlapping
+ * compartments add); the gene of an HGT event of compartment c is drawn in proportion to w_rec[c][g] among the donor's
+ * present genes, weights quantised to 16 bits of the compartment's largest, a gene of weight 0 never, no event if none
+ * qualifies (:672); at most 65536 genes.  Core handles: w_rec = NULL -- the reference draws the site of a core HR event
+ * uniformly whatever the weights say (:687-689) -- and the lam_rec of the compartments add.  Negative or non-finite weights,
+ * and an all-zero vector under a non-zero rate (WeightedIndex::new would panic), fail with PS_ERR_INVALID and a message.
+ * When every vector is the 0/1 mask of one contiguous range, w_mut[c] == w_rec[c], the ranges disjoint and n_comp <= 2
+ * (core: one compartment, every site 1), this call IS ps_set_rates with those ranges: same plan, same bits.  Rates and
+ * weights are state of the handle, set together, for the reason given above; ps_set_rates switches back. */
+#define PS_MAX_SITE_COMP 8
+int ps_set_site_rates(ps_population *p, int n_comp, const double *lam_mut, const double *lam_rec,
+                      const float *w_mut, const float *w_rec);
+/* The tables ps_set_site_rates hands to the kernels, computed on the host alone (no device is touched).  plan_out[5]:
+ * core k, R, cshift, has_events (accessory: 0), then 1 if the vectors are ranges (the ps_set_rates path).  thr_out: core
+ * 7 x global_cols level-2 thresholds (site-major), accessory global_cols flip thresholds.  wq_out (accessory only):
+ * n_comp x global_cols quantised HGT weights.  Any output may be NULL. */
+int ps_site_tables(int core, uint64_t global_cols, int n_comp, const double *lam_mut, const double *lam_rec,
+                   const float *w_mut, const float *w_rec, uint32_t *plan_out, uint32_t *thr_out, uint16_t *wq_out);
+
 /* Population::next_generation(&sample) (population.rs:450-465) */
 int ps_next_generation(ps_population *p, const uint32_t *sample);
 /* Population::mutate_alleles (population.rs:467-542), generation = loop index j of main.rs:429 */
@@ -312,6 +335,10 @@ void ps_sim_destroy(ps_sim *s);
  * until the simulation's next generation. */
 int ps_sim_run(ps_sim *s, uint32_t first_generation, uint32_t count);
 int ps_sim_sync(ps_sim *s);
+/* Run the loop with per-site weights (ps_set_site_rates on both handles; the rates stay those of the parameters).  w_core:
+ * core_size values; w_acc_mut / w_acc_rec: n_comp x pan_size (n_comp of ps_sim_derive), given together.  NULL leaves that
+ * matrix as it is.  Call it between runs; it waits for queued generations. */
+int ps_sim_set_site_weights(ps_sim *s, const float *w_core, const float *w_acc_mut, const float *w_acc_rec);
 /* Shard the HGT donors over the site shards of this run (shard_rank / shard_count of the parameters) and exchange the
  * deltas through `fn` once per generation (ps_set_donor_shard).  Every shard of the run must do the same. */
 int ps_sim_set_exchange(ps_sim *s, ps_exchange_fn fn, void *ctx);
@@ -393,6 +420,9 @@ int ps_multi_pairwise_distances(ps_multi *m, double *core_out, double *acc_out);
 /* population.rs:753-784 of the run's core matrix (core != 0: every shard counts its sites, shard 0 adds and folds; the tuning
  * keys of shard 0's core handle apply) or of its accessory matrix (core == 0: shard 0's replica).  out: pop_size values. */
 int ps_multi_average_distance(ps_multi *m, int core, double *out);
+/* ps_sim_set_site_weights for a ps_multi run is NOT plumbed yet: always PS_ERR_INVALID, with a message that says what to do
+ * instead (one ps_sim per shard). */
+int ps_multi_set_site_weights(ps_multi *m, const float *w_core, const float *w_acc_mut, const float *w_acc_rec);
 /* main.rs:550-553: <outpref>_core_genome.csv (lines assembled from the shards' columns) and _pangenome.csv */
 int ps_multi_write(ps_multi *m, const char *outpref);
 

@@ -69,6 +69,8 @@ SIGNATURES = {
     "ps_load_matrix": (_int, [_vp, _u8p]),
     "ps_read_matrix": (_int, [_vp, _u8p]),
     "ps_set_rates": (_int, [_vp, _int, _f64p, _f64p, _u64p, _u64p]),
+    "ps_set_site_rates": (_int, [_vp, _int, _f64p, _f64p, _vp, _vp]),
+    "ps_site_tables": (_int, [_int, _u64, _int, _f64p, _f64p, _vp, _vp, _vp, _vp, _vp]),
     "ps_next_generation": (_int, [_vp, _u32p]),
     "ps_mutate_alleles": (_int, [_vp, _u32]),
     "ps_recombine": (_int, [_vp, _u32]),
@@ -107,6 +109,7 @@ SIGNATURES = {
     "ps_sim_run": (_int, [_vp, _u32, _u32]),
     "ps_sim_sync": (_int, [_vp]),
     "ps_sim_set_exchange": (_int, [_vp, _vp, _vp]),
+    "ps_sim_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_sim_emulate_exchange": (_int, [_vp, _int]),
     "ps_sim_exchange_stats": (_int, [_vp, _int, C.POINTER(_u64), C.POINTER(_u64)]),
     "ps_sim_emulated_link_time": (_int, [_vp, _int, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
@@ -136,6 +139,7 @@ SIGNATURES = {
     "ps_multi_pairwise_counts": (_int, [_vp, _u32p]),
     "ps_multi_pairwise_distances": (_int, [_vp, _f64p, _f64p]),
     "ps_multi_average_distance": (_int, [_vp, _int, _f64p]),
+    "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }
 

@@ -83,6 +83,7 @@ struct acc_step_args {
     acc_dims d;
     uint32_t gen, k0, k1;
     ps_acc_plan plan;
+    const uint32_t *gene_thr; // per-gene rates: 64 * GW flip thresholds, one per gene (zero behind G); null = plan
 };
 
 // 64-bit mask of the genes of row word gw that lie in [gb, ge)
@@ -105,7 +106,7 @@ __device__ __forceinline__ uint64_t ps_word_range_mask(uint32_t gw, uint32_t gb,
 // (Round 2's form gathered one parent WORD of the gene-major view per (individual, gene) -- 8 bytes read per
 // bit at N = 65536, 0.63 ms for a 33 MB matrix -- and rebuilt the gene-major view with one ballot per gene;
 // that view is now rebuilt only when someone asks for gene frequencies.)
-template <bool DO_GATHER, bool DO_MUT>
+template <bool DO_GATHER, bool DO_MUT, bool WT = false>
 __global__ void __launch_bounds__(256) acc_step_rows_kernel(acc_step_args a)
 {
     const acc_dims d = a.d;
@@ -116,7 +117,19 @@ __global__ void __launch_bounds__(256) acc_step_rows_kernel(acc_step_args a)
     const uint32_t p = DO_GATHER ? a.idx[i] : i;
     if (DO_GATHER && a.idx_out && gw == 0) a.idx_out[i] = p;
     uint64_t word = a.srcI[(uint64_t)p * d.GW + gw];
-    if (DO_MUT) {
+    if (DO_MUT && WT) {
+        // per-gene rates: the same 16 Philox blocks, every word against ITS gene's threshold (four thresholds per 16-byte load)
+        const uint4 *thr = (const uint4 *)(a.gene_thr + (size_t)gw * 64u);
+        uint32_t lt[2] = { 0u, 0u };
+#pragma unroll
+        for (uint32_t j = 0; j < 16u; j++) {
+            const ps_u4 r = ps_philox(gw * 16u + j, i, a.gen, PS_STREAM_ACC_MUT, a.k0, a.k1);
+            const uint4 t = thr[j];
+            const uint32_t b = 4u * j;
+            lt[b >> 5] |= ((r.x < t.x ? 1u : 0u) | (r.y < t.y ? 2u : 0u) | (r.z < t.z ? 4u : 0u) | (r.w < t.w ? 8u : 0u)) << (b & 31u);
+        }
+        word ^= ((uint64_t)lt[1] << 32) | lt[0];
+    } else if (DO_MUT) {
         const uint32_t t0 = a.plan.n_comp > 0 ? a.plan.flip_thr[0] : 0u, t1 = a.plan.n_comp > 1 ? a.plan.flip_thr[1] : 0u;
         const uint64_t m0 = a.plan.n_comp > 0 ? ps_word_range_mask(gw, a.plan.comp_begin[0], a.plan.comp_end[0]) : 0ull;
         // (a gene in both ranges takes the LAST compartment's threshold, as the per-gene loop of round 2 did)
@@ -178,6 +191,11 @@ struct acc_hgt_args {
     // donor and the recipient's bit is ORed, so the union over any partition of the donors is the unsharded result.
     uint32_t dn_lo, dn_cnt;
     uint32_t bin_prio;             // bin pass: wave priority (s_setprio) while it runs beside a sweep (0 = leave it)
+    // per-gene HGT weights (the WT variants of the donor kernels): the compartment's quantised weights (one u16 per
+    // gene), the bit mask of its genes of non-zero weight (GW words), and where the u32 prefix sums sit behind a donor's list
+    const uint16_t *wq[PS_MAX_COMP];
+    const uint64_t *wnz[PS_MAX_COMP];
+    uint32_t pref_off;             // in u16 units from the start of the list, a multiple of 8
 };
 
 // k_d for every (compartment, donor): kmin + number of thresholds <= u (ps_poisson_table).
@@ -236,15 +254,62 @@ __device__ __forceinline__ uint32_t ps_wave_gene_list(const uint64_t *row, uint3
     return base;
 }
 
+// The same under per-gene weights: the present genes of non-zero weight and, in pref[], the inclusive prefix sums of their
+// quantised weights (below 2^32: at most 65536 genes of at most 65535 each); *total = the last of them.
+__device__ __forceinline__ uint32_t ps_wave_gene_list_w(const uint64_t *row, uint32_t GW, uint32_t G, const uint64_t *wnz, const uint16_t *wq,
+                                                        uint16_t *list, uint32_t *pref, uint32_t lane, uint32_t *total)
+{
+    uint32_t base = 0, wbase = 0;
+    for (uint32_t gw0 = 0; gw0 * 64u < G; gw0 += 64u) {
+        const uint32_t gw = gw0 + lane;
+        uint64_t word = 0;
+        if (gw < GW) word = row[gw] & wnz[gw];          // (wnz has no bit at or behind G)
+        const uint32_t pc = __popcll(word);
+        uint32_t ws = 0;
+        for (uint64_t t = word; t; t &= t - 1ull) ws += wq[gw * 64u + (uint32_t)__builtin_ctzll(t)];
+        uint32_t incl = pc, wincl = ws;                  // inclusive wave prefix sums
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t t = __shfl_up(incl, off, 64), u = __shfl_up(wincl, off, 64);
+            if ((int)lane >= off) { incl += t; wincl += u; }
+        }
+        uint32_t pos = base + incl - pc, run = wbase + wincl - ws;
+        while (word) {
+            const uint32_t g = gw * 64u + (uint32_t)__builtin_ctzll(word);
+            word &= word - 1ull;
+            run += wq[g];
+            list[pos] = (uint16_t)g;
+            pref[pos++] = run;
+        }
+        base += __shfl(incl, 63, 64);
+        wbase += __shfl(wincl, 63, 64);
+    }
+    *total = wbase;
+    return base;
+}
+// the entry an event's word picks: x = mulhi(word, total), the first entry whose prefix sum exceeds x
+__device__ __forceinline__ uint32_t ps_weighted_pick(const uint32_t *pref, uint32_t n, uint32_t total, uint32_t word)
+{
+    const uint32_t x = ps_mulhi(word, total);
+    uint32_t lo = 0, hi = n - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pref[mid] > x) hi = mid; else lo = mid + 1u;
+    }
+    return lo;
+}
+
 // Light HGT: one 64-bit atomicOr per event.  One wave per workgroup and no static LDS, so that the
 // kernel fits beside whatever the core sweep leaves on a CU; the donor's gene list lives in dynamic
 // LDS or -- when the co-running block sweep owns the CU's LDS (cfg4 population) -- in the
 // workgroup's slice of a global scratch that stays hot in L2.  srcI must be a snapshot copy of the
 // matrix, dstI the live one.  Launched narrow by ps_sim.
+template <bool WT = false>
 __global__ void __launch_bounds__(64) acc_hgt_donor_wave_kernel(acc_hgt_args a)
 {
     extern __shared__ __attribute__((aligned(16))) uint16_t lds_list[];
     uint16_t *glist = a.list_scratch ? a.list_scratch + (uint64_t)blockIdx.x * a.list_stride : lds_list;
+    uint32_t *pref = (uint32_t *)(glist + a.pref_off);    // (WT only)
+    uint32_t wtotal = 0;
     const acc_dims d = a.d;
     const uint32_t lane = threadIdx.x;
     const uint32_t items = a.n_comp * a.dn_cnt;
@@ -257,7 +322,8 @@ __global__ void __launch_bounds__(64) acc_hgt_donor_wave_kernel(acc_hgt_args a)
         const uint32_t k = ps_hgt_count(a, c, dn);
         if (k == 0u) continue;
         __threadfence_block();                             // the previous item's list reads are done
-        const uint32_t n = ps_wave_gene_list(a.srcI + (uint64_t)dn * d.GW, d.GW, a.gb[c], a.ge[c], glist, lane);
+        const uint32_t n = WT ? ps_wave_gene_list_w(a.srcI + (uint64_t)dn * d.GW, d.GW, d.G, a.wnz[c], a.wq[c], glist, pref, lane, &wtotal)
+                              : ps_wave_gene_list(a.srcI + (uint64_t)dn * d.GW, d.GW, a.gb[c], a.ge[c], glist, lane);
         __threadfence_block();                             // the list is written (it may live in global memory)
         if (n == 0u) continue;                             // population.rs:672
         const uint32_t stream = PS_STREAM_HGT | (c << 8);
@@ -269,7 +335,7 @@ __global__ void __launch_bounds__(64) acc_hgt_donor_wave_kernel(acc_hgt_args a)
                 if (2u * jp + h >= k) break;
                 uint32_t rc = ps_mulhi(h ? r.z : r.x, d.N - 1u);
                 rc += (rc >= dn) ? 1u : 0u;                             // population.rs:618
-                const uint32_t gene = glist[ps_mulhi(h ? r.w : r.y, n)];
+                const uint32_t gene = glist[WT ? ps_weighted_pick(pref, n, wtotal, h ? r.w : r.y) : ps_mulhi(h ? r.w : r.y, n)];
                 atomicOr((unsigned long long *)&a.dstI[(uint64_t)rc * d.GW + (gene >> 6)], 1ull << (gene & 63u));
             }
         }
@@ -286,6 +352,7 @@ __global__ void __launch_bounds__(64) acc_hgt_donor_wave_kernel(acc_hgt_args a)
 #ifndef PS_HGT_BIN_BLOCKS
 #define PS_HGT_BIN_BLOCKS 2u
 #endif
+template <bool WT = false>
 __global__ void __launch_bounds__(256) acc_hgt_donor_bin_kernel(acc_hgt_args a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t sc_lds[];
@@ -295,6 +362,8 @@ __global__ void __launch_bounds__(256) acc_hgt_donor_bin_kernel(acc_hgt_args a)
     uint16_t *glist = a.list_scratch ? a.list_scratch + (uint64_t)blockIdx.x * a.list_stride
                                      : (uint16_t *)(sc_lds + ((a.parts + 3u) & ~3u));
     __shared__ uint32_t sh_n;
+    __shared__ uint32_t sh_total;                                      // (WT only)
+    const uint32_t *pref = (const uint32_t *)(glist + a.pref_off);     // (WT only)
     const acc_dims d = a.d;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t items = a.n_comp * a.dn_cnt;
@@ -312,13 +381,16 @@ __global__ void __launch_bounds__(256) acc_hgt_donor_bin_kernel(acc_hgt_args a)
         const uint32_t k = ps_hgt_count(a, c, dn);      // (every thread draws the same count: no separate counts kernel on the chain)
         if (k == 0u) continue;
         if (tid < 64u) {
-            const uint32_t m = ps_wave_gene_list(a.srcI + (uint64_t)dn * d.GW, d.GW, a.gb[c], a.ge[c], glist, lane);
-            if (tid == 0) sh_n = m;
+            uint32_t tot = 0;
+            const uint32_t m = WT ? ps_wave_gene_list_w(a.srcI + (uint64_t)dn * d.GW, d.GW, d.G, a.wnz[c], a.wq[c], glist, (uint32_t *)(glist + a.pref_off), lane, &tot)
+                                  : ps_wave_gene_list(a.srcI + (uint64_t)dn * d.GW, d.GW, a.gb[c], a.ge[c], glist, lane);
+            if (tid == 0) { sh_n = m; if (WT) sh_total = tot; }
             __threadfence_block();                         // (the list may live in global memory)
         }
         __syncthreads();
         const uint32_t n = sh_n;
         if (n == 0u) continue;                             // population.rs:672
+        const uint32_t wtotal = WT ? sh_total : 0u;
         const uint32_t stream = PS_STREAM_HGT | (c << 8);
         // one Philox block serves two events: (x, y) = (recipient, gene) words of event 2 jp, (z, w) of event 2 jp + 1
         // (beside a sweep the pass has ONE wave per SIMD: nothing hides the chain Philox -> list read -> LDS atomic -> store
@@ -347,7 +419,7 @@ __global__ void __launch_bounds__(256) acc_hgt_donor_bin_kernel(acc_hgt_args a)
             for (uint32_t e = 0; e < 2u * NBK; e++) {
                 rc[e] = ps_mulhi(wr[e], d.N - 1u);
                 rc[e] += (rc[e] >= dn) ? 1u : 0u;                       // population.rs:618
-                gene[e] = glist[ps_mulhi(wg[e], n)];
+                gene[e] = glist[WT ? ps_weighted_pick(pref, n, wtotal, wg[e]) : ps_mulhi(wg[e], n)];
                 part[e] = ps_mulhi(rc[e], a.part_magic);                // rc / rows_per_part
             }
 #pragma unroll

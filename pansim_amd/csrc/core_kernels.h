@@ -32,6 +32,7 @@ struct core_sweep_args {
     uint32_t qcap;             // wave / window sweeps: entries of a wave's candidate queue (sized by the host for the plan)
     uint32_t qcap_limit;       // tests: pretend the candidate queues / HR lists hold only this many entries (0 = their real size)
     uint32_t *wide_flags;      // window sweep: [(generation & 1) * 32] != 0 iff the first launch met a segment for the second one
+    const uint32_t *site_T;    // per-site rates: record 8 * local row = the row's seven level-2 thresholds; null = plan.T
 };
 
 typedef uint32_t ps_u32x4 __attribute__((ext_vector_type(4)));
@@ -102,10 +103,25 @@ __device__ __forceinline__ uint32_t ps_cand_word(const ps_u4 &A, uint32_t site, 
     return ~ps_noncand_word(A, cshift) & ps_site_bits(site);
 }
 
+// Level 2 under per-site rates (WT): the residual word of a cell of global site `site` is cut by the thresholds
+// of that site's 32-byte record instead of the plan's.  Level 1 (k = 0, R and cshift of the envelope) is the plan's own.  The
+// row index is clamped: lanes that work on a batch's rows outside the shard compute values nobody stores.
+template <bool WT>
+__device__ __forceinline__ ps_cell ps_classify_site(uint32_t u, const ps_core_plan &pl, const core_sweep_args &a, uint32_t site)
+{
+    if (!WT) return ps_classify(u, pl);
+    const uint4 *rec = (const uint4 *)(a.site_T + 8u * (size_t)min(site - a.site_offset, a.rows - 1u));
+    const uint4 lo = rec[0], hi = rec[1];
+    ps_core_plan sp;
+    sp.T[0] = lo.x; sp.T[1] = lo.y; sp.T[2] = lo.z; sp.T[3] = lo.w; sp.T[4] = hi.x; sp.T[5] = hi.y; sp.T[6] = hi.z;
+    return ps_classify(u, sp);
+}
+
 // Queue-free evaluation of one candidate cell from its two blocks: the allele it mutates to (0 = none) and whether it
 // receives a donor allele (then l2y is the word the donor is drawn from).  A pure function of (seed, generation, site,
 // individual): the redo paths, the inline sweep and the window sweep's donor recomputation all go through it.
-__device__ __forceinline__ ps_cell ps_cell_events(const ps_u4 &A, const ps_u4 &B, uint32_t site, uint32_t ind, uint32_t gen,
+template <bool WT>
+__device__ __forceinline__ ps_cell ps_cell_events(const core_sweep_args &a, const ps_u4 &A, const ps_u4 &B, uint32_t site, uint32_t ind, uint32_t gen,
                                                   uint32_t k0, uint32_t k1, const ps_core_plan &pl, uint32_t &l2y)
 {
     ps_cell o = { 0u, 0u };
@@ -116,7 +132,7 @@ __device__ __forceinline__ ps_cell ps_cell_events(const ps_u4 &A, const ps_u4 &B
         o.mut = code;
     } else if (code == 1u) {
         const ps_u4 l2 = ps_philox(site, ind, gen, PS_STREAM_CORE_L2, k0, k1);
-        o = ps_classify(l2.x, pl);
+        o = ps_classify_site<WT>(l2.x, pl, a, site);
         l2y = l2.y;
     }
     return o;
@@ -126,7 +142,7 @@ __device__ __forceinline__ ps_cell ps_cell_events(const ps_u4 &A, const ps_u4 &B
 // workgroup per row; every candidate is handled by its owner lane (lanes diverge), HR cells are
 // remembered in a 16-bit mask per chunk.  Correct for any rates (nothing can overflow); used when
 // the queues of core_sweep_block_kernel cannot be sized safely.
-template <bool DO_GATHER, bool DO_MUT, bool DO_HR>
+template <bool DO_GATHER, bool DO_MUT, bool DO_HR, bool WT = false>
 __global__ void __launch_bounds__(1024) core_sweep_inline_kernel(core_sweep_args a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -173,7 +189,7 @@ __global__ void __launch_bounds__(1024) core_sweep_inline_kernel(core_sweep_args
                     const uint32_t i = c * 16u + k;
                     if (i >= a.N) continue;
                     uint32_t l2y;
-                    const ps_cell cell = ps_cell_events(A, B, site, i, a.gen, a.k0, a.k1, pl, l2y);
+                    const ps_cell cell = ps_cell_events<WT>(a, A, B, site, i, a.gen, a.k0, a.k1, pl, l2y);
                     if (DO_MUT && cell.mut) ps_set_byte(d, k, cell.mut);
                     if (DO_HR && cell.hr) hm |= 1u << k;
                 }
@@ -375,7 +391,7 @@ __device__ __forceinline__ uint32_t ps_pack4(uint32_t b0, uint32_t b1, uint32_t 
 __host__ __device__ constexpr uint32_t ps_queue_bytes(uint32_t qcap) { return (qcap * 2u + 15u) & ~15u; }
 __host__ __device__ constexpr uint32_t ps_wave_lds(uint32_t qcap) { return PS_BATCH_ROWS * 1024u + ps_queue_bytes(qcap); }
 
-template <bool DO_GATHER, bool DO_MUT, bool DO_HR, bool NT = false>
+template <bool DO_GATHER, bool DO_MUT, bool DO_HR, bool NT = false, bool WT = false>
 __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_sweep_args a)
 {
 #ifdef PS_STAMP
@@ -546,7 +562,7 @@ __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_s
                     const uint32_t k = ps_bit_cell(__builtin_ctz(cmr)), cellidx = i0 + k;
                     cmr &= cmr - 1u;
                     uint32_t l2y = 0;
-                    const ps_cell cell = ps_cell_events(Ar, Br, site, cellidx, a.gen, a.k0, a.k1, pl, l2y);
+                    const ps_cell cell = ps_cell_events<WT>(a, Ar, Br, site, cellidx, a.gen, a.k0, a.k1, pl, l2y);
                     if (DO_MUT && cell.mut) row[cellidx] = (uint8_t)cell.mut;
                     if (DO_HR && cell.hr) hm |= 1u << k;
                 }
@@ -579,7 +595,7 @@ __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_s
                     const uint32_t ent = ps_entry_cell(q[e]);      // cell | row << 10 = the cell's byte address in rowbuf
                     const uint32_t cellidx = ent & 1023u, rr = ent >> 10;
                     const ps_u4 l2 = ps_philox(4u * sg + rr, cellidx, a.gen, PS_STREAM_CORE_L2, a.k0, a.k1);
-                    const ps_cell cell = ps_classify(l2.x, pl);
+                    const ps_cell cell = ps_classify_site<WT>(l2.x, pl, a, 4u * sg + rr);
                     if (DO_MUT && cell.mut) rowbuf[ent] = (uint8_t)cell.mut;
                     if (DO_HR) {
                         uint32_t out = 0;
@@ -677,6 +693,7 @@ __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_s
 __host__ __device__ constexpr uint32_t ps_window_lds(uint32_t qcap) { return PS_BATCH_ROWS * PS_WSTRIDE + ps_queue_bytes(qcap) + PS_WHR * 6u; }
 
 // post-mutation, pre-recombination value of cell (site row, individual donor), from the old generation
+template <bool WT>
 __device__ __forceinline__ uint32_t ps_donor_value(const core_sweep_args &a, const ps_core_plan &pl, const uint8_t *old_row,
                                                    uint32_t site, uint32_t donor, bool do_mut)
 {
@@ -691,7 +708,7 @@ __device__ __forceinline__ uint32_t ps_donor_value(const core_sweep_args &a, con
                 val = code;                                      // population.rs:511-540
             } else if (code == 1u) {
                 const ps_u4 l2 = ps_philox(site, donor, a.gen, PS_STREAM_CORE_L2, a.k0, a.k1);
-                const ps_cell cell = ps_classify(l2.x, pl);
+                const ps_cell cell = ps_classify_site<WT>(l2.x, pl, a, site);
                 if (cell.mut) val = cell.mut;
             }
         }
@@ -704,7 +721,7 @@ __device__ __forceinline__ uint32_t ps_donor_value(const core_sweep_args &a, con
 // the others (parents far apart: strong selection against a stretch of the population) -- same code, the bytes gathered
 // straight from the old row in global memory; ascending parents keep every load instruction's 64 addresses in one compact
 // range.  A wave whose segment belongs to the other launch leaves at once.
-template <bool DO_MUT, bool DO_HR, bool NT, bool WIDE>
+template <bool DO_MUT, bool DO_HR, bool NT, bool WIDE, bool WT = false>
 __global__ void __launch_bounds__(256, PS_WLB) core_sweep_window_kernel(core_sweep_args a)
 {
     constexpr uint32_t PS_ROWS = PS_BATCH_ROWS;
@@ -853,12 +870,12 @@ __global__ void __launch_bounds__(256, PS_WLB) core_sweep_window_kernel(core_swe
                     const uint32_t k = ps_bit_cell(__builtin_ctz(cmr)), cell = c0 + k;
                     cmr &= cmr - 1u;
                     uint32_t l2y = 0;
-                    const ps_cell cl = ps_cell_events(Ar, Br, site, cell, a.gen, a.k0, a.k1, pl, l2y);
+                    const ps_cell cl = ps_cell_events<WT>(a, Ar, Br, site, cell, a.gen, a.k0, a.k1, pl, l2y);
                     if (DO_MUT && cl.mut) row[i0 + k] = (uint8_t)cl.mut;
                     if (DO_HR && cl.hr) {
                         uint32_t donor = ps_mulhi(l2y, a.N - 1u);
                         donor += (donor >= cell) ? 1u : 0u;                      // population.rs:618
-                        row[i0 + k] = (uint8_t)ps_donor_value(a, pl, old_row, site, donor, DO_MUT);
+                        row[i0 + k] = (uint8_t)ps_donor_value<WT>(a, pl, old_row, site, donor, DO_MUT);
                     }
                 }
             }
@@ -876,7 +893,7 @@ __global__ void __launch_bounds__(256, PS_WLB) core_sweep_window_kernel(core_swe
                 if (lane < nh) {
                     const uint32_t ent = hr_e[lane], donor = hr_d[lane], rr = ent >> 10;
                     const uint32_t rg = (uint32_t)min(max(lr0 + (int)rr, 0), (int)a.rows - 1);
-                    rowbuf[cell_addr(ent)] = (uint8_t)ps_donor_value(a, pl, a.state + (size_t)rg * a.pitch, 4u * sg + rr, donor, DO_MUT);
+                    rowbuf[cell_addr(ent)] = (uint8_t)ps_donor_value<WT>(a, pl, a.state + (size_t)rg * a.pitch, 4u * sg + rr, donor, DO_MUT);
                 }
                 nh = 0;
                 ps_wave_sync();
@@ -890,7 +907,7 @@ __global__ void __launch_bounds__(256, PS_WLB) core_sweep_window_kernel(core_swe
                     const uint32_t rr = ent >> 10;
                     const uint32_t cell = c_first + (ent & 1023u);
                     const ps_u4 l2 = ps_philox(4u * sg + rr, cell, a.gen, PS_STREAM_CORE_L2, a.k0, a.k1);
-                    const ps_cell cl = ps_classify(l2.x, pl);
+                    const ps_cell cl = ps_classify_site<WT>(l2.x, pl, a, 4u * sg + rr);
                     if (DO_MUT && cl.mut) rowbuf[cell_addr(ent)] = (uint8_t)cl.mut;
                     if (DO_HR && cl.hr) {
                         hr = true;
@@ -966,7 +983,7 @@ __device__ __forceinline__ uint32_t ps_valid_cells(uint32_t i0, uint32_t N)
     return ps_valid_word(i0 >= N ? 0u : min(16u, N - i0));
 }
 
-template <uint32_t PS_SB, bool PRE, bool DO_GATHER, bool DO_MUT, bool DO_HR>
+template <uint32_t PS_SB, bool PRE, bool DO_GATHER, bool DO_MUT, bool DO_HR, bool WT = false>
 __global__ void __launch_bounds__(1024) core_sweep_block_kernel(core_sweep_args a, core_block_geom g)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -1177,7 +1194,7 @@ __global__ void __launch_bounds__(1024) core_sweep_block_kernel(core_sweep_args 
                     }
                     const uint32_t cellidx = off - rbase;
                     const ps_u4 l2 = ps_philox(site, cellidx, a.gen, PS_STREAM_CORE_L2, a.k0, a.k1);
-                    const ps_cell cell = ps_classify(l2.x, pl);
+                    const ps_cell cell = ps_classify_site<WT>(l2.x, pl, a, site);
                     if (DO_MUT && cell.mut) rowS[off] = (uint8_t)cell.mut;
                     if (DO_HR && cell.hr) {
                         hr = true;
@@ -1248,7 +1265,7 @@ __global__ void __launch_bounds__(1024) core_sweep_block_kernel(core_sweep_args 
                     const uint32_t i = i0 + k;
                     if (i >= a.N) continue;
                     uint32_t l2y = 0;
-                    const ps_cell cell = ps_cell_events(A, B, site, i, a.gen, a.k0, a.k1, pl, l2y);
+                    const ps_cell cell = ps_cell_events<WT>(a, A, B, site, i, a.gen, a.k0, a.k1, pl, l2y);
                     if (DO_MUT && cell.mut) ps_set_byte(d, k, cell.mut);
                     if (DO_HR && cell.hr) hm |= 1u << k;
                 }

@@ -198,6 +198,11 @@ struct ps_population {
                                      // memory; measured -2 % at cfg2, -9 % at cfg3), 0 for the block sweep (no gain at N = 65536)
     uint32_t pitch = 0, cpr = 0;
     ps_core_plan cplan{};
+    // per-site rates (ps_set_site_rates): the tables replace the per-compartment constants of the plans
+    bool site_weighted = false;
+    uint32_t *d_site_T = nullptr;    // core: 8 u32 per local site row (seven level-2 thresholds + padding)
+    uint8_t *d_gene_tab = nullptr;   // accessory, one allocation: 64 * GW flip thresholds (u32) | per compartment GW non-zero mask
+                                     // words (u64) | per compartment 64 * GW quantised HGT weights (u16)
     bool nibble_safe = true;         // every byte is below 16 (the nibble-packed distance kernels; checked on load)
     bool onehot_safe = true;         // every byte is 1, 2, 4 or 8 (true for simulated states; checked on load)
     uint32_t *d_pack2 = nullptr;     // 2-bit packed copy of the matrix for the sampled-pair distances
@@ -336,6 +341,10 @@ extern "C" void ps_population_destroy(ps_population *p)
                      p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
+    for (int c = 2; c < PS_MAX_COMP; c++)
+        if (p->d_ptab[c]) (void)hipFree(p->d_ptab[c]);
+    if (p->d_site_T) (void)hipFree(p->d_site_T);
+    if (p->d_gene_tab) (void)hipFree(p->d_gene_tab);
     if (p->h_flag) (void)hipHostFree(p->h_flag);
     if (p->h_stamps) {
         if (p->d_stamps) {
@@ -684,11 +693,29 @@ extern "C" int ps_read_matrix(ps_population *p, uint8_t *rows)
 // ---------------------------------------------------------------------------
 // rates
 // ---------------------------------------------------------------------------
+// Poisson threshold tables of the per-donor HGT event counts (population.rs:599)
+static int set_hgt_count_tables(ps_population *p, int n_comp, const double *lam_rec)
+{
+    PSCHK(use_device(p));
+    for (int c = 0; c < PS_MAX_COMP; c++) {
+        if (p->d_ptab[c]) { HIPCHK(hipStreamSynchronize(p->stream)); HIPCHK(hipFree(p->d_ptab[c])); }
+        p->d_ptab[c] = nullptr;
+        p->ptab_len[c] = 0;
+        if (c >= n_comp || !(lam_rec[c] > 0.0)) continue;
+        std::vector<uint32_t> thr;
+        hs_poisson_table(lam_rec[c], &p->ptab_kmin[c], &thr);
+        HIPCHK(hipMalloc(&p->d_ptab[c], thr.size() * sizeof(uint32_t)));
+        HIPCHK(hipMemcpy(p->d_ptab[c], thr.data(), thr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        p->ptab_len[c] = (uint32_t)thr.size();
+    }
+    return PS_OK;
+}
+
 extern "C" int ps_set_rates(ps_population *p, int n_comp, const double *lam_mut, const double *lam_rec,
                             const uint64_t *comp_begin, const uint64_t *comp_end)
 {
     if (!p) return ps_fail(PS_ERR_INVALID, "null handle");
-    if (n_comp < 0 || n_comp > PS_MAX_COMP) return ps_fail(PS_ERR_INVALID, "n_comp must be 0..2");
+    if (n_comp < 0 || n_comp > 2) return ps_fail(PS_ERR_INVALID, "n_comp must be 0..2");
     for (int c = 0; c < n_comp; c++) {
         // statrs Poisson::new(lambda).unwrap() panics on lambda <= 0 or NaN; 0 is skipped
         // before (population.rs:480, :558)
@@ -713,20 +740,243 @@ extern "C" int ps_set_rates(ps_population *p, int n_comp, const double *lam_mut,
             p->aplan.flip_thr[c] = acc_flip_threshold(lam_mut[c], comp_end[c] - comp_begin[c]);
             p->aplan.lam_rec[c] = lam_rec[c];
         }
-        // Poisson threshold tables of the per-donor HGT event counts (population.rs:599)
-        PSCHK(use_device(p));
-        for (int c = 0; c < PS_MAX_COMP; c++) {
-            if (p->d_ptab[c]) { HIPCHK(hipStreamSynchronize(p->stream)); HIPCHK(hipFree(p->d_ptab[c])); }
-            p->d_ptab[c] = nullptr;
-            p->ptab_len[c] = 0;
-            if (c >= n_comp || !(lam_rec[c] > 0.0)) continue;
-            std::vector<uint32_t> thr;
-            hs_poisson_table(lam_rec[c], &p->ptab_kmin[c], &thr);
-            HIPCHK(hipMalloc(&p->d_ptab[c], thr.size() * sizeof(uint32_t)));
-            HIPCHK(hipMemcpy(p->d_ptab[c], thr.data(), thr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            p->ptab_len[c] = (uint32_t)thr.size();
+        PSCHK(set_hgt_count_tables(p, n_comp, lam_rec));
+    }
+    p->site_weighted = false;
+    p->rates_set = true;
+    return PS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// per-site rates: host tables, then ps_set_site_rates
+// ---------------------------------------------------------------------------
+static_assert(PS_MAX_COMP == PS_MAX_SITE_COMP, "the header documents the compartment cap");
+struct site_tables {
+    bool ranges = false;                 // every vector is a 0/1 mask of a contiguous range: the ps_set_rates path
+    uint64_t rb[PS_MAX_COMP] = {}, re[PS_MAX_COMP] = {};
+    ps_core_plan cplan{};                // core: k = 0, R and cshift of the envelope (ranges: the uniform plan)
+    std::vector<uint32_t> T;             // core: 7 thresholds per global site
+    std::vector<uint32_t> flip;          // accessory: one flip threshold per gene
+    std::vector<uint16_t> wq;            // accessory: n_comp x G quantised HGT weights
+};
+
+// 0/1 mask of one non-empty contiguous range?
+static bool mask_range(const float *w, uint64_t n, uint64_t *b, uint64_t *e)
+{
+    uint64_t i = 0;
+    while (i < n && w[i] == 0.0f) i++;
+    if (i == n) return false;
+    *b = i;
+    while (i < n && w[i] == 1.0f) i++;
+    *e = i;
+    while (i < n && w[i] == 0.0f) i++;
+    return i == n;
+}
+
+// the seven thresholds of a cell with mutation probability p, HR probability q, inside R residual symbols (scale = 64 / R);
+// the expressions of make_core_plan with k = 0
+static double site_event_mass(double p, double q)
+{
+    const double a = p * (1.0 - q) / 3.0, b = p * q / 3.0, c = (1.0 - p) * q;
+    return a + a + a + b + b + b + c;
+}
+static void site_thresholds(double p, double q, double scale, uint32_t *T)
+{
+    const double a = p * (1.0 - q) / 3.0, b = p * q / 3.0, c = (1.0 - p) * q;
+    double cum[7];
+    cum[0] = a * scale;
+    cum[1] = (a + a) * scale;
+    cum[2] = (a + a + a) * scale;
+    cum[3] = (a + a + a + b) * scale;
+    cum[4] = (a + a + a + b + b) * scale;
+    cum[5] = (a + a + a + b + b + b) * scale;
+    cum[6] = (a + a + a + b + b + b + c) * scale;
+    uint32_t prev = 0;
+    for (int j = 0; j < 7; j++) {
+        uint32_t t = prob_to_u32(cum[j]);
+        if (t < prev) t = prev;
+        T[j] = prev = t;
+    }
+}
+
+// Validation and every table of ps_set_site_rates; no device is touched (ps_site_tables is this function).
+static int make_site_tables(int core, uint64_t cols, int n_comp, const double *lam_mut, const double *lam_rec, const float *w_mut,
+                            const float *w_rec, site_tables *t)
+{
+    if (n_comp < 1 || n_comp > PS_MAX_COMP) return ps_fail(PS_ERR_INVALID, "n_comp must be 1..%d", PS_MAX_COMP);
+    if (!lam_mut || !lam_rec || !w_mut) return ps_fail(PS_ERR_INVALID, "null rate or weight vector");
+    if (!core && !w_rec) return ps_fail(PS_ERR_INVALID, "an accessory handle needs recombination weights");
+    if (cols == 0) return ps_fail(PS_ERR_INVALID, "no columns to weight");
+    if (!core && cols > 65536) return ps_fail(PS_ERR_INVALID, "weighted HGT serves at most 65536 genes");
+    std::vector<double> Wm(n_comp, 0.0), Wr(n_comp, 0.0);
+    for (int c = 0; c < n_comp; c++) {
+        if (!(lam_mut[c] >= 0.0) || !(lam_rec[c] >= 0.0) || std::isinf(lam_mut[c]) || std::isinf(lam_rec[c]))
+            return ps_fail(PS_ERR_INVALID, "rates must be finite and >= 0");
+        for (int k = 0; k < (core ? 1 : 2); k++) {
+            const float *w = (k ? w_rec : w_mut) + (uint64_t)c * cols;
+            double sum = 0.0;
+            for (uint64_t i = 0; i < cols; i++) {
+                if (!(w[i] >= 0.0f) || std::isinf(w[i]))
+                    return ps_fail(PS_ERR_INVALID, "%s weight %llu of compartment %d is negative or not finite", k ? "recombination" : "mutation",
+                                   (unsigned long long)i, c);
+                sum += (double)w[i];
+            }
+            // (WeightedIndex::new panics on an all-zero vector: main.rs:342-366 builds one per compartment)
+            if (sum == 0.0 && (k ? lam_rec[c] : lam_mut[c]) > 0.0)
+                return ps_fail(PS_ERR_INVALID, "the %s weights of compartment %d are all zero but its rate is not", k ? "recombination" : "mutation", c);
+            (k ? Wr : Wm)[c] = sum;
         }
     }
+    // contiguous 0/1 masks, disjoint: the ps_set_rates path (core: one compartment over every site)
+    t->ranges = core ? n_comp == 1 : n_comp <= 2;
+    for (int c = 0; c < n_comp && t->ranges; c++) {
+        uint64_t b2 = 0, e2 = 0;
+        t->ranges = mask_range(w_mut + (uint64_t)c * cols, cols, &t->rb[c], &t->re[c]);
+        if (t->ranges && core) t->ranges = t->rb[c] == 0 && t->re[c] == cols;
+        if (t->ranges && !core)
+            t->ranges = mask_range(w_rec + (uint64_t)c * cols, cols, &b2, &e2) && b2 == t->rb[c] && e2 == t->re[c];
+        if (t->ranges && c == 1) t->ranges = t->re[0] <= t->rb[1] || t->re[1] <= t->rb[0];
+    }
+    if (core) {
+        t->T.assign(7 * cols, 0u);
+        if (t->ranges) {
+            make_core_plan(lam_mut[0], lam_rec[0], cols, &t->cplan);
+            for (uint64_t s = 0; s < cols; s++) memcpy(&t->T[7 * s], t->cplan.T, 7 * sizeof(uint32_t));
+            return PS_OK;
+        }
+        // HR is uniform over the sites (population.rs:687-689): one q, the compartments' rates add
+        double lam_hr = 0.0;
+        for (int c = 0; c < n_comp; c++) lam_hr += lam_rec[c];
+        const double q = (lam_hr > 0.0) ? -std::expm1(-lam_hr / (double)cols) : 0.0;
+        std::vector<double> ps(cols);
+        double m_max = 0.0;
+        for (uint64_t s = 0; s < cols; s++) {
+            double r = 0.0;
+            for (int c = 0; c < n_comp; c++)
+                if (lam_mut[c] > 0.0) r += lam_mut[c] * (double)w_mut[(uint64_t)c * cols + s] / Wm[c];
+            ps[s] = (r > 0.0) ? -std::expm1(-r) : 0.0;
+            m_max = std::max(m_max, site_event_mass(ps[s], q));
+        }
+        uint32_t R = (uint32_t)std::ceil(m_max * 64.0);
+        if (R > 64u) R = 64u;
+        const double scale = R ? 64.0 / (double)R : 0.0;
+        uint32_t t6 = 0;
+        for (uint64_t s = 0; s < cols; s++) {
+            site_thresholds(ps[s], q, scale, &t->T[7 * s]);
+            t6 = std::max(t6, t->T[7 * s + 6]);
+        }
+        if (t6 == 0u) R = 0u;
+        ps_core_plan &pl = t->cplan;
+        pl = ps_core_plan{};
+        pl.T[6] = t6;                  // (the host sizes the block sweep's HR lists from T[6] - T[2]: the envelope)
+        pl.k = 0u;
+        pl.R = R;
+        pl.has_events = R > 0u ? 1u : 0u;
+        uint32_t cs = 0;
+        while (cs < 4u && R > (4u << cs)) cs++;
+        pl.cshift = cs;
+        return PS_OK;
+    }
+    t->flip.assign(cols, 0u);
+    t->wq.assign((uint64_t)n_comp * cols, 0);
+    if (t->ranges) {
+        for (int c = 0; c < n_comp; c++)
+            for (uint64_t g = t->rb[c]; g < t->re[c]; g++) {
+                t->flip[g] = acc_flip_threshold(lam_mut[c], t->re[c] - t->rb[c]);
+                t->wq[(uint64_t)c * cols + g] = 1;
+            }
+        return PS_OK;
+    }
+    for (uint64_t g = 0; g < cols; g++) {
+        double r = 0.0;                // overlapping compartments add their rates
+        for (int c = 0; c < n_comp; c++)
+            if (lam_mut[c] > 0.0) r += lam_mut[c] * (double)w_mut[(uint64_t)c * cols + g] / Wm[c];
+        t->flip[g] = (r > 0.0) ? prob_to_u32(-std::expm1(-2.0 * r) / 2.0) : 0u;
+    }
+    for (int c = 0; c < n_comp; c++) {
+        const float *w = w_rec + (uint64_t)c * cols;
+        double wmax = 0.0;
+        for (uint64_t g = 0; g < cols; g++) wmax = std::max(wmax, (double)w[g]);
+        if (!(wmax > 0.0)) continue;
+        for (uint64_t g = 0; g < cols; g++) {
+            if (!(w[g] > 0.0f)) continue;
+            const double x = std::floor((double)w[g] / wmax * 65535.0 + 0.5);
+            t->wq[(uint64_t)c * cols + g] = (uint16_t)(x < 1.0 ? 1.0 : x);     // a positive weight stays drawable
+        }
+    }
+    return PS_OK;
+}
+
+extern "C" int ps_site_tables(int core, uint64_t global_cols, int n_comp, const double *lam_mut, const double *lam_rec, const float *w_mut,
+                              const float *w_rec, uint32_t *plan_out, uint32_t *thr_out, uint16_t *wq_out)
+{
+    site_tables t;
+    PSCHK(make_site_tables(core, global_cols, n_comp, lam_mut, lam_rec, w_mut, w_rec, &t));
+    if (plan_out) {
+        plan_out[0] = core ? t.cplan.k : 0u;
+        plan_out[1] = core ? t.cplan.R : 0u;
+        plan_out[2] = core ? t.cplan.cshift : 0u;
+        plan_out[3] = core ? t.cplan.has_events : 0u;
+        plan_out[4] = t.ranges ? 1u : 0u;
+    }
+    if (thr_out) {
+        const std::vector<uint32_t> &v = core ? t.T : t.flip;
+        memcpy(thr_out, v.data(), v.size() * sizeof(uint32_t));
+    }
+    if (wq_out && !core) memcpy(wq_out, t.wq.data(), t.wq.size() * sizeof(uint16_t));
+    return PS_OK;
+}
+
+extern "C" int ps_set_site_rates(ps_population *p, int n_comp, const double *lam_mut, const double *lam_rec, const float *w_mut,
+                                 const float *w_rec)
+{
+    if (!p) return ps_fail(PS_ERR_INVALID, "null handle");
+    const int core = p->cfg.core ? 1 : 0;
+    const uint64_t cols = p->cfg.global_cols;
+    site_tables t;
+    PSCHK(make_site_tables(core, cols, n_comp, lam_mut, lam_rec, w_mut, w_rec, &t));
+    if (t.ranges) return ps_set_rates(p, n_comp, lam_mut, lam_rec, t.rb, t.re);      // (clears site_weighted)
+    for (int c = 0; c < n_comp; c++)
+        if (p->cfg.pop_size < 2 && lam_rec[c] > 0.0)
+            return ps_fail(PS_ERR_INVALID, "recombination needs pop_size >= 2 (population.rs:584 panics)");
+    PSCHK(use_device(p));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (core) {
+        // the shard's rows of the table, one 32-byte record per row (normalisation and envelope are global: a site shard
+        // equals its columns of the whole run)
+        const uint64_t rows = p->cfg.ncols, off = p->cfg.col_offset;
+        std::vector<uint32_t> rec(8 * std::max<uint64_t>(rows, 1), 0u);
+        for (uint64_t r = 0; r < rows; r++) memcpy(&rec[8 * r], &t.T[7 * (off + r)], 7 * sizeof(uint32_t));
+        if (!p->d_site_T) HIPCHK(hipMalloc(&p->d_site_T, rec.size() * sizeof(uint32_t)));
+        HIPCHK(hipMemcpy(p->d_site_T, rec.data(), rec.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        p->cplan = t.cplan;
+    } else {
+        const uint64_t GW = p->d.GW, G64 = GW * 64;
+        const uint64_t thr_bytes = G64 * 4, nz_bytes = (uint64_t)PS_MAX_COMP * GW * 8, wq_bytes = (uint64_t)PS_MAX_COMP * G64 * 2;
+        std::vector<uint8_t> tab(thr_bytes + nz_bytes + wq_bytes, 0);
+        uint32_t *thr = (uint32_t *)tab.data();
+        uint64_t *nz = (uint64_t *)(tab.data() + thr_bytes);
+        uint16_t *wq = (uint16_t *)(tab.data() + thr_bytes + nz_bytes);
+        memcpy(thr, t.flip.data(), cols * 4);
+        for (int c = 0; c < n_comp; c++)
+            for (uint64_t g = 0; g < cols; g++) {
+                const uint16_t v = t.wq[(uint64_t)c * cols + g];
+                wq[(uint64_t)c * G64 + g] = v;
+                if (v) nz[(uint64_t)c * GW + (g >> 6)] |= 1ull << (g & 63u);
+            }
+        if (!p->d_gene_tab) HIPCHK(hipMalloc(&p->d_gene_tab, tab.size()));
+        HIPCHK(hipMemcpy(p->d_gene_tab, tab.data(), tab.size(), hipMemcpyHostToDevice));
+        // every compartment spans all genes; what a compartment can draw is its non-zero mask
+        p->aplan = ps_acc_plan{};
+        p->aplan.n_comp = n_comp;
+        for (int c = 0; c < n_comp; c++) {
+            p->aplan.comp_begin[c] = 0;
+            p->aplan.comp_end[c] = (uint32_t)cols;
+            p->aplan.lam_rec[c] = lam_rec[c];
+        }
+        PSCHK(set_hgt_count_tables(p, n_comp, lam_rec));
+    }
+    p->site_weighted = true;
     p->rates_set = true;
     return PS_OK;
 }
@@ -761,7 +1011,12 @@ static int launch_core_sweep_wave(ps_population *p, core_sweep_args a, hipStream
     const uint32_t fit = std::max(1u, std::min(8u, p->lds_limit / lds));
     const uint32_t bpc = std::min(p->sweep_blocks_per_cu, fit);
     const uint32_t grid = std::max(8u, std::min((want + 7u) & ~7u, 256u * bpc));   // a multiple of the 8 groups
-    if (a.nt) hipLaunchKernelGGL((core_sweep_wave_kernel<GA, MU, HR, true>), dim3(grid), dim3(block), lds, st, a);
+    // (per-site rates, DESIGN.md 3.6: the variants whose exact pass reads the site's own threshold record)
+    constexpr bool EV = MU || HR;
+    if (EV && a.site_T) {
+        if (a.nt) hipLaunchKernelGGL((core_sweep_wave_kernel<GA, MU, HR, true, EV>), dim3(grid), dim3(block), lds, st, a);
+        else hipLaunchKernelGGL((core_sweep_wave_kernel<GA, MU, HR, false, EV>), dim3(grid), dim3(block), lds, st, a);
+    } else if (a.nt) hipLaunchKernelGGL((core_sweep_wave_kernel<GA, MU, HR, true>), dim3(grid), dim3(block), lds, st, a);
     else hipLaunchKernelGGL((core_sweep_wave_kernel<GA, MU, HR, false>), dim3(grid), dim3(block), lds, st, a);
     HIPCHK(hipGetLastError());
     return PS_OK;
@@ -827,10 +1082,11 @@ static bool block_sweep_preload(const ps_population *p, const core_block_geom &g
     return p->pitch <= 65536u && g.R * g.segs <= nw * g.SB && !p->no_block_preload;
 }
 
-template <uint32_t SB, bool PRE, bool GA, bool MU, bool HR>
+template <uint32_t SB, bool PRE, bool GA, bool MU, bool HR, bool WT = false>
 static int launch_block_kernel(const core_sweep_args &a, const core_block_geom &g, uint32_t lds, uint32_t nw, hipStream_t st)
 {
-    auto kern = core_sweep_block_kernel<SB, PRE, GA, MU, HR>;
+    if ((MU || HR) && !WT && a.site_T) return launch_block_kernel<SB, PRE, GA, MU, HR, MU || HR>(a, g, lds, nw, st);   // per-site rates
+    auto kern = core_sweep_block_kernel<SB, PRE, GA, MU, HR, WT>;
     if (lds > 64 * 1024)
         HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const uint32_t groups = (a.rows + g.R - 1) / g.R;
@@ -868,7 +1124,8 @@ static int launch_core_sweep_block(ps_population *p, const core_sweep_args &a, c
     if (lds > p->lds_limit)
         return ps_fail(PS_ERR_INVALID, "pop_size %u needs %u bytes of LDS per row (limit %u)", a.N, lds,
                        p->lds_limit);
-    auto kern = core_sweep_inline_kernel<GA, MU, HR>;
+    constexpr bool EV = MU || HR;
+    auto kern = (EV && a.site_T) ? core_sweep_inline_kernel<GA, MU, HR, EV> : core_sweep_inline_kernel<GA, MU, HR>;
     if (lds > 64 * 1024)
         HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const uint32_t cap = 256u * (lds > 80 * 1024 ? 1u : 2u);
@@ -907,7 +1164,14 @@ static int launch_core_sweep_window(ps_population *p, const core_sweep_args &a, 
         hipLaunchKernelGGL((core_sweep_window_kernel<true, HR, NT_, false>), dim3(grid), dim3(256), lds, st, a0);          \
         hipLaunchKernelGGL((core_sweep_window_kernel<true, HR, NT_, true>), dim3(grid), dim3(256), lds, st, b);            \
     }
-    if (a.nt) PS_WLAUNCH(true) else PS_WLAUNCH(false)
+#define PS_WLAUNCH_W(NT_)                                                                                                  \
+    {                                                                                                                     \
+        hipLaunchKernelGGL((core_sweep_window_kernel<true, HR, NT_, false, true>), dim3(grid), dim3(256), lds, st, a0);    \
+        hipLaunchKernelGGL((core_sweep_window_kernel<true, HR, NT_, true, true>), dim3(grid), dim3(256), lds, st, b);      \
+    }
+    if (a.site_T) { if (a.nt) PS_WLAUNCH_W(true) else PS_WLAUNCH_W(false) }
+    else if (a.nt) PS_WLAUNCH(true) else PS_WLAUNCH(false)
+#undef PS_WLAUNCH_W
 #undef PS_WLAUNCH
     HIPCHK(hipGetLastError());
     return PS_OK;
@@ -929,6 +1193,7 @@ static int launch_core_sweep(ps_population *p, const uint32_t *d_idx, uint32_t g
     a.k0 = (uint32_t)p->cfg.seed;
     a.k1 = (uint32_t)(p->cfg.seed >> 32);
     a.plan = p->cplan;
+    a.site_T = p->site_weighted ? p->d_site_T : nullptr;
     // the kernels' mutate / HR variants assume a plan with events (straight-line per-row code)
     if (!a.plan.has_events) mu = hr = false;
     if (!mu && !hr) a.plan.has_events = 0;
@@ -1026,8 +1291,13 @@ static int launch_acc_step(ps_population *p, const uint32_t *d_idx, uint32_t gen
     a.k0 = (uint32_t)p->cfg.seed;
     a.k1 = (uint32_t)(p->cfg.seed >> 32);
     a.plan = p->aplan;
+    a.gene_thr = p->site_weighted ? (const uint32_t *)p->d_gene_tab : nullptr;
     const uint64_t threads = (uint64_t)p->d.N * p->d.GW;
     const uint32_t grid = (uint32_t)((threads + 255) / 256);
+    if (mu && a.gene_thr) {            // per-gene rates
+        if (ga) acc_step_rows_kernel<true, true, true><<<grid, 256, 0, st>>>(a);
+        else acc_step_rows_kernel<false, true, true><<<grid, 256, 0, st>>>(a);
+    } else
     if (ga && mu) acc_step_rows_kernel<true, true><<<grid, 256, 0, st>>>(a);
     else if (ga) acc_step_rows_kernel<true, false><<<grid, 256, 0, st>>>(a);
     else acc_step_rows_kernel<false, true><<<grid, 256, 0, st>>>(a);
@@ -1059,6 +1329,14 @@ static uint32_t hgt_partitions(const ps_population *p)
     return (uint32_t)((p->d.N + part_cap - 1) / part_cap);
 }
 
+// a donor's gene list: u16 entries; under per-gene weights the u32 prefix sums of the quantised weights sit
+// behind it, 16-byte aligned.  Sizes in u16 units.
+static uint32_t hgt_pref_off(uint32_t max_comp) { return (max_comp + 7u) & ~7u; }
+static uint32_t hgt_list_u16(const ps_population *p, uint32_t max_comp)
+{
+    return p->site_weighted ? hgt_pref_off(max_comp) + 2u * max_comp : max_comp;
+}
+
 // which form launch_acc_hgt will take for this handle's rates (its callers decide from it whether the step before the HGT
 // should leave the light form's snapshot: the binned form never reads one)
 static bool hgt_takes_binned_form(const ps_population *p)
@@ -1070,7 +1348,7 @@ static bool hgt_takes_binned_form(const ps_population *p)
         expected += (double)p->d.N * p->aplan.lam_rec[c];
         max_comp = std::max(max_comp, p->aplan.comp_end[c] - p->aplan.comp_begin[c]);
     }
-    const uint32_t list_lds = ((max_comp * 2u + 15u) & ~15u);
+    const uint32_t list_lds = ((hgt_list_u16(p, max_comp) * 2u + 15u) & ~15u);
     const uint32_t parts = hgt_partitions(p);
     const uint32_t rpp = parts ? (p->d.N + parts - 1) / parts : 0;
     return parts >= 1 && parts <= 1024 && rpp >= 2 && p->d.G <= 65536u && (uint64_t)p->d.N * rpp < (1ull << 32)
@@ -1125,7 +1403,18 @@ static int launch_acc_hgt(ps_population *p, uint32_t gen, hipStream_t st, hipEve
         HIPCHK(hipMalloc(&p->d_delta, p->delta_words * 8));
         HIPCHK(hipMemsetAsync(p->d_delta, 0, p->delta_words * 8, st));
     }
-    const uint32_t list_lds = ((max_comp * 2u + 15u) & ~15u);
+    const bool wt = p->site_weighted;
+    if (wt) {
+        const uint64_t GW = p->d.GW, G64 = GW * 64;
+        const uint8_t *nz = p->d_gene_tab + G64 * 4, *wq = nz + (uint64_t)PS_MAX_COMP * GW * 8;
+        for (int c = 0; c < p->aplan.n_comp; c++) {
+            a.wnz[c] = (const uint64_t *)nz + (uint64_t)c * GW;
+            a.wq[c] = (const uint16_t *)wq + (uint64_t)c * G64;
+        }
+        a.pref_off = hgt_pref_off(max_comp);
+    }
+    const uint32_t list_u16 = hgt_list_u16(p, max_comp);
+    const uint32_t list_lds = ((list_u16 * 2u + 15u) & ~15u);
     if (list_lds > p->lds_limit)
         return ps_fail(PS_ERR_INVALID, "a compartment of %u genes needs %u bytes of LDS (limit %u)", max_comp, list_lds, p->lds_limit);
 
@@ -1174,7 +1463,7 @@ static int launch_acc_hgt(ps_population *p, uint32_t gen, hipStream_t st, hipEve
         const uint64_t cnt_bytes = ((uint64_t)donor_blocks * parts * 4 + 255) & ~255ull;
         // (measured at the cfg4 population: the bin pass running beside the block sweep this way makes the generation
         // LONGER -- 8.3 -> 9.4 ms per generation at 1/8 of the sites -- so ps_sim leaves it off: test hook only)
-        const uint64_t list_bytes = p->hgt_bin_list_in_global ? (((uint64_t)donor_blocks * max_comp * sizeof(uint16_t) + 255) & ~255ull) : 0;
+        const uint64_t list_bytes = p->hgt_bin_list_in_global ? (((uint64_t)donor_blocks * list_u16 * sizeof(uint16_t) + 255) & ~255ull) : 0;
         const uint64_t need = img_bytes + bin_words * 4 + cnt_bytes + list_bytes;
         if (p->hgt_scratch_cap < need) {
             if (p->hgt_scratch) HIPCHK(hipFree(p->hgt_scratch));
@@ -1203,12 +1492,13 @@ static int launch_acc_hgt(ps_population *p, uint32_t gen, hipStream_t st, hipEve
             // the co-running block sweep owns the CU's LDS: donor lists in global scratch, the bin pass then fits
             // beside it with its fill counters only
             a.list_scratch = (uint16_t *)((uint8_t *)p->hgt_scratch + img_bytes + bin_words * 4 + cnt_bytes);
-            a.list_stride = max_comp;
+            a.list_stride = list_u16;
         }
         const uint32_t dlds = ((parts + 3u) & ~3u) * 4u + (list_bytes ? 0u : list_lds);
+        auto bin_kern = wt ? acc_hgt_donor_bin_kernel<true> : acc_hgt_donor_bin_kernel<false>;
         if (dlds > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)acc_hgt_donor_bin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));
-        hipLaunchKernelGGL(acc_hgt_donor_bin_kernel, dim3(donor_blocks), dim3(256), dlds, st, a);
+            HIPCHK(hipFuncSetAttribute((const void *)bin_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));
+        hipLaunchKernelGGL(bin_kern, dim3(donor_blocks), dim3(256), dlds, st, a);
         const bool in_gap = st_gap && ev_bin && record_after_apply && !p->exchange_beside_sweep;
         hipStream_t run = st;            // where the passes between two sweeps go
         if (in_gap) {
@@ -1257,7 +1547,7 @@ static int launch_acc_hgt(ps_population *p, uint32_t gen, hipStream_t st, hipEve
         if (p->hgt_list_in_global) {
             // the co-running block sweep owns the CU's LDS: keep the donor lists in a per-workgroup
             // global scratch instead (hot in L2; reads of a list come from the workgroup that wrote it)
-            const uint64_t need = (uint64_t)grid * max_comp * sizeof(uint16_t);
+            const uint64_t need = (uint64_t)grid * list_u16 * sizeof(uint16_t);
             if (p->hgt_scratch_cap < need) {
                 if (p->hgt_scratch) HIPCHK(hipFree(p->hgt_scratch));
                 p->hgt_scratch = nullptr;
@@ -1266,12 +1556,13 @@ static int launch_acc_hgt(ps_population *p, uint32_t gen, hipStream_t st, hipEve
                 p->hgt_scratch_cap = need;
             }
             a.list_scratch = (uint16_t *)p->hgt_scratch;
-            a.list_stride = max_comp;
+            a.list_stride = list_u16;
             dyn_lds = 0;
         }
+        auto wave_kern = wt ? acc_hgt_donor_wave_kernel<true> : acc_hgt_donor_wave_kernel<false>;
         if (dyn_lds > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)acc_hgt_donor_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
-        hipLaunchKernelGGL(acc_hgt_donor_wave_kernel, dim3(grid), dim3(64), dyn_lds, st, a);
+            HIPCHK(hipFuncSetAttribute((const void *)wave_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
+        hipLaunchKernelGGL(wave_kern, dim3(grid), dim3(64), dyn_lds, st, a);
     }
     HIPCHK(hipGetLastError());
     if (sharded) {
@@ -3576,6 +3867,38 @@ extern "C" int ps_sim_set_exchange(ps_sim *s, ps_exchange_fn fn, void *ctx)
     PSCHK(ps_set_donor_shard(s->acc, (uint32_t)s->prm.shard_rank, (uint32_t)s->prm.shard_count, fn, ctx));
     sim_exchange_schedule(s);
     return PS_OK;
+}
+
+// Per-site weights for the whole loop: the rates stay those of the parameters (what ps_sim_create passed to
+// ps_set_rates), the weights replace the compartments' 0/1 masks.
+extern "C" int ps_sim_set_site_weights(ps_sim *s, const float *w_core, const float *w_acc_mut, const float *w_acc_rec)
+{
+    if (!s) return ps_fail(PS_ERR_INVALID, "null handle");
+    if ((w_acc_mut == nullptr) != (w_acc_rec == nullptr))
+        return ps_fail(PS_ERR_INVALID, "the accessory weights come as a pair (mutation and recombination)");
+    PSCHK(ps_sim_sync(s));
+    const ps_sim_params &p = s->prm;
+    const ps_derived &d = s->der;
+    if (w_core) {
+        const double lm = d.n_core_mutations;
+        const double lr = (p.HR_rate > 0.0) ? d.n_recombinations_core : 0.0;   // main.rs:459
+        PSCHK(ps_set_site_rates(s->core, 1, &lm, &lr, w_core, nullptr));
+    }
+    if (w_acc_mut) {
+        double lrec[2] = { 0, 0 };
+        for (int c = 0; c < d.n_comp; c++) lrec[c] = (p.HGT_rate > 0.0) ? d.n_recombinations_pan[c] : 0.0; // :462
+        PSCHK(ps_set_site_rates(s->acc, d.n_comp, d.n_pan_mutations, lrec, w_acc_mut, w_acc_rec));
+        // (a weighted donor list takes 6 bytes per gene instead of 2: beside the sweep it goes to global scratch earlier)
+        if (s->acc->site_weighted && (uint64_t)hgt_list_u16(s->acc, (uint32_t)s->acc->d.G) * 2u > 36u * 1024u) s->acc->hgt_list_in_global = true;
+    }
+    return PS_OK;
+}
+
+// (several site shards in one process: not plumbed yet)
+extern "C" int ps_multi_set_site_weights(ps_multi *m, const float *w_core, const float *w_acc_mut, const float *w_acc_rec)
+{
+    (void)m; (void)w_core; (void)w_acc_mut; (void)w_acc_rec;
+    return ps_fail(PS_ERR_INVALID, "ps_multi runs have no per-site weights yet: drive one ps_sim per shard and call ps_sim_set_site_weights");
 }
 
 // bench.py --emulate-shard K: this process plays shard 0 of K.  Its HGT serves donors [0, N / K) and the exchange is

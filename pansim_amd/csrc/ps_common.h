@@ -146,7 +146,7 @@ PS_HD ps_cell ps_classify(uint32_t u, const ps_core_plan &pl)
     return o;
 }
 
-#define PS_MAX_COMP 2
+#define PS_MAX_COMP 8      // compartments of ps_set_site_rates (ps_set_rates: two ranges)
 struct ps_acc_plan {
     int32_t n_comp;
     uint32_t comp_begin[PS_MAX_COMP], comp_end[PS_MAX_COMP];

@@ -82,6 +82,42 @@ def sample_weights(num_genes, logw, n_genes, avg_gene_num, avg_pairwise_dists,
     return w
 
 
+def _weights(w, n_comp, cols, what):
+    """n_comp x cols f32, row-major (one vector is taken as one compartment); None stays None"""
+    if w is None:
+        return None
+    w = np.ascontiguousarray(w, np.float32)
+    if w.ndim == 1:
+        w = w.reshape(1, -1)
+    if w.shape != (n_comp, cols):
+        raise ValueError("%s weights must be (%d compartments, %d global columns)" % (what, n_comp, cols))
+    return w
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def site_tables(core, global_cols, mutations_vec, recombinations_vec, mutation_weights, recombination_weights=None):
+    """The host tables of `Population.set_site_rates` (ps_site_tables; no device): a dict with the core plan fields
+    `k`, `R`, `cshift`, `has_events`, `ranges` (True: the vectors are contiguous 0/1 masks, the set_rates path), `thresholds`
+    (core: (global_cols, 7) level-2 thresholds; accessory: global_cols flip thresholds) and, accessory only, `hgt_weights`
+    ((n_comp, global_cols) u16)."""
+    lib = _lib.load()
+    lm, lr = _f64(mutations_vec), _f64(recombinations_vec)
+    cols = int(global_cols)
+    wm = _weights(mutation_weights, lm.size, cols, "mutation")
+    wr = _weights(recombination_weights, lm.size, cols, "recombination")
+    plan = np.zeros(5, np.uint32)
+    thr = np.zeros((cols, 7) if core else cols, np.uint32)
+    wq = np.zeros((lm.size, cols), np.uint16)
+    check(lib.ps_site_tables(int(bool(core)), cols, lm.size, lm, lr, _ptr(wm), _ptr(wr), _ptr(plan), _ptr(thr), _ptr(wq)))
+    out = dict(k=int(plan[0]), R=int(plan[1]), cshift=int(plan[2]), has_events=int(plan[3]), ranges=bool(plan[4]), thresholds=thr)
+    if not core:
+        out["hgt_weights"] = wq
+    return out
+
+
 def draw_parents(weights, seed, generation):
     """population.rs:440-443"""
     w = _f64(weights)
@@ -159,6 +195,19 @@ class Population:
         b = np.ascontiguousarray(comp_begin, np.uint64)
         e = np.ascontiguousarray(comp_end, np.uint64)
         check(self._lib.ps_set_rates(self._h, lm.size, lm, lr, b, e))
+
+    def set_site_rates(self, mutations_vec, recombinations_vec, mutation_weights, recombination_weights=None):
+        """The rates with the reference's weight vectors (`weighted_dist` of mutate_alleles, population.rs:467-471;
+        `locus_weights` of recombine, :544-549): (n_comp, global_cols) f32 each, over the GLOBAL columns even on a site
+        shard.  Core populations pass no recombination weights (:687-689 draws the site uniformly)."""
+        lm, lr = _f64(mutations_vec), _f64(recombinations_vec)
+        if lr.size != lm.size:
+            raise ValueError("one recombination rate per mutation rate")
+        wm = _weights(mutation_weights, lm.size, self.global_cols, "mutation")
+        wr = _weights(recombination_weights, lm.size, self.global_cols, "recombination")
+        if wm is None:
+            raise ValueError("mutation weights are required")
+        check(self._lib.ps_set_site_rates(self._h, lm.size, lm, lr, _ptr(wm), _ptr(wr)))
 
     # -- per-generation operators ---------------------------------------------------
     def next_generation(self, sample):

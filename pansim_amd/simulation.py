@@ -121,6 +121,16 @@ class Simulation:
         self._exchange_fn = fn          # keep the ctypes thunk alive
         check(self._lib.ps_sim_set_exchange(self._h, C.cast(fn, C.c_void_p), ctx))
 
+    def set_site_weights(self, core_weights=None, pan_mutation_weights=None, pan_recombination_weights=None):
+        """run the loop with per-site weights (ps_sim_set_site_weights): `core_weights` core_size values;
+        the accessory pair (n_comp, pan_size) each, n_comp = derived.n_comp; the rates stay those of the parameters"""
+        from .population import _ptr, _weights
+        p, d = self.params, self.derived
+        wc = _weights(core_weights, 1, p.core_size, "core")
+        wm = _weights(pan_mutation_weights, d.n_comp, d.pan_size, "accessory mutation")
+        wr = _weights(pan_recombination_weights, d.n_comp, d.pan_size, "accessory recombination")
+        check(self._lib.ps_sim_set_site_weights(self._h, _ptr(wc), _ptr(wm), _ptr(wr)))
+
     def emulate_exchange(self, n_shards):
         """bench.py --emulate-shard: shard 0 of n_shards, exchange stood in for by device-local copies (timing only)"""
         check(self._lib.ps_sim_emulate_exchange(self._h, int(n_shards)))
