@@ -242,7 +242,11 @@ int ps_sync(ps_population *p);
  * buffer that then swaps roles with the first, 2 = the same with nontemporal row loads and stores; results are identical),
  * "lds_limit" (bytes of LDS a workgroup may use), "block_waves" (block sweep: waves per
  * workgroup, 0 = choose), "block_batch" (block sweep: segments per wave batch, 0 = choose, 2 or 4),
- * "no_block_preload" (block sweep: parent indices re-read per batch). */
+ * "no_block_preload" (block sweep: parent indices re-read per batch),
+ * "sweep_generations" (core handle of a ps_sim: generations one launch of the wave sweep applies in ps_sim_run, 0 = choose,
+ * 1 or 2; only where the wave sweep takes the loop's step -- pop_size <= 1024 -- and only for runs of at least that many
+ * generations, everything else keeps one generation per launch; results are identical; the environment variable
+ * PANSIM_SWEEP_GENERATIONS sets the same at creation). */
 int ps_set_tuning(ps_population *p, const char *key, int64_t value);
 
 /* ------------------------------------------------------------------------ */
@@ -377,7 +381,10 @@ const uint32_t *ps_sim_range2(ps_sim *s);
 int ps_sim_last_parents(ps_sim *s, uint32_t *out_idx);
 /* Device timing of the core sweep kernel, measured with HIP events on the
  * stream it is launched on, accumulated since the last reset: launches, total
- * milliseconds, and algorithmic bytes per launch (2*N*L_local). */
+ * milliseconds, and algorithmic bytes per launch (2*N*L_local).  A launch of the
+ * wave sweep may carry several generations ("sweep_generations"): it still reads
+ * and writes the matrix once, so bytes per launch stay 2*N*L_local and `launches`
+ * is smaller than the number of generations (ps_sim_host_timing counts those). */
 int ps_sim_sweep_timing(ps_sim *s, int reset, uint64_t *launches, double *total_ms,
                         double *bytes_per_launch);
 int ps_sim_enable_timing(ps_sim *s, int on);

@@ -15,14 +15,16 @@
 
 #include <type_traits>
 
+#define PS_SWEEP_MAX_GENS 2      // generations one launch of the wave sweep can apply (template parameter T below)
 struct core_sweep_args {
     uint8_t *state;        // the generation that is read
     uint8_t *out;          // where the new generation is written: == state (in place) or the second buffer (out of place)
     const uint32_t *idx;   // parents (device), DO_GATHER only
+    const uint32_t *idx_next[PS_SWEEP_MAX_GENS - 1];   // wave sweep, several generations per pass: parents of generation gen + 1 + k
     const uint32_t *idxT;  // idxT[k * cpr + chunk] = idx[16 * chunk + k] (block sweep)
     uint32_t N, pitch, cpr, rows;
     uint32_t site_offset;  // global site index of local row 0 (Philox counter)
-    uint32_t gen, k0, k1;
+    uint32_t gen, k0, k1;  // gen: the (first) generation of the launch
     ps_core_plan plan;
     uint32_t *overflow_flag;   // host-mapped sticky error word
     unsigned long long *stamps; // diagnostic builds (PS_STAMP) only
@@ -391,9 +393,20 @@ __device__ __forceinline__ uint32_t ps_pack4(uint32_t b0, uint32_t b1, uint32_t 
 __host__ __device__ constexpr uint32_t ps_queue_bytes(uint32_t qcap) { return (qcap * 2u + 15u) & ~15u; }
 __host__ __device__ constexpr uint32_t ps_wave_lds(uint32_t qcap) { return PS_BATCH_ROWS * 1024u + ps_queue_bytes(qcap); }
 
-template <bool DO_GATHER, bool DO_MUT, bool DO_HR, bool NT = false, bool WT = false>
-__global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_sweep_args a)
+// T generations per pass (T > 1: the fused gather + events step of the generation loop only).  Every operator is local to a
+// site row and a wave owns its 4 rows for the whole batch, so after the exact pass of generation g the LDS rows ARE
+// generation g, complete -- the parent rows of generation g + 1.  The wave applies generations gen .. gen + T - 1 (Philox
+// keyed on gen + t, parents idx / idx_next[t - 1]) between ONE load and ONE store of the rows: the HBM traffic per
+// generation is 2 N L / T and the results are those of T launches, bit for bit.  T = 1 is the single-generation kernel
+// unchanged (70 VGPRs, built for PS_WAVE_LB = 6 waves per SIMD); T = 2 keeps both generations' 16 parent indices in
+// registers -- unpacked: two 10-bit indices per register would save 16 VGPRs the build does not need (it takes 95 of the
+// 128 that 4 waves per SIMD allow, the residency the generation loop launches it at; no scratch) and cost a v_bfe per
+// gathered byte on the vector ALUs, which bound a two-generation launch (profiles/sweep_two_generations.md).
+template <bool DO_GATHER, bool DO_MUT, bool DO_HR, bool NT = false, bool WT = false, uint32_t T = 1>
+__global__ void __launch_bounds__(256, T > 1 ? 4 : PS_WAVE_LB) core_sweep_wave_kernel(core_sweep_args a)
 {
+    static_assert(T >= 1 && T <= PS_SWEEP_MAX_GENS, "generations per pass");
+    static_assert(T == 1 || (DO_GATHER && (DO_MUT || DO_HR)), "several generations per pass: the gather + events form only");
 #ifdef PS_STAMP
     unsigned long long st_acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     unsigned long long st_last;
@@ -420,11 +433,16 @@ __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_s
     const uint32_t nvalid = (i0 >= a.N) ? 0u : min(16u, a.N - i0);
     const uint32_t vm = ps_valid_word(nvalid);        // the lane's cells that exist, at both sites of a plane word
 
-    uint32_t pidx[16];
+    uint32_t pidx[T][16];
     if (DO_GATHER) {
-        // cells beyond N gather the first padding byte of the row, which is always 0
+        // cells beyond N gather the first padding byte of the row, which is always 0 (in every generation of the pass:
+        // that byte gathers itself)
 #pragma unroll
-        for (uint32_t k = 0; k < 16; k++) pidx[k] = (k < nvalid) ? a.idx[i0 + k] : min(a.N, a.pitch - 1u);
+        for (uint32_t t = 0; t < T; t++) {
+            const uint32_t *ix = t ? a.idx_next[t ? t - 1u : 0u] : a.idx;
+#pragma unroll
+            for (uint32_t k = 0; k < 16; k++) pidx[t][k] = (k < nvalid) ? ix[i0 + k] : min(a.N, a.pitch - 1u);
+        }
     }
 
     // Dynamic row assignment.  The batches (global site groups: batch b = sites 4 * (site_offset / 4 + b) .. + 3, of which
@@ -481,14 +499,19 @@ __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_s
         }
         PS_T(0);   // global load + LDS stage
 
+        // the generations of the pass, one after the other on the LDS rows (the wave sync that ends a generation's exact pass
+        // -- all donor reads done, all copies applied -- is the fence the next generation's gather needs)
+#pragma unroll
+        for (uint32_t t = 0; t < T; t++) {
+        const uint32_t gen = a.gen + t;
         // Phase 1: the symbol planes of the batch (three Philox calls per lane for 4 x 16 cells), then, row by row, the child
         // bytes.  (Interleaving the rows' gathers needs more registers than 8 waves per SIMD leave.)
         uint32_t wl[2] = { 0u, 0u };      // the residual words of ps_push_scan, one per row pair
         ps_apply_words y[2] = {};
         if (events) {
-            const ps_u4 A0 = ps_philox_l1a(2u * sg, lane, a.gen, a.k0, a.k1);
-            const ps_u4 A1 = ps_philox_l1a(2u * sg + 1u, lane, a.gen, a.k0, a.k1);
-            const ps_u4 B = ps_philox_l1b(sg, lane, a.gen, a.k0, a.k1);
+            const ps_u4 A0 = ps_philox_l1a(2u * sg, lane, gen, a.k0, a.k1);
+            const ps_u4 A1 = ps_philox_l1a(2u * sg + 1u, lane, gen, a.k0, a.k1);
+            const ps_u4 B = ps_philox_l1b(sg, lane, gen, a.k0, a.k1);
             const ps_class_words c0 = ps_classes(A0.x, A0.y, A0.z, A0.w, B.x, B.z, pl.k, nE, vm);
             const ps_class_words c1 = ps_classes(A1.x, A1.y, A1.z, A1.w, B.y, B.w, pl.k, nE, vm);
             wl[0] = c0.res;
@@ -507,7 +530,7 @@ __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_s
                 uint32_t w[4];
 #pragma unroll
                 for (int j = 0; j < 4; j++)
-                    w[j] = ps_pack4(row[pidx[4 * j]], row[pidx[4 * j + 1]], row[pidx[4 * j + 2]], row[pidx[4 * j + 3]]);
+                    w[j] = ps_pack4(row[pidx[t][4 * j]], row[pidx[t][4 * j + 1]], row[pidx[t][4 * j + 2]], row[pidx[t][4 * j + 3]]);
                 d = make_uint4(w[0], w[1], w[2], w[3]);
             }
             // the mutations the symbols decide, in registers (population.rs:511-540)
@@ -528,7 +551,7 @@ __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_s
         PS_T(3);   // queue push
         ps_wave_sync();
 #if PS_WAVE_PREFETCH
-        {
+        if (t + 1u == T) {
             // the rows of the wave's NEXT batch -- the next one of this chunk, or the first one of the chunk it has already
             // been handed -- requested now, in flight behind the exact pass and the stores of this batch
             uint32_t nb = batch + 1u;
@@ -554,15 +577,15 @@ __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_s
             for (uint32_t rr = 0; rr < PS_ROWS; rr++) {
                 uint8_t *row = rowbuf + rr * 1024u;
                 const uint32_t site = 4u * sg + rr;
-                const ps_u4 Ar = ps_philox_l1a(site >> 1, lane, a.gen, a.k0, a.k1);
-                const ps_u4 Br = ps_philox_l1b(sg, lane, a.gen, a.k0, a.k1);
+                const ps_u4 Ar = ps_philox_l1a(site >> 1, lane, gen, a.k0, a.k1);
+                const ps_u4 Br = ps_philox_l1b(sg, lane, gen, a.k0, a.k1);
                 uint32_t cmr = ps_cand_word(Ar, site, pl.cshift) & vm;
                 uint32_t hm = 0;
                 while (cmr) {
                     const uint32_t k = ps_bit_cell(__builtin_ctz(cmr)), cellidx = i0 + k;
                     cmr &= cmr - 1u;
                     uint32_t l2y = 0;
-                    const ps_cell cell = ps_cell_events<WT>(a, Ar, Br, site, cellidx, a.gen, a.k0, a.k1, pl, l2y);
+                    const ps_cell cell = ps_cell_events<WT>(a, Ar, Br, site, cellidx, gen, a.k0, a.k1, pl, l2y);
                     if (DO_MUT && cell.mut) row[cellidx] = (uint8_t)cell.mut;
                     if (DO_HR && cell.hr) hm |= 1u << k;
                 }
@@ -572,7 +595,7 @@ __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_s
                     for (uint32_t tmp = hm; tmp;) {
                         const uint32_t k = __builtin_ctz(tmp), cellidx = i0 + k;
                         tmp &= tmp - 1u;
-                        const ps_u4 l2 = ps_philox(site, cellidx, a.gen, PS_STREAM_CORE_L2, a.k0, a.k1);
+                        const ps_u4 l2 = ps_philox(site, cellidx, gen, PS_STREAM_CORE_L2, a.k0, a.k1);
                         uint32_t donor = ps_mulhi(l2.y, a.N - 1u);
                         donor += (donor >= cellidx) ? 1u : 0u;                       // population.rs:618
                         ps_set_byte(dv, k, (uint32_t)row[donor]);
@@ -594,7 +617,7 @@ __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_s
                 if (e < qn) {
                     const uint32_t ent = ps_entry_cell(q[e]);      // cell | row << 10 = the cell's byte address in rowbuf
                     const uint32_t cellidx = ent & 1023u, rr = ent >> 10;
-                    const ps_u4 l2 = ps_philox(4u * sg + rr, cellidx, a.gen, PS_STREAM_CORE_L2, a.k0, a.k1);
+                    const ps_u4 l2 = ps_philox(4u * sg + rr, cellidx, gen, PS_STREAM_CORE_L2, a.k0, a.k1);
                     const ps_cell cell = ps_classify_site<WT>(l2.x, pl, a, 4u * sg + rr);
                     if (DO_MUT && cell.mut) rowbuf[ent] = (uint8_t)cell.mut;
                     if (DO_HR) {
@@ -627,6 +650,7 @@ __global__ void __launch_bounds__(256, PS_WAVE_LB) core_sweep_wave_kernel(core_s
                 }
             }
             ps_wave_sync();
+        }
         }
         PS_T(5);   // exact pass + HR
 

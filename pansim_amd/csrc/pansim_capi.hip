@@ -288,6 +288,7 @@ struct ps_population {
     uint32_t block_waves = 0;           // block sweep: waves per workgroup (0 = auto: 4, 8 or 16)
     bool no_block_preload = false;      // tests: block sweep reads its parent indices per batch
     uint32_t block_batch = 0;           // block sweep: segments per wave batch (0 = 4, falling back to 2; 2 = force 2)
+    uint32_t sweep_generations = 0;     // ps_sim_run, wave sweep: generations per launch (0 = choose, 1, 2; "sweep_generations" / PANSIM_SWEEP_GENERATIONS)
     uint32_t sweep_queue_cap = 0;       // tests: the sweeps treat their candidate queues / HR lists as this short (0 = real size)
     uint32_t hgt_apply_threads = 1024;  // binned HGT, LDS-image pass: threads per workgroup (256 / 512 / 1024; "hgt_apply_threads")
     uint32_t window_blocks_per_cu = 0;  // window sweep: workgroups per CU (0 = PS_WBPC)
@@ -392,6 +393,10 @@ static int pop_create_impl(const ps_config *cfg, const uint8_t *init_vec, ps_pop
     if (const char *e = getenv("PANSIM_SWEEP_BLOCKS_PER_CU")) {
         const int v = atoi(e);
         if (v >= 1 && v <= 8) p->sweep_blocks_per_cu = (uint32_t)v;
+    }
+    if (const char *e = getenv("PANSIM_SWEEP_GENERATIONS")) {
+        const int v = atoi(e);
+        if (v >= 0 && v <= (int)PS_SWEEP_MAX_GENS) p->sweep_generations = (uint32_t)v;
     }
     if (const char *e = getenv("PANSIM_HGT_MODE")) p->hgt_mode = atoi(e);
     if (const char *e = getenv("PANSIM_SWEEP_OOP")) p->sweep_oop = std::max(-1, std::min(2, atoi(e)));
@@ -597,6 +602,9 @@ extern "C" int ps_set_tuning(ps_population *p, const char *key, int64_t value)
     } else if (k == "window_sweep") {
         if (value < -1 || value > 1) return ps_fail(PS_ERR_INVALID, "window_sweep must be -1 (choose), 0 (block sweep) or 1 (window sweep where the parents are sorted)");
         p->window_sweep = (int)value;
+    } else if (k == "sweep_generations") {
+        if (value < 0 || value > (int64_t)PS_SWEEP_MAX_GENS) return ps_fail(PS_ERR_INVALID, "sweep_generations must be 0 (choose), 1 or 2");
+        p->sweep_generations = (uint32_t)value;
     } else if (k == "sweep_queue_cap") {
         if (value < 0 || value > 65536) return ps_fail(PS_ERR_INVALID, "sweep_queue_cap must be 0 (real size)..65536");
         p->sweep_queue_cap = (uint32_t)value;
@@ -999,7 +1007,7 @@ static uint32_t sweep_queue_entries(const ps_core_plan &pl, uint32_t cells, bool
 }
 
 template <bool GA, bool MU, bool HR>
-static int launch_core_sweep_wave(ps_population *p, core_sweep_args a, hipStream_t st)
+static int launch_core_sweep_wave(ps_population *p, core_sweep_args a, hipStream_t st, uint32_t gens = 1)
 {
     const uint32_t block = 256u, wpb = block / 64u;
     a.qcap = sweep_queue_entries(a.plan, std::min(1024u, (uint32_t)p->cfg.pop_size), HR);
@@ -1013,6 +1021,18 @@ static int launch_core_sweep_wave(ps_population *p, core_sweep_args a, hipStream
     const uint32_t grid = std::max(8u, std::min((want + 7u) & ~7u, 256u * bpc));   // a multiple of the 8 groups
     // (per-site rates, DESIGN.md 3.6: the variants whose exact pass reads the site's own threshold record)
     constexpr bool EV = MU || HR;
+    if (gens > 1) {
+        // several generations per pass: the generation loop's fused step only (gather + mutate [+ HR])
+        if constexpr (GA && MU) {
+            if (gens != 2u) return ps_fail(PS_ERR_INVALID, "the wave sweep applies 1 or 2 generations per launch, not %u", gens);
+            if (a.site_T) {
+                if (a.nt) hipLaunchKernelGGL((core_sweep_wave_kernel<true, true, HR, true, true, 2u>), dim3(grid), dim3(block), lds, st, a);
+                else hipLaunchKernelGGL((core_sweep_wave_kernel<true, true, HR, false, true, 2u>), dim3(grid), dim3(block), lds, st, a);
+            } else if (a.nt) hipLaunchKernelGGL((core_sweep_wave_kernel<true, true, HR, true, false, 2u>), dim3(grid), dim3(block), lds, st, a);
+            else hipLaunchKernelGGL((core_sweep_wave_kernel<true, true, HR, false, false, 2u>), dim3(grid), dim3(block), lds, st, a);
+        } else
+            return ps_fail(PS_ERR_INVALID, "the wave sweep has no several-generation form of this step");
+    } else
     if (EV && a.site_T) {
         if (a.nt) hipLaunchKernelGGL((core_sweep_wave_kernel<GA, MU, HR, true, EV>), dim3(grid), dim3(block), lds, st, a);
         else hipLaunchKernelGGL((core_sweep_wave_kernel<GA, MU, HR, false, EV>), dim3(grid), dim3(block), lds, st, a);
@@ -1177,13 +1197,17 @@ static int launch_core_sweep_window(ps_population *p, const core_sweep_args &a, 
     return PS_OK;
 }
 
+// gens > 1 (the generation loop on a wave-sweep-eligible handle, sim_sweep_generations): ONE launch applies generations
+// gen .. gen + gens - 1; d_idx_next[k] = the parents of generation gen + 1 + k
 static int launch_core_sweep(ps_population *p, const uint32_t *d_idx, uint32_t gen, bool ga, bool mu,
-                             bool hr, hipStream_t st, bool parents_sorted = false)
+                             bool hr, hipStream_t st, bool parents_sorted = false, uint32_t gens = 1,
+                             const uint32_t *const *d_idx_next = nullptr)
 {
     if (p->cfg.ncols == 0) return PS_OK;
     core_sweep_args a;
     a.state = p->state;
     a.idx = d_idx;
+    for (uint32_t k = 0; k + 1u < PS_SWEEP_MAX_GENS; k++) a.idx_next[k] = (k + 1u < gens && d_idx_next) ? d_idx_next[k] : nullptr;
     a.N = (uint32_t)p->cfg.pop_size;
     a.pitch = p->pitch;
     a.cpr = p->cpr;
@@ -1199,6 +1223,7 @@ static int launch_core_sweep(ps_population *p, const uint32_t *d_idx, uint32_t g
     if (!mu && !hr) a.plan.has_events = 0;
     if (!ga && !mu && !hr) return PS_OK;
     const bool wave = wave_sweep_eligible(p, mu, hr);
+    if (gens > 1 && !(wave && ga && mu && d_idx_next)) return ps_fail(PS_ERR_STATE, "several generations per launch need the wave sweep's fused step");
     // Out of place: the new generation goes to the second buffer and the two swap roles (an out-of-place stream has
     // a higher ceiling on this GPU than an in-place one, scripts/ubench/inplace_stream.hip); the inline fallback
     // kernel and a failed allocation of the second buffer keep the in-place form -- results are identical.
@@ -1247,7 +1272,7 @@ static int launch_core_sweep(ps_population *p, const uint32_t *d_idx, uint32_t g
     if (window) return hr ? launch_core_sweep_window<true>(p, a, st) : launch_core_sweep_window<false>(p, a, st);
 #define PS_DISPATCH(G_, M_, H_)                                              \
     if (ga == G_ && mu == M_ && hr == H_)                                    \
-        return wave ? launch_core_sweep_wave<G_, M_, H_>(p, a, st)           \
+        return wave ? launch_core_sweep_wave<G_, M_, H_>(p, a, st, gens)     \
                     : launch_core_sweep_block<G_, M_, H_>(p, a, d_idx, st);
     PS_DISPATCH(true, false, false)
     PS_DISPATCH(false, true, false)
@@ -3365,7 +3390,9 @@ extern "C" int ps_sample_pairs(uint64_t seed, uint64_t N, uint64_t P, uint32_t *
 // ---------------------------------------------------------------------------
 // generation loop (main.rs:429-464)
 // ---------------------------------------------------------------------------
-#define PS_RING 4
+// (8 slots: a launch of the core sweep may carry 2 generations, each with a slot of its own, and as many LAUNCHES as with the
+// 4 slots of one-generation launches stay in flight; see sim_accessory_half for how far the chain runs ahead)
+#define PS_RING 8
 struct ps_sim {
     ps_sim_params prm{};
     ps_derived der{};
@@ -3391,10 +3418,11 @@ struct ps_sim {
     uint64_t sigma_step = ~0ull;           // step_count the two were computed for
     bool heavy_hgt = false;             // expected HGT events per generation >= 1e7: HGT and sweep take turns
     bool slot_used[PS_RING] = {};
+    int last_sweep_slot = -1;           // the slot whose ev_core the most recent sweep launch recorded last (-1: none yet)
     int32_t *h_num_genes = nullptr, *m_num_genes = nullptr;   // pinned + its device alias
     double *h_logw = nullptr, *m_logw = nullptr, *h_avg = nullptr;
     double *d_avg = nullptr;
-    // D-avg of the NEXT generation computed ahead of the sweep (sim_one_generation): valid while the accessory matrix is the
+    // D-avg of the NEXT generation computed ahead of the sweep (sim_accessory_half): valid while the accessory matrix is the
     // one it was computed from
     bool avg_prefetched = false;
     uint64_t avg_epoch = 0;
@@ -3472,6 +3500,7 @@ extern "C" void ps_sim_destroy(ps_sim *s)
 }
 
 static int sim_refresh_rows(void *ctx);
+static uint32_t sim_sweep_generations(ps_sim *s);
 
 static int sim_create_impl(const ps_sim_params *p, ps_sim *s)
 {
@@ -3548,17 +3577,30 @@ static int sim_create_impl(const ps_sim_params *p, ps_sim *s)
         if (block_sweep_geometry(s->core, true, true, p->HR_rate > 0.0, &g, &lds, &nw))
             s->acc->hgt_list_in_global = lds + 16384u > s->core->lds_limit;
     }
-    // light HGT co-runs with the sweep: launch it narrow when the sweep is long enough to hide it.
-    // The chain of a generation is ~0.3 ms of latency-bound work plus ~1 us per event a thread handles
-    // in sequence; it is given half of what the sweep (estimated at 4.2 TB/s) leaves, at most 112
-    // events per thread (cfg2, generations/s at 32 / 64 / 128 / 192 / 256 / 384 events per thread:
-    // 1690 / 1736 / 1781 / 1775 / 1727 / 1480).  A short sweep leaves the accessory chain critical,
-    // which wants the whole chip (0).  An adaptive controller (widen when the core stream is found
-    // idle) was tried and lost to its own overshoots.
+    // light HGT co-runs with the sweep: launch it narrow when the sweep is long enough to hide it.  The narrower it runs
+    // (the more events a thread handles in sequence) the less it takes from the sweep, and the longer the chain of a
+    // generation gets; the chain must stay inside the time the sweep takes PER GENERATION, launch(T) / T.
+    //  * Two generations per launch (profiles/sweep_two_generations.md): the launch is bound by its vector instructions
+    //    (cfg2: 0.65 ms = 2 N L bytes at 3.7 TB/s), the chain measures ~0.25 ms + 0.4 us per event a thread handles
+    //    (0.11 ms with the whole chip to itself), and 95 % of launch / 2 is what it gets -- cfg2, generations/s at 0 / 32 /
+    //    64 / 96 / 112 / 144 / 192 / 256 / 384 events per thread: 2470 / 2545 / 2582 / 2844 / 2837-2905 / 2918-2931 / 2944 /
+    //    2811 / 2467 (past ~200 the period follows the chain, below ~100 the wide HGT kernel slows the launch).
+    //  * One generation per launch (the form before, kept for A/B runs at PANSIM_SWEEP_GENERATIONS=1): half of what a
+    //    sweep estimated at 4.2 TB/s leaves beyond 0.3 ms, at most 112 (cfg2 at 32 / 64 / 128 / 192 / 256 / 384: 1690 /
+    //    1736 / 1781 / 1775 / 1727 / 1480).
+    // A short sweep leaves the accessory chain critical, which wants the whole chip (0).  An adaptive controller (widen
+    // when the core stream is found idle) was tried and lost to its own overshoots.
     {
-        const double sweep_ms = 2.0 * (double)N * (double)s->core->cfg.ncols / 4.2e12 * 1e3;
-        const double ept = (sweep_ms - 0.3) / 1.0e-3 * 0.5;
-        s->acc->hgt_events_per_thread = ept >= 16.0 ? (uint32_t)std::min(ept, 112.0) : 0u;   // (at 7 sweep blocks per CU: 96 / 112 / 128 / 160 / 192 -> 1785 / 1815 / 1821 / 1826 / 1700)
+        const double bytes = 2.0 * (double)N * (double)s->core->cfg.ncols;
+        double ept;
+        if (sim_sweep_generations(s) >= 2u) {
+            const double per_gen_ms = bytes / 3.7e12 * 1e3 / 2.0;
+            ept = std::min((0.95 * per_gen_ms - 0.25) / 0.4e-3, 192.0);
+        } else {
+            const double sweep_ms = bytes / 4.2e12 * 1e3;
+            ept = std::min((sweep_ms - 0.3) / 1.0e-3 * 0.5, 112.0);
+        }
+        s->acc->hgt_events_per_thread = ept >= 16.0 ? (uint32_t)ept : 0u;
         if (const char *e = getenv("PANSIM_HGT_EVENTS_PER_THREAD")) s->acc->hgt_events_per_thread = (uint32_t)atoi(e);
     }
     HIPCHK(hipEventCreateWithFlags(&s->ev_hgt, hipEventDisableTiming));
@@ -3701,7 +3743,22 @@ static int sim_host_weights(ps_sim *s, uint32_t gen, double *w, bool avg_ready =
     return PS_OK;
 }
 
-static int sim_one_generation(ps_sim *s, uint32_t gen)
+// the light form of HGT (main.rs:462-464) of generation `gen`, beside the sweep; the heavy form takes turns with it (below)
+static int sim_light_hgt(ps_sim *s, uint32_t gen)
+{
+    const bool heavy_hgt = s->prm.HGT_rate > 0.0 && s->heavy_hgt;
+    if (s->prm.HGT_rate > 0.0 && !heavy_hgt) PSCHK(launch_acc_hgt(s->acc, gen, s->acc->stream));
+    return PS_OK;
+}
+
+// A generation has two halves.  The ACCESSORY half (main.rs:435-447, :455, :462-464 for the accessory matrix) draws the
+// parents into the generation's ring slot and runs the accessory chain; it needs nothing of the core matrix.  The CORE half
+// is the sweep, which needs nothing but the parents (ev_idx of the slot) -- so a launch of the wave sweep can wait for the
+// accessory halves of `gens` generations and apply them all in one pass over the matrix (core_sweep_wave_kernel, T).
+// sim_accessory_half: generation `gen` into slot step_count % PS_RING; `gens` is the number of generations the sweep
+// launches carry (how far the chain may run ahead), light_hgt whether the light-form HGT is launched here or left to the
+// caller (sim_light_hgt, after the sweep's launch).
+static int sim_accessory_half(ps_sim *s, uint32_t gen, uint32_t gens, bool light_hgt)
 {
     ps_population *core = s->core, *acc = s->acc;
     const ps_sim_params &p = s->prm;
@@ -3710,9 +3767,15 @@ static int sim_one_generation(ps_sim *s, uint32_t gen)
     const int slot = (int)(s->step_count % PS_RING);
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
-    // the slot's previous core sweep must have consumed its indices
+    // The chain runs at most 4 sweep LAUNCHES ahead: the sweep of generation gen - 4 * gens must have completed (with
+    // two-generation launches that is the slot's own previous use -- its indices consumed; with one generation per launch
+    // the slot 4 back, the depth the loop has always had)
     auto th0 = clk::now();
-    if (s->slot_used[slot]) HIPCHK(hipEventSynchronize(s->ev_core[slot]));
+    {
+        const int back = (int)std::min<uint32_t>(4u * gens, PS_RING);
+        const int wslot = (slot + PS_RING - back) % PS_RING;
+        if (s->slot_used[wslot]) HIPCHK(hipEventSynchronize(s->ev_core[wslot]));
+    }
     s->host_wait_ms += ms_since(th0);
     // main.rs:435-443: the weights of sample_indices -- from this shard's own replica of the accessory matrix, or (several
     // shards in one process) computed once by shard 0 and handed to the others, whose replicas are bit-identical
@@ -3777,7 +3840,8 @@ static int sim_one_generation(ps_sim *s, uint32_t gen)
     // generation g+1 hides behind sweep(g).
     const bool heavy_hgt = p.HGT_rate > 0.0 && s->heavy_hgt;
     if (heavy_hgt) {
-        const int prev = (slot + PS_RING - 1) % PS_RING;
+        // (inside a block of generations that share a launch the previous sweep is the previous BLOCK's)
+        const int prev = s->last_sweep_slot;
         // only the LDS-image passes (apply, reduce) wait for the previous sweep: the bin pass -- LDS-local
         // gathers, streaming appends -- runs beside its tail (cfg3: 1359 -> 1411 generations/s)
         HIPCHK(hipEventRecord(s->ev_hgt, sa));       // (recorded again after the LDS-image pass; this one covers an HGT that launches nothing)
@@ -3785,7 +3849,7 @@ static int sim_one_generation(ps_sim *s, uint32_t gen)
         // 0.66 / 0.66 -- what sits between two sweeps is the bin pass finishing late, not the event latency; profiles/r05_sweep_experiments.md 8)
         static const bool gap_on_core = getenv("PANSIM_GAP_ON_CORE_STREAM") && atoi(getenv("PANSIM_GAP_ON_CORE_STREAM")) != 0;
         if (gap_on_core && !s->ev_bin) HIPCHK(hipEventCreateWithFlags(&s->ev_bin, hipEventDisableTiming));
-        PSCHK(launch_acc_hgt(acc, gen, sa, s->slot_used[prev] ? s->ev_core[prev] : nullptr, s->ev_hgt, gap_on_core ? sc : nullptr, s->ev_bin));
+        PSCHK(launch_acc_hgt(acc, gen, sa, prev >= 0 ? s->ev_core[prev] : nullptr, s->ev_hgt, gap_on_core ? sc : nullptr, s->ev_bin));
         HIPCHK(hipStreamWaitEvent(sc, s->ev_hgt, 0));      // (a no-op when the event was recorded on sc itself)
     }
 
@@ -3808,8 +3872,23 @@ static int sim_one_generation(ps_sim *s, uint32_t gen)
         }
     }
 
-    // main.rs:445, :452, :459-461 on the core stream, one fused pass
-    HIPCHK(hipStreamWaitEvent(sc, s->ev_idx[slot], 0));
+    // (the light-form HGT of a block's LAST generation is enqueued after the sweep so that the sweep's launch is not queued behind it)
+    if (light_hgt) PSCHK(sim_light_hgt(s, gen));
+    s->step_count++;
+    return PS_OK;
+}
+
+// main.rs:445, :452, :459-461 on the core stream, one fused pass over the matrix for generations first .. first + gens - 1,
+// whose accessory halves have been enqueued (they hold the last `gens` ring slots)
+static int sim_core_half(ps_sim *s, uint32_t first, uint32_t gens)
+{
+    ps_population *core = s->core;
+    const ps_sim_params &p = s->prm;
+    hipStream_t sc = core->stream;
+    int slots[PS_SWEEP_MAX_GENS];
+    for (uint32_t t = 0; t < gens; t++) slots[t] = (int)((s->step_count + PS_RING - gens + t) % PS_RING);
+    const int slot = slots[gens - 1u];
+    HIPCHK(hipStreamWaitEvent(sc, s->ev_idx[slot], 0));      // (the accessory stream records them in order: the last one covers all)
     hipEvent_t t0 = nullptr, t1 = nullptr;
     if (s->timing) {
         auto take = [&](hipEvent_t *e) -> int {
@@ -3831,19 +3910,42 @@ static int sim_one_generation(ps_sim *s, uint32_t gen)
         }
         HIPCHK(hipEventRecord(s->ev_gap[slot][0], sc));
     }
-    PSCHK(step_device(core, s->d_idx[slot], gen, true, true, p.HR_rate > 0.0, sc, nullptr, true));
+    const uint32_t *next[PS_SWEEP_MAX_GENS] = {};
+    for (uint32_t t = 1; t < gens; t++) next[t - 1u] = s->d_idx[slots[t]];
+    PSCHK(launch_core_sweep(core, s->d_idx[slots[0]], first, true, true, p.HR_rate > 0.0, sc, true, gens, next));
     if (s->timing) {
         HIPCHK(hipEventRecord(t1, sc));
         s->tev.emplace_back(t0, t1);
     } else {
         HIPCHK(hipEventRecord(s->ev_gap[slot][1], sc));
     }
-    HIPCHK(hipEventRecord(s->ev_core[slot], sc));
-    // HGT is enqueued after the sweep so that the sweep's launch is not queued behind it
-    if (p.HGT_rate > 0.0 && !heavy_hgt) PSCHK(launch_acc_hgt(acc, gen, sa));
-    s->slot_used[slot] = true;
-    s->step_count++;
+    for (uint32_t t = 0; t < gens; t++) {
+        HIPCHK(hipEventRecord(s->ev_core[slots[t]], sc));
+        s->slot_used[slots[t]] = true;
+    }
+    s->last_sweep_slot = slot;
     return PS_OK;
+}
+
+// Generations per launch of the core sweep in ps_sim_run: 2 where the wave sweep takes the loop's fused step (N <= 1024,
+// rates the queued sweeps admit; site shards included -- the blocking is per site row), 1 for the window / block / inline
+// sweeps.  "sweep_generations" (ps_set_tuning on the core handle) / PANSIM_SWEEP_GENERATIONS override the choice where two
+// are possible.
+static uint32_t sim_sweep_generations(ps_sim *s)
+{
+    ps_population *core = s->core;
+    if (core->cfg.ncols == 0 || !core->cplan.has_events) return 1u;
+    if (!wave_sweep_eligible(core, true, s->prm.HR_rate > 0.0)) return 1u;
+    if (core->sweep_generations) return std::min<uint32_t>(core->sweep_generations, PS_SWEEP_MAX_GENS);
+    return 2u;
+}
+
+// `gens` generations first .. first + gens - 1 with one sweep launch
+static int sim_generations(ps_sim *s, uint32_t first, uint32_t gens, uint32_t depth)
+{
+    for (uint32_t t = 0; t < gens; t++) PSCHK(sim_accessory_half(s, first + t, depth, t + 1u < gens));
+    PSCHK(sim_core_half(s, first, gens));
+    return sim_light_hgt(s, first + gens - 1u);
 }
 
 // PANSIM_EXCHANGE_BESIDE_SWEEP=1 (experiment): a donor-sharded run lets sweep(g) start behind the LDS-image pass of HGT(g)
@@ -4005,7 +4107,12 @@ extern "C" int ps_sim_run(ps_sim *s, uint32_t first_generation, uint32_t count)
 {
     if (!s) return ps_fail(PS_ERR_INVALID, "null handle");
     PSCHK(use_device(s->core));
-    for (uint32_t g = 0; g < count; g++) PSCHK(sim_one_generation(s, first_generation + g));
+    // blocks of T generations per sweep launch, then the remainder one by one (a run split anywhere gives the same state:
+    // every generation is keyed on its own number, whichever launch carries it)
+    const uint32_t T = sim_sweep_generations(s);
+    uint32_t g = 0;
+    for (; g + T <= count; g += T) PSCHK(sim_generations(s, first_generation + g, T, T));
+    for (; g < count; g++) PSCHK(sim_generations(s, first_generation + g, 1u, T));
     return PS_OK;
 }
 
@@ -4375,7 +4482,7 @@ static int multi_weights(void *vctx, ps_sim *s, uint32_t gen, double *w)
     // D-avg sharded by rows over the shards like the HGT donors: every shard computes its rows and takes part in the exchange
     bool avg_ready = false;
     if (m->prm.competition_strength > 0.0 && s->acc->exchange && s->acc->donor_cnt != 0 && s->acc->d.G > 0) {
-        // (every shard takes the same branch: the flags are set in lockstep by sim_one_generation)
+        // (every shard takes the same branch: the flags are set in lockstep by sim_accessory_half)
         if (!(s->avg_prefetched && s->avg_epoch == s->acc->edit_epoch)) PSCHK(sim_average_distance(s));
         avg_ready = true;
     }
