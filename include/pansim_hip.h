@@ -402,6 +402,45 @@ int ps_sim_host_timing(ps_sim *s, int reset, uint64_t *generations, double *wait
                        double *draw_ms);
 
 /* ------------------------------------------------------------------------ */
+/* state files: save a run, continue it bit for bit, or branch off it        */
+/* ------------------------------------------------------------------------ */
+/* The reference has no counterpart (a run lives and dies with main()).  Every random decision here is a function of (seed,
+ * stream, generation, site, internal row), so the state of a run is its two matrices in INTERNAL row order, the
+ * generation number and the row maps of DESIGN.md 3.5; docs/STATE_FORMAT.md specifies the file, DESIGN.md 3.7 the semantics.
+ * The core matrix of a simulated population is one-hot and is stored at 2 bits per cell (PS_STATE_PACKED2; packed and
+ * unpacked by kernels, in chunks through pinned buffers: no N x L host copy); a matrix that is not one-hot -- bytes loaded with
+ * ps_load_matrix -- is stored as it is (PS_STATE_RAW8).  NOT stored: selection coefficients, pair list, plans and tables
+ * (functions of the parameters), tuning keys, and the per-site weight vectors, which are state of the handles: call
+ * ps_sim_set_site_weights again after ps_sim_load.  One file per ps_sim; a ps_multi run is saved shard by shard,
+ * ps_sim_save(ps_multi_shard(m, k), ...), and loaded as one ps_sim per shard. */
+enum { PS_STATE_PACKED2 = 1, PS_STATE_RAW8 = 2 };
+typedef struct {
+    uint32_t version, core_encoding;         /* format version (1); PS_STATE_PACKED2 / PS_STATE_RAW8 */
+    uint64_t generations_done;               /* g0: generations [0, g0) have been applied */
+    uint64_t pan_size, site_begin, site_end; /* accessory genes; this shard's core sites [site_begin, site_end) */
+    uint64_t pitch;                          /* cells per stored core row (pop_size rounded up to 128) */
+    uint64_t core_offset, core_bytes, acc_offset, acc_bytes, maps_offset, maps_bytes, per_gen_offset, per_gen_bytes;
+    int32_t has_row_maps;                    /* 0: internal order == output order, no last parents (no generation yet) */
+    int32_t core_rows_overridden, acc_rows_overridden;   /* a direct ps_load_matrix / ps_step made that handle's orders coincide */
+    int32_t has_per_gen;                     /* a per-generation section (4 doubles per generation) is present */
+} ps_state_header;
+/* Write the state of the run after its last queued generation (waits for it; the run may go on afterwards, unperturbed).
+ * per_gen: 4 x generations_done doubles kept for the caller (the CLI's _per_gen.tsv rows), or NULL. */
+int ps_sim_save(ps_sim *s, const char *path, const double *per_gen);
+/* A new ps_sim from a file.  params == NULL: the saved parameters (on the current device) -- ps_sim_run(s, g0, count) then
+ * continues the saved run bit for bit.  params != NULL: a BRANCH -- pop_size, core_size, pan_genes, core_genes (hence
+ * pan_size), shard_rank and shard_count must equal the file's (else PS_ERR_INVALID, the message names the field);
+ * everything else, the seed included, is the caller's: selection coefficients, pair list, rates and plans are derived from
+ * `params`.  Unreadable / short file, bad magic or version, checksum mismatch: PS_ERR_IO, the message names the section.
+ * A failed load leaves no handle and no device memory behind. */
+int ps_sim_load(const char *path, const ps_sim_params *params, ps_sim **out);
+/* g0 of a loaded run; first + count of the last ps_sim_run */
+uint32_t ps_sim_generations_done(ps_sim *s);
+/* The header of a file, no device touched (as ps_site_tables): saved parameters, generations_done, encoding, section sizes.
+ * per_gen_out (cap doubles; may be NULL): the per-generation section, checksum verified.  Any output may be NULL. */
+int ps_state_info(const char *path, ps_sim_params *params_out, ps_state_header *hdr_out, double *per_gen_out, uint64_t cap);
+
+/* ------------------------------------------------------------------------ */
 /* one process, several devices: the run sharded by core site  */
 /* ------------------------------------------------------------------------ */
 /* main() of the reference is one process (main.rs:429-553).  ps_multi holds one ps_sim per site shard,

@@ -49,6 +49,18 @@ class Derived(C.Structure):
                 ("n_pan_mutations", C.c_double * 2), ("n_recombinations_pan", C.c_double * 2)]
 
 
+class StateHeader(C.Structure):
+    """ps_state_header: what ps_state_info reads from a state file (docs/STATE_FORMAT.md)"""
+    _fields_ = [("version", C.c_uint32), ("core_encoding", C.c_uint32), ("generations_done", C.c_uint64),
+                ("pan_size", C.c_uint64), ("site_begin", C.c_uint64), ("site_end", C.c_uint64), ("pitch", C.c_uint64),
+                ("core_offset", C.c_uint64), ("core_bytes", C.c_uint64), ("acc_offset", C.c_uint64),
+                ("acc_bytes", C.c_uint64), ("maps_offset", C.c_uint64), ("maps_bytes", C.c_uint64),
+                ("per_gen_offset", C.c_uint64), ("per_gen_bytes", C.c_uint64), ("has_row_maps", C.c_int32),
+                ("core_rows_overridden", C.c_int32), ("acc_rows_overridden", C.c_int32), ("has_per_gen", C.c_int32)]
+
+
+PS_STATE_PACKED2, PS_STATE_RAW8 = 1, 2
+
 # every symbol include/pansim_hip.h declares (tests/test_host_logic.py::test_library_exports_every_declared_symbol checks the header against this)
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -130,6 +142,10 @@ SIGNATURES = {
     "ps_sim_pairwise_distances": (_int, [_vp, _f64p, _f64p]),
     "ps_sim_distance_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_sim_host_timing": (_int, [_vp, _int, C.POINTER(_u64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_sim_save": (_int, [_vp, C.c_char_p, _vp]),
+    "ps_sim_load": (_int, [C.c_char_p, C.POINTER(SimParams), C.POINTER(_vp)]),
+    "ps_sim_generations_done": (_u32, [_vp]),
+    "ps_state_info": (_int, [C.c_char_p, C.POINTER(SimParams), C.POINTER(StateHeader), _vp, _u64]),
     "ps_multi_create": (_int, [C.POINTER(SimParams), _int, C.POINTER(_int), C.POINTER(_vp)]),
     "ps_multi_destroy": (None, [_vp]),
     "ps_multi_shards": (_int, [_vp]),

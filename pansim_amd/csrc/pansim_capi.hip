@@ -3431,6 +3431,7 @@ struct ps_sim {
     hipEvent_t ev_bin = nullptr;     // the bin pass of the binned HGT is complete (the LDS-image pass on the core stream waits for it)
     double *d_log1p = nullptr;          // ln(1 + s_g) of THIS run (the accessory handle's own table belongs to its Population API)
     uint64_t step_count = 0;
+    uint64_t gens_done = 0;             // first + count of the last ps_sim_run, or g0 of the state file the run was loaded from
     bool need_logw = false;
     // P-draw on the device (populations of >= 4096: the N binary searches over the cumulative table are the
     // largest part of the host half there, and the host half does not shrink with the number of site shards)
@@ -4113,6 +4114,7 @@ extern "C" int ps_sim_run(ps_sim *s, uint32_t first_generation, uint32_t count)
     uint32_t g = 0;
     for (; g + T <= count; g += T) PSCHK(sim_generations(s, first_generation + g, T, T));
     for (; g < count; g++) PSCHK(sim_generations(s, first_generation + g, 1u, T));
+    s->gens_done = (uint64_t)first_generation + count;
     return PS_OK;
 }
 
@@ -4873,6 +4875,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
     PSCHK(rc);
     return ps_write(m->shard[0]->acc, outpref);
 }
+
+// state files (ps_sim_save, ps_sim_load, ps_state_info)
+#include "state_file.h"
 
 // the native RCCL provider of ps_exchange_fn (ps_rccl_*, ps_exchange_rccl)
 #include "exchange_rccl.h"

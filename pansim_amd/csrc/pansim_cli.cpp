@@ -50,6 +50,8 @@ static const Flag FLAGS[] = {
 static const Flag EXT_FLAGS[] = {
     { "gpus", "Number of core-site shards, one per GPU (more shards than GPUs share them). Results do not depend on it.", "1", true },
     { "reference_seed_stream", "Draw the selection coefficients from the reference's own seeded stream (ChaCha12 StdRng, restated from the published algorithms of the rand / statrs crates, ziggurat tables recomputed: UNVERIFIED against a Pansim binary) instead of the build's Philox stream.", nullptr, false },
+    { "save_state", "Write the state of the run after its last generation to this file (ps_sim_save), beside the usual outputs. One shard only (--gpus 1).", "", true },
+    { "load_state", "Start from a state file instead of a clonal population: --n_gen stays the TOTAL, generations [saved, n_gen) are run. pop_size, core_size, pan_genes and core_genes must be the file's; every other flag is this command line's (the same flags continue the saved run bit for bit, other flags branch off it). With --print_dist the earlier rows of _per_gen.tsv come from the file, which must have been saved with --print_dist. One shard only (--gpus 1).", "", true },
 };
 
 // clap 3's layout (the reference's own `pansim --help`, /root/reference/README.md:40-138): the options sorted by clap's
@@ -81,7 +83,7 @@ static void print_flag(const Flag &f, const char *short_name)
     if (f.takes_value) printf(" <%s>", f.name);
     printf("\n");
     std::string text = f.help;
-    if (f.takes_value) text += std::string(" [default: ") + f.def + "]";
+    if (f.takes_value && *f.def) text += std::string(" [default: ") + f.def + "]";      // (the file flags of the extensions have none)
     print_wrapped(text, 12, 100);
 }
 
@@ -290,10 +292,43 @@ int main(int argc, char **argv)
     // one ps_sim per core-site shard (one shard: the plain run); main.rs:372-427
     const uint64_t n_shards = as_u64(val, "gpus");
     if (n_shards < 1 || n_shards > 1024) die(101, "pansim: --gpus must be 1..1024");
-    ps_multi *multi = nullptr;
-    CK(ps_multi_create(&p, (int)n_shards, nullptr, &multi));
-    ps_sim *sim = ps_multi_shard(multi, 0);
+    const std::string save_state = val["save_state"], load_state = val["load_state"];
+    if (n_shards > 1 && !(save_state.empty() && load_state.empty()))
+        die(101, "pansim: --save_state / --load_state need --gpus 1: a sharded run is saved shard by shard through the library "
+                 "(ps_multi_shard + ps_sim_save) and loaded as one ps_sim per shard");
     const uint64_t G = d.pan_size, P = p.max_distances;
+    std::vector<double> avg_core(p.n_gen), avg_acc(p.n_gen), std_core(p.n_gen), std_acc(p.n_gen);
+    // a fresh run goes through ps_multi (one shard: the plain run); a LOADED run is a plain ps_sim, driven by the ps_sim_*
+    // calls ps_multi itself makes for one shard
+    ps_multi *multi = nullptr;
+    ps_sim *sim = nullptr;
+    int32_t g0 = 0;
+    if (!load_state.empty()) {
+        ps_state_header sh;
+        CK(ps_state_info(load_state.c_str(), nullptr, &sh, nullptr, 0));
+        if ((uint64_t)p.n_gen < sh.generations_done)
+            die(101, "pansim: --n_gen is the total number of generations: " + load_state + " already holds " + std::to_string(sh.generations_done)
+                         + ", --n_gen " + std::to_string(p.n_gen) + " asks for fewer");
+        g0 = (int32_t)sh.generations_done;
+        if (p.print_dist) {
+            if (!sh.has_per_gen)
+                die(101, "pansim: " + load_state + " was saved without --print_dist: it has no rows of _per_gen.tsv for its "
+                             + std::to_string(g0) + " generations, so this run cannot print them");
+            std::vector<double> rows(4 * (size_t)g0 + 1);
+            CK(ps_state_info(load_state.c_str(), nullptr, nullptr, rows.data(), rows.size()));
+            for (int32_t j = 0; j < g0; j++) {
+                avg_core[j] = rows[4 * j]; std_core[j] = rows[4 * j + 1]; avg_acc[j] = rows[4 * j + 2]; std_acc[j] = rows[4 * j + 3];
+            }
+        }
+        CK(ps_sim_load(load_state.c_str(), &p, &sim));
+        if (p.verbose) printf("Loaded %d generations from %s, running generations %d to %d\n", g0, load_state.c_str(), g0 + 1, p.n_gen);
+    } else {
+        CK(ps_multi_create(&p, (int)n_shards, nullptr, &multi));
+        sim = ps_multi_shard(multi, 0);
+    }
+    auto run = [&](uint32_t first, uint32_t count) { return multi ? ps_multi_run(multi, first, count) : ps_sim_run(sim, first, count); };
+    auto sync = [&]() { return multi ? ps_multi_sync(multi) : ps_sim_sync(sim); };
+    auto distances = [&](double *c, double *a) { return multi ? ps_multi_pairwise_distances(multi, c, a) : ps_sim_pairwise_distances(sim, c, a); };
 
     if (p.print_selection) {                                           // main.rs:321-331
         FILE *f = fopen((outpref + "_selection.tsv").c_str(), "w");
@@ -305,15 +340,12 @@ int main(int argc, char **argv)
     }
 
     ps_population *acc = ps_sim_acc(sim);      // replicated on every shard
-    std::vector<double> avg_core(p.n_gen), avg_acc(p.n_gen), std_core(p.n_gen), std_acc(p.n_gen);
     std::vector<double> cd(P), ad(P);
     const bool stepwise = p.print_dist || p.verbose;
-    if (!stepwise) CK(ps_multi_run(multi, 0, (uint32_t)p.n_gen));      // main.rs:429-464
-    for (int32_t j = 0; j < p.n_gen; j++) {
-        if (stepwise) CK(ps_multi_run(multi, (uint32_t)j, 1));
-        if (j == p.n_gen - 1) {                                        // main.rs:467-499
-            CK(ps_multi_sync(multi));
-            CK(ps_multi_pairwise_distances(multi, cd.data(), ad.data()));
+    auto final_outputs = [&]() {                                       // main.rs:467-499
+        {
+            CK(sync());
+            CK(distances(cd.data(), ad.data()));
             FILE *f = fopen((outpref + ".tsv").c_str(), "w");
             if (!f) die(1, "Error: cannot create " + outpref + ".tsv");
             write_pairs_tsv(f, cd, ad);
@@ -325,16 +357,22 @@ int main(int argc, char **argv)
             for (double x : freqs) fprintf(f, "%s\n", fmt(x).c_str());
             fclose(f);
         }
+    };
+    if (!stepwise && p.n_gen > g0) CK(run((uint32_t)g0, (uint32_t)(p.n_gen - g0)));      // main.rs:429-464
+    if (g0 > 0 && g0 == p.n_gen) final_outputs();                       // (a loaded state that is already at --n_gen)
+    for (int32_t j = g0; j < p.n_gen; j++) {
+        if (stepwise) CK(run((uint32_t)j, 1));
+        if (j == p.n_gen - 1) final_outputs();
         if (p.print_dist) {                                            // main.rs:502-519
-            CK(ps_multi_sync(multi));
-            CK(ps_multi_pairwise_distances(multi, cd.data(), ad.data()));
+            CK(sync());
+            CK(distances(cd.data(), ad.data()));
             CK(ps_standard_deviation(cd.data(), P, &std_core[j], &avg_core[j]));
             CK(ps_standard_deviation(ad.data(), P, &std_acc[j], &avg_acc[j]));
         }
         if (p.verbose) {                                               // main.rs:522-526
             printf("Finished gen: %d\n", j + 1);
             double gf = 0.0;
-            CK(ps_multi_sync(multi));
+            CK(sync());
             CK(ps_calc_gene_freq(acc, &gf));
             printf("avg_gene_freq: %s\n", fmt(gf).c_str());
         }
@@ -348,8 +386,17 @@ int main(int argc, char **argv)
         fclose(f);
     }
     if (p.print_matrices) {                                            // main.rs:550-553 (errors ignored)
-        (void)ps_multi_write(multi, outpref.c_str());
+        if (multi) (void)ps_multi_write(multi, outpref.c_str());
+        else if (ps_write(ps_sim_core(sim), outpref.c_str()) == PS_OK) (void)ps_write(acc, outpref.c_str());
     }
-    ps_multi_destroy(multi);
+    if (!save_state.empty()) {
+        // the rows of _per_gen.tsv travel with the state, so that a continuation with --print_dist prints all of them
+        std::vector<double> rows;
+        for (int32_t j = 0; p.print_dist && j < p.n_gen; j++) rows.insert(rows.end(), { avg_core[j], std_core[j], avg_acc[j], std_acc[j] });
+        rows.push_back(0.0);                                           // (never an empty vector's null pointer)
+        CK(ps_sim_save(sim, save_state.c_str(), p.print_dist ? rows.data() : nullptr));
+    }
+    if (multi) ps_multi_destroy(multi);
+    else ps_sim_destroy(sim);
     return 0;
 }

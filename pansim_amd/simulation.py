@@ -2,11 +2,12 @@
 parameter validation/derivation, the seeded host draws and the generation loop.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
 from . import _lib
-from ._lib import Derived, SimParams, check
+from ._lib import Derived, SimParams, StateHeader, check
 from .population import Population, fmt_f64, standard_deviation
 
 # flag names and defaults of main.rs:21-151
@@ -55,6 +56,23 @@ def sample_pairs(seed, pop_size, max_distances):
     r2 = np.zeros(max_distances, np.uint32)
     check(_lib.load().ps_sample_pairs(int(seed), int(pop_size), int(max_distances), r1, r2))
     return r1, r2
+
+
+def state_info(path, per_gen=False):
+    """the header of a state file, no device touched (ps_state_info): dict(params=SimParams, header=StateHeader,
+    generations_done, encoding "packed2" / "raw8"; per_gen=True adds per_gen, the (generations_done, 4) rows, or None)"""
+    lib = _lib.load()
+    p, h = SimParams(), StateHeader()
+    check(lib.ps_state_info(os.fsencode(path), C.byref(p), C.byref(h), None, 0))
+    out = dict(params=p, header=h, generations_done=int(h.generations_done),
+               encoding={_lib.PS_STATE_PACKED2: "packed2", _lib.PS_STATE_RAW8: "raw8"}[h.core_encoding])
+    if per_gen:
+        out["per_gen"] = None
+        if h.has_per_gen:
+            rows = np.zeros(max(h.per_gen_bytes // 8, 1))
+            check(lib.ps_state_info(os.fsencode(path), None, None, rows.ctypes.data, rows.size))
+            out["per_gen"] = rows[:h.per_gen_bytes // 8].reshape(-1, 4)
+    return out
 
 
 class Simulation:
@@ -108,6 +126,46 @@ class Simulation:
 
     def sync(self):
         check(self._lib.ps_sim_sync(self._h))
+
+    # -- state files (ps_sim_save / ps_sim_load; docs/STATE_FORMAT.md) -----------------
+    def save(self, path, per_gen=None):
+        """write the state after the last queued generation (waits for it; the run may go on, unperturbed).  `per_gen`:
+        (generations_done, 4) doubles kept for the caller (the CLI's _per_gen.tsv rows), or None.  Per-site weights are
+        not stored: call set_site_weights again after load()."""
+        rows = None
+        if per_gen is not None:
+            rows = np.ascontiguousarray(per_gen, np.float64).reshape(-1)
+            if rows.size != 4 * self.generations_done:
+                raise ValueError("per_gen must hold 4 values for each of the %d generations done" % self.generations_done)
+            if rows.size == 0:
+                rows = np.zeros(1)
+        check(self._lib.ps_sim_save(self._h, os.fsencode(path), rows.ctypes.data if rows is not None else None))
+
+    @classmethod
+    def load(cls, path, params=None):
+        """a Simulation from a state file.  params None: the saved parameters -- run(count) continues the saved run bit
+        for bit (self.generation starts at the file's generations_done).  Otherwise a branch: the sizes and the shard
+        must be the file's, everything else (seed included) is `params`'."""
+        lib = _lib.load()
+        h = C.c_void_p()
+        check(lib.ps_sim_load(os.fsencode(path), C.byref(params) if params is not None else None, C.byref(h)))
+        try:
+            if params is None:
+                params = SimParams()
+                check(lib.ps_state_info(os.fsencode(path), C.byref(params), None, None, 0))
+                params.device = -1
+            sim = cls(params, _handle=h.value)
+        except Exception:
+            lib.ps_sim_destroy(h)
+            raise
+        sim._owned = True
+        sim.generation = sim.generations_done
+        return sim
+
+    @property
+    def generations_done(self):
+        """generations_done of the file a loaded run came from; first + count of the last run()"""
+        return int(self._lib.ps_sim_generations_done(self._h))
 
     def last_parents(self):
         out = np.zeros(self.params.pop_size, np.uint32)
@@ -254,5 +312,5 @@ class MultiSimulation:
         check(self._lib.ps_multi_write(self._h, str(outpref).encode()))
 
 
-__all__ = ["Simulation", "MultiSimulation", "make_params", "validate", "derive", "selection_coefficients", "sample_pairs",
+__all__ = ["Simulation", "MultiSimulation", "make_params", "state_info", "validate", "derive", "selection_coefficients", "sample_pairs",
            "DEFAULTS", "standard_deviation"]
