@@ -203,6 +203,35 @@ enum {
 int ps_last_sweep_form(ps_population *p);
 /* Population::gene_frequencies (population.rs:840-863): ncols + core_genes values */
 int ps_gene_frequencies(ps_population *p, double *out);
+/* Core allele counts and diversity (docs/CORE_DIVERSITY.md).  The reference has no such function: these are the core
+ * counterparts of Population::gene_frequencies (population.rs:840-863), which answers for the accessory matrix only.  One
+ * streaming pass over the site-major matrix, ordered on the handle's stream behind every queued generation; column sums do
+ * not depend on the row order, so the calls are valid on a simulation's handle at any point.  The classes of a site are A, C,
+ * G, T (bytes 1, 2, 4, 8) and `other` (any other byte: only after ps_load_matrix of arbitrary bytes), which counts in no
+ * column.  An accessory handle fails with PS_ERR_INVALID (use ps_gene_frequencies).  A site-shard handle (ncols !=
+ * global_cols) answers for its own columns, sites = ncols: every field except the double adds across shards. */
+typedef struct {
+    uint64_t pop_size, sites;          /* N; columns this result covers */
+    uint64_t other_cells;              /* cells that are not 1/2/4/8 */
+    uint64_t segregating_sites;        /* sites where at least two of the five classes are non-empty */
+    uint64_t pair_differences;         /* sum over i<j of differing sites = sum over sites of (N^2 - sum_c n_c^2) / 2 */
+    uint64_t base_cells[4];            /* A, C, G, T totals */
+    double   mean_pairwise_distance;   /* (double)pair_differences / (double)(N*(N-1)/2) / (double)sites, 0.0 if N < 2 or sites == 0 */
+} ps_core_diversity_t;
+/* Core counterpart of Population::gene_frequencies (population.rs:840-863; the reference has no such function): counts[4 s + a]
+ * = cells of local site s that equal 1 << a, as integers (a frequency is count / pop_size).  counts: ncols x 4. */
+int ps_site_allele_counts(ps_population *core, uint32_t *counts);
+/* The summary of the same pass without writing the counts (core counterpart of population.rs:840-863; the reference has no such
+ * function).  spectrum: pop_size + 1 bins, or NULL -- spectrum[m] = sites whose minor count N - max_c n_c is m. */
+int ps_core_diversity(ps_population *core, ps_core_diversity_t *out, uint64_t *spectrum);
+/* The same summary from a counts table, on the host alone (no device is touched, as ps_site_tables; the reference has no such
+ * function; core counterpart of population.rs:840-863 for tables read back or assembled elsewhere).  counts: sites x 4; a site
+ * whose counts exceed pop_size fails with PS_ERR_INVALID. */
+int ps_diversity_from_counts(const uint32_t *counts, uint64_t sites, uint64_t pop_size, ps_core_diversity_t *out,
+                             uint64_t *spectrum);
+/* device time of the counts kernel of the last ps_site_allele_counts / ps_core_diversity call on this handle (HIP events
+ * around the launch; no reference counterpart) */
+int ps_core_diversity_timing(ps_population *core, double *kernel_ms);
 /* Population::calc_gene_freq (population.rs:244-268) */
 int ps_calc_gene_freq(ps_population *p, double *out);
 /* Population::write (population.rs:865-897): <outpref>_core_genome.csv / _pangenome.csv */
@@ -466,6 +495,11 @@ int ps_multi_pairwise_distances(ps_multi *m, double *core_out, double *acc_out);
 /* population.rs:753-784 of the run's core matrix (core != 0: every shard counts its sites, shard 0 adds and folds; the tuning
  * keys of shard 0's core handle apply) or of its accessory matrix (core == 0: shard 0's replica).  out: pop_size values. */
 int ps_multi_average_distance(ps_multi *m, int core, double *out);
+/* ps_site_allele_counts / ps_core_diversity of the run's core matrix (core counterparts of population.rs:840-863; the reference
+ * has no such function): the shards' counts concatenated (counts: core_size x 4), their integers and spectra added, the
+ * double formed once over core_size. */
+int ps_multi_site_allele_counts(ps_multi *m, uint32_t *counts);
+int ps_multi_core_diversity(ps_multi *m, ps_core_diversity_t *out, uint64_t *spectrum);
 /* ps_sim_set_site_weights for a ps_multi run is NOT plumbed yet: always PS_ERR_INVALID, with a message that says what to do
  * instead (one ps_sim per shard). */
 int ps_multi_set_site_weights(ps_multi *m, const float *w_core, const float *w_acc_mut, const float *w_acc_rec);

@@ -61,6 +61,14 @@ class StateHeader(C.Structure):
 
 PS_STATE_PACKED2, PS_STATE_RAW8 = 1, 2
 
+
+class CoreDiversity(C.Structure):
+    """ps_core_diversity_t: the summary of ps_core_diversity / ps_diversity_from_counts (docs/CORE_DIVERSITY.md)"""
+    _fields_ = [("pop_size", C.c_uint64), ("sites", C.c_uint64), ("other_cells", C.c_uint64),
+                ("segregating_sites", C.c_uint64), ("pair_differences", C.c_uint64), ("base_cells", C.c_uint64 * 4),
+                ("mean_pairwise_distance", C.c_double)]
+
+
 # every symbol include/pansim_hip.h declares (tests/test_host_logic.py::test_library_exports_every_declared_symbol checks the header against this)
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -99,6 +107,10 @@ SIGNATURES = {
     "ps_last_pair_form": (_int, [_vp]),
     "ps_last_sweep_form": (_int, [_vp]),
     "ps_gene_frequencies": (_int, [_vp, _f64p]),
+    "ps_site_allele_counts": (_int, [_vp, _vp]),
+    "ps_core_diversity": (_int, [_vp, C.POINTER(CoreDiversity), _vp]),
+    "ps_diversity_from_counts": (_int, [_vp, _u64, _u64, C.POINTER(CoreDiversity), _vp]),
+    "ps_core_diversity_timing": (_int, [_vp, C.POINTER(_f64)]),
     "ps_calc_gene_freq": (_int, [_vp, C.POINTER(_f64)]),
     "ps_write": (_int, [_vp, C.c_char_p]),
     "ps_sync": (_int, [_vp]),
@@ -155,6 +167,8 @@ SIGNATURES = {
     "ps_multi_pairwise_counts": (_int, [_vp, _u32p]),
     "ps_multi_pairwise_distances": (_int, [_vp, _f64p, _f64p]),
     "ps_multi_average_distance": (_int, [_vp, _int, _f64p]),
+    "ps_multi_site_allele_counts": (_int, [_vp, _vp]),
+    "ps_multi_core_diversity": (_int, [_vp, C.POINTER(CoreDiversity), _vp]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

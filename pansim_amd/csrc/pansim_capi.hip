@@ -305,6 +305,11 @@ struct ps_population {
     std::vector<uint32_t> row_slot;
     uint32_t *d_row_slot = nullptr;
     bool rows_overridden = false;
+    // core allele counts and diversity (core_diversity.h): scratch kept from the first call on
+    uint32_t *d_site_counts = nullptr;      // ncols x 4 counts of ps_site_allele_counts
+    unsigned long long *d_div = nullptr;    // ps_core_diversity: the summary words, then the pop_size + 1 spectrum bins
+    hipEvent_t div_ev[2] = {};              // around the last launch of the counts kernel (ps_core_diversity_timing)
+    bool div_timed = false;
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
     unsigned long long *h_stamps = nullptr, *d_stamps = nullptr;   // diagnostic phase stamps
 };
@@ -346,6 +351,10 @@ extern "C" void ps_population_destroy(ps_population *p)
         if (p->d_ptab[c]) (void)hipFree(p->d_ptab[c]);
     if (p->d_site_T) (void)hipFree(p->d_site_T);
     if (p->d_gene_tab) (void)hipFree(p->d_gene_tab);
+    if (p->d_site_counts) (void)hipFree(p->d_site_counts);
+    if (p->d_div) (void)hipFree(p->d_div);
+    for (hipEvent_t e : p->div_ev)
+        if (e) (void)hipEventDestroy(e);
     if (p->h_flag) (void)hipHostFree(p->h_flag);
     if (p->h_stamps) {
         if (p->d_stamps) {
@@ -4878,6 +4887,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // state files (ps_sim_save, ps_sim_load, ps_state_info)
 #include "state_file.h"
+
+// core allele counts and diversity (ps_site_allele_counts, ps_core_diversity, ps_diversity_from_counts, ps_multi_*)
+#include "core_diversity.h"
 
 // the native RCCL provider of ps_exchange_fn (ps_rccl_*, ps_exchange_rccl)
 #include "exchange_rccl.h"

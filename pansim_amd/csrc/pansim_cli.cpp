@@ -51,6 +51,7 @@ static const Flag EXT_FLAGS[] = {
     { "gpus", "Number of core-site shards, one per GPU (more shards than GPUs share them). Results do not depend on it.", "1", true },
     { "reference_seed_stream", "Draw the selection coefficients from the reference's own seeded stream (ChaCha12 StdRng, restated from the published algorithms of the rand / statrs crates, ziggurat tables recomputed: UNVERIFIED against a Pansim binary) instead of the build's Philox stream.", nullptr, false },
     { "save_state", "Write the state of the run after its last generation to this file (ps_sim_save), beside the usual outputs. One shard only (--gpus 1).", "", true },
+    { "print_core_freqs", "Write the core genome's per-site base counts to <outpref>_core_freqs.tsv (one line A, C, G, T per site, tab separated) and its diversity summary to <outpref>_core_diversity.tsv (number of segregating sites, exact sum and mean of ALL pairwise core distances, minor-allele spectrum; docs/CORE_DIVERSITY.md), beside _freqs.txt.", nullptr, false },
     { "load_state", "Start from a state file instead of a clonal population: --n_gen stays the TOTAL, generations [saved, n_gen) are run. pop_size, core_size, pan_genes and core_genes must be the file's; every other flag is this command line's (the same flags continue the saved run bit for bit, other flags branch off it). With --print_dist the earlier rows of _per_gen.tsv come from the file, which must have been saved with --print_dist. One shard only (--gpus 1).", "", true },
 };
 
@@ -355,6 +356,29 @@ int main(int argc, char **argv)
             f = fopen((outpref + "_freqs.txt").c_str(), "w");
             if (!f) die(1, "Error: cannot create " + outpref + "_freqs.txt");
             for (double x : freqs) fprintf(f, "%s\n", fmt(x).c_str());
+            fclose(f);
+        }
+        if (present["print_core_freqs"]) {                             // (no counterpart in the reference: docs/CORE_DIVERSITY.md)
+            std::vector<uint32_t> cnt(4 * (size_t)p.core_size + 1);
+            std::vector<uint64_t> spec((size_t)p.pop_size + 1);
+            ps_core_diversity_t dv;
+            CK(multi ? ps_multi_site_allele_counts(multi, cnt.data()) : ps_site_allele_counts(ps_sim_core(sim), cnt.data()));
+            CK(multi ? ps_multi_core_diversity(multi, &dv, spec.data()) : ps_core_diversity(ps_sim_core(sim), &dv, spec.data()));
+            FILE *f = fopen((outpref + "_core_freqs.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_core_freqs.tsv");
+            for (uint64_t s = 0; s < p.core_size; s++) fprintf(f, "%u\t%u\t%u\t%u\n", cnt[4 * s], cnt[4 * s + 1], cnt[4 * s + 2], cnt[4 * s + 3]);
+            fclose(f);
+            f = fopen((outpref + "_core_diversity.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_core_diversity.tsv");
+            const std::pair<const char *, uint64_t> fields[] = {
+                { "pop_size", dv.pop_size }, { "sites", dv.sites }, { "other_cells", dv.other_cells },
+                { "segregating_sites", dv.segregating_sites }, { "pair_differences", dv.pair_differences },
+                { "base_cells_A", dv.base_cells[0] }, { "base_cells_C", dv.base_cells[1] }, { "base_cells_G", dv.base_cells[2] },
+                { "base_cells_T", dv.base_cells[3] } };
+            for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+            fprintf(f, "mean_pairwise_distance\t%s\n", fmt(dv.mean_pairwise_distance).c_str());
+            for (uint64_t m = 0; m < spec.size(); m++)
+                if (spec[m]) fprintf(f, "spectrum\t%llu\t%llu\n", (unsigned long long)m, (unsigned long long)spec[m]);
             fclose(f);
         }
     };

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import Config, check
+from ._lib import Config, CoreDiversity, check
 
 
 def _u32(a):
@@ -116,6 +116,34 @@ def site_tables(core, global_cols, mutations_vec, recombinations_vec, mutation_w
     if not core:
         out["hgt_weights"] = wq
     return out
+
+
+def _diversity_dict(d, spectrum):
+    out = {name: int(getattr(d, name)) for name in ("pop_size", "sites", "other_cells", "segregating_sites", "pair_differences")}
+    out["base_cells"] = [int(x) for x in d.base_cells]
+    out["mean_pairwise_distance"] = float(d.mean_pairwise_distance)
+    if spectrum is not None:
+        out["spectrum"] = spectrum
+    return out
+
+
+def _diversity_call(fn, pop_size, spectrum, *head):
+    """fn(*head, &summary, spectrum or NULL) -> the dict of Population.core_diversity"""
+    d = CoreDiversity()
+    spec = np.zeros(int(pop_size) + 1, np.uint64) if spectrum else None
+    check(fn(*head, C.byref(d), _ptr(spec)))
+    return _diversity_dict(d, spec)
+
+
+def diversity_from_counts(counts, pop_size, spectrum=False):
+    """The summary of `Population.core_diversity` from a (sites, 4) table of A, C, G, T counts, on the host alone
+    (ps_diversity_from_counts; no device).  Cells a site's counts do not cover are its `other` class."""
+    c = np.ascontiguousarray(counts, np.uint32)
+    if c.ndim != 2 or c.shape[1] != 4:
+        raise ValueError("counts must be (sites, 4): A, C, G, T per site")
+    if int(pop_size) < 1:
+        raise ValueError("pop_size must be >= 1")
+    return _diversity_call(_lib.load().ps_diversity_from_counts, pop_size, spectrum, _ptr(c), c.shape[0], int(pop_size))
 
 
 def draw_parents(weights, seed, generation):
@@ -304,6 +332,25 @@ class Population:
         out = np.zeros(self.ncols + self.core_genes, np.float64)
         check(self._lib.ps_gene_frequencies(self._h, out))
         return out
+
+    def site_allele_counts(self):
+        """core counterpart of gene_frequencies (the reference has none): (ncols, 4) uint32, the cells of every site of
+        this handle that are A, C, G, T (bytes 1, 2, 4, 8); docs/CORE_DIVERSITY.md"""
+        out = np.zeros((self.ncols, 4), np.uint32)
+        check(self._lib.ps_site_allele_counts(self._h, _ptr(out)))
+        return out
+
+    def core_diversity(self, spectrum=False):
+        """the diversity summary of this handle's core sites (ps_core_diversity): a dict of the fields of
+        ps_core_diversity_t -- pop_size, sites, other_cells, segregating_sites, pair_differences, base_cells (A, C, G, T),
+        mean_pairwise_distance -- plus, on request, `spectrum`: pop_size + 1 bins of sites by minor count"""
+        return _diversity_call(self._lib.ps_core_diversity, self.size, spectrum, self._h)
+
+    def core_diversity_timing(self):
+        """device ms of the counts kernel of the last site_allele_counts() / core_diversity() call"""
+        ms = C.c_double()
+        check(self._lib.ps_core_diversity_timing(self._h, C.byref(ms)))
+        return ms.value
 
     def calc_gene_freq(self):
         """population.rs:244-268"""

@@ -308,6 +308,18 @@ class MultiSimulation:
         check(self._lib.ps_multi_average_distance(self._h, int(bool(core)), out))
         return out
 
+    def site_allele_counts(self):
+        """(core_size, 4) uint32: the shards' Population.site_allele_counts() concatenated"""
+        from .population import _ptr
+        out = np.zeros((self.params.core_size, 4), np.uint32)
+        check(self._lib.ps_multi_site_allele_counts(self._h, _ptr(out)))
+        return out
+
+    def core_diversity(self, spectrum=False):
+        """Population.core_diversity() of the whole core matrix: the shards' integers and spectra added"""
+        from .population import _diversity_call
+        return _diversity_call(self._lib.ps_multi_core_diversity, self.params.pop_size, spectrum, self._h)
+
     def write(self, outpref):
         check(self._lib.ps_multi_write(self._h, str(outpref).encode()))
 
