@@ -506,6 +506,47 @@ int ps_multi_set_site_weights(ps_multi *m, const float *w_core, const float *w_a
 /* main.rs:550-553: <outpref>_core_genome.csv (lines assembled from the shards' columns) and _pangenome.csv */
 int ps_multi_write(ps_multi *m, const char *outpref);
 
+/* Joint core x accessory distance histogram over ALL N (N - 1) / 2 unordered pairs (docs/DISTANCE_HISTOGRAM.md).  The reference
+ * has no such function: it writes a SAMPLE of pairs as text (population.rs:787-837) and bins the text afterwards
+ * (scripts/plot_distances.R).  Per pair i < j, in integers: core d = h / 2 (h as ps_pairwise_counts returns it),
+ * bin_c = min(core_bins - 1, floor(d core_bins / core_span)), a pair with d >= core_span counted in core_clamped; accessory
+ * a = U - I, b = U + core_genes, bin_a = min(acc_bins - 1, floor(a acc_bins / b)), a pair with b == 0 (the reference's NaN)
+ * in no bin and counted in undefined_pairs.  joint[bin_c * acc_bins + bin_a] (core_bins x acc_bins values); the moments
+ * cover all pairs, undefined ones included.  1 <= core_bins, acc_bins; core_bins x acc_bins <= 16384; pop_size >= 2; at most
+ * 65535 accessory genes: anything else is PS_ERR_INVALID.  Results do not depend on the launch geometry. */
+typedef struct {
+    uint32_t core_bins, acc_bins;
+    uint64_t core_span;                /* S >= 1 in units of d; 0 = automatic: core_d_max + 1 (a first pass without binning) */
+} ps_pair_hist_params;
+typedef struct {
+    uint64_t pop_size, pairs, core_sites, core_genes;      /* pop_size is 0 from ps_histogram_from_counts */
+    uint32_t core_bins, acc_bins;
+    uint64_t core_span;                /* the span used */
+    uint64_t undefined_pairs, core_clamped;
+    uint64_t core_d_min, core_d_max, core_d_sum, core_d_sqsum_lo, core_d_sqsum_hi;      /* sum of d^2 = hi 2^64 + lo */
+    double   mean_core_distance;       /* (double)core_d_sum / (double)pairs / (double)core_sites, 0.0 if core_sites == 0 */
+} ps_pair_hist_t;
+/* All pairs of two handles of equal pop_size on one device (the reference has no such function; replaces population.rs:787-837 +
+ * scripts/plot_distances.R): `core` a core handle that holds all sites, `acc` an accessory handle.  Ordered behind all queued
+ * work of BOTH handles; changes no state.  PS_ERR_NO_DEVICE before anything else when no GPU is visible. */
+int ps_distance_histogram(ps_population *core, ps_population *acc, const ps_pair_hist_params *prm, ps_pair_hist_t *out,
+                          uint64_t *joint);
+/* The same for the two matrices of a simulation (the reference has no such function; population.rs:787-837 +
+ * scripts/plot_distances.R); a site shard fails with a message that points to ps_multi_distance_histogram */
+int ps_sim_distance_histogram(ps_sim *s, const ps_pair_hist_params *prm, ps_pair_hist_t *out, uint64_t *joint);
+/* The same for a sharded run (the reference has no such function; population.rs:787-837 + scripts/plot_distances.R): every
+ * shard counts its own sites band by band, shard 0 adds, halves and bins against its accessory replica */
+int ps_multi_distance_histogram(ps_multi *m, const ps_pair_hist_params *prm, ps_pair_hist_t *out, uint64_t *joint);
+/* The same integer rules on the host alone (no device is touched, as ps_diversity_from_counts; the reference has no such
+ * function; population.rs:787-837 + scripts/plot_distances.R): bins any list of pair numerators, e.g. ps_pairwise_counts'.
+ * n_pairs >= 1; an intersection above its union is PS_ERR_INVALID. */
+int ps_histogram_from_counts(const uint32_t *core_h, const uint32_t *acc_inter, const uint32_t *acc_union, uint64_t n_pairs,
+                             uint64_t core_sites, uint64_t core_genes, const ps_pair_hist_params *prm, ps_pair_hist_t *out,
+                             uint64_t *joint);
+/* device ms of the last ps_distance_histogram on this core handle (HIP events; no reference counterpart): the count kernels
+ * of both matrices, and the binning kernel (with the moments pass of an automatic span) */
+int ps_distance_histogram_timing(ps_population *core, double *counts_ms, double *binning_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,20 @@ class CoreDiversity(C.Structure):
                 ("mean_pairwise_distance", C.c_double)]
 
 
+class PairHistParams(C.Structure):
+    """ps_pair_hist_params: the bins of ps_distance_histogram (docs/DISTANCE_HISTOGRAM.md); core_span 0 = automatic"""
+    _fields_ = [("core_bins", C.c_uint32), ("acc_bins", C.c_uint32), ("core_span", C.c_uint64)]
+
+
+class PairHist(C.Structure):
+    """ps_pair_hist_t: the summary of ps_distance_histogram / ps_histogram_from_counts"""
+    _fields_ = [("pop_size", C.c_uint64), ("pairs", C.c_uint64), ("core_sites", C.c_uint64), ("core_genes", C.c_uint64),
+                ("core_bins", C.c_uint32), ("acc_bins", C.c_uint32), ("core_span", C.c_uint64),
+                ("undefined_pairs", C.c_uint64), ("core_clamped", C.c_uint64), ("core_d_min", C.c_uint64),
+                ("core_d_max", C.c_uint64), ("core_d_sum", C.c_uint64), ("core_d_sqsum_lo", C.c_uint64),
+                ("core_d_sqsum_hi", C.c_uint64), ("mean_core_distance", C.c_double)]
+
+
 # every symbol include/pansim_hip.h declares (tests/test_host_logic.py::test_library_exports_every_declared_symbol checks the header against this)
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -169,6 +183,11 @@ SIGNATURES = {
     "ps_multi_average_distance": (_int, [_vp, _int, _f64p]),
     "ps_multi_site_allele_counts": (_int, [_vp, _vp]),
     "ps_multi_core_diversity": (_int, [_vp, C.POINTER(CoreDiversity), _vp]),
+    "ps_distance_histogram": (_int, [_vp, _vp, C.POINTER(PairHistParams), C.POINTER(PairHist), _vp]),
+    "ps_sim_distance_histogram": (_int, [_vp, C.POINTER(PairHistParams), C.POINTER(PairHist), _vp]),
+    "ps_multi_distance_histogram": (_int, [_vp, C.POINTER(PairHistParams), C.POINTER(PairHist), _vp]),
+    "ps_histogram_from_counts": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, C.POINTER(PairHistParams), C.POINTER(PairHist), _vp]),
+    "ps_distance_histogram_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

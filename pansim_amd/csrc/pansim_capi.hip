@@ -310,6 +310,11 @@ struct ps_population {
     unsigned long long *d_div = nullptr;    // ps_core_diversity: the summary words, then the pop_size + 1 spectrum bins
     hipEvent_t div_ev[2] = {};              // around the last launch of the counts kernel (ps_core_diversity_timing)
     bool div_timed = false;
+    // joint distance histogram (pair_histogram.h), on the core handle: the summary words, then the bins; the last call's times
+    unsigned long long *d_ph = nullptr;
+    uint64_t ph_cap = 0;                    // (words)
+    double ph_counts_ms = 0.0, ph_bin_ms = 0.0;
+    bool ph_timed = false;
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
     unsigned long long *h_stamps = nullptr, *d_stamps = nullptr;   // diagnostic phase stamps
 };
@@ -353,6 +358,7 @@ extern "C" void ps_population_destroy(ps_population *p)
     if (p->d_gene_tab) (void)hipFree(p->d_gene_tab);
     if (p->d_site_counts) (void)hipFree(p->d_site_counts);
     if (p->d_div) (void)hipFree(p->d_div);
+    if (p->d_ph) (void)hipFree(p->d_ph);
     for (hipEvent_t e : p->div_ev)
         if (e) (void)hipEventDestroy(e);
     if (p->h_flag) (void)hipHostFree(p->h_flag);
@@ -4890,6 +4896,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // core allele counts and diversity (ps_site_allele_counts, ps_core_diversity, ps_diversity_from_counts, ps_multi_*)
 #include "core_diversity.h"
+
+// joint core x accessory distance histogram over all pairs (ps_distance_histogram, ps_histogram_from_counts, ps_multi_*)
+#include "pair_histogram.h"
 
 // the native RCCL provider of ps_exchange_fn (ps_rccl_*, ps_exchange_rccl)
 #include "exchange_rccl.h"

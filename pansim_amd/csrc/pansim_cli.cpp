@@ -52,6 +52,9 @@ static const Flag EXT_FLAGS[] = {
     { "reference_seed_stream", "Draw the selection coefficients from the reference's own seeded stream (ChaCha12 StdRng, restated from the published algorithms of the rand / statrs crates, ziggurat tables recomputed: UNVERIFIED against a Pansim binary) instead of the build's Philox stream.", nullptr, false },
     { "save_state", "Write the state of the run after its last generation to this file (ps_sim_save), beside the usual outputs. One shard only (--gpus 1).", "", true },
     { "print_core_freqs", "Write the core genome's per-site base counts to <outpref>_core_freqs.tsv (one line A, C, G, T per site, tab separated) and its diversity summary to <outpref>_core_diversity.tsv (number of segregating sites, exact sum and mean of ALL pairwise core distances, minor-allele spectrum; docs/CORE_DIVERSITY.md), beside _freqs.txt.", nullptr, false },
+    { "print_dist_hist", "Write the joint histogram of (core distance, accessory distance) over ALL pairs of the final population to <outpref>_dist_hist.tsv (core_bin, acc_bin, count per non-empty bin) and its summary to <outpref>_dist_hist_summary.tsv (docs/DISTANCE_HISTOGRAM.md), beside the usual outputs.", nullptr, false },
+    { "dist_hist_bins", "Bins of --print_dist_hist as <core>,<accessory>: both at least 1, their product at most 16384.", "64,64", true },
+    { "dist_hist_core_max", "Upper end of the core axis of --print_dist_hist as a distance (pairs at or above it land in the last bin and are counted as clamped). Must be > 0.0. Without it the axis ends just above the largest core distance found.", "", true },
     { "load_state", "Start from a state file instead of a clonal population: --n_gen stays the TOTAL, generations [saved, n_gen) are run. pop_size, core_size, pan_genes and core_genes must be the file's; every other flag is this command line's (the same flags continue the saved run bit for bit, other flags branch off it). With --print_dist the earlier rows of _per_gen.tsv come from the file, which must have been saved with --print_dist. One shard only (--gpus 1).", "", true },
 };
 
@@ -297,6 +300,26 @@ int main(int argc, char **argv)
     if (n_shards > 1 && !(save_state.empty() && load_state.empty()))
         die(101, "pansim: --save_state / --load_state need --gpus 1: a sharded run is saved shard by shard through the library "
                  "(ps_multi_shard + ps_sim_save) and loaded as one ps_sim per shard");
+    // --print_dist_hist: its two optional flags are checked whether or not it is given
+    ps_pair_hist_params hist_prm = { 64, 64, 0 };
+    {
+        const std::string &b = val["dist_hist_bins"];
+        unsigned long long bc = 0, ba = 0;
+        int used = 0;
+        if (sscanf(b.c_str(), "%llu,%llu%n", &bc, &ba, &used) != 2 || (size_t)used != b.size() || b.find_first_of("+- ") != std::string::npos)
+            die(101, "pansim: --dist_hist_bins must be <core>,<accessory> (two whole numbers), not \"" + b + "\"");
+        if (bc < 1 || ba < 1) die(101, "pansim: --dist_hist_bins must be at least 1 on both axes");
+        if (bc > 16384 || ba > 16384 || bc * ba > 16384)
+            die(101, "pansim: --dist_hist_bins " + b + ": the product of the two must be at most 16384");
+        hist_prm.core_bins = (uint32_t)bc;
+        hist_prm.acc_bins = (uint32_t)ba;
+        if (!val["dist_hist_core_max"].empty()) {
+            const double cm = as_f64(val, "dist_hist_core_max");
+            if (!(cm > 0.0) || !std::isfinite(cm)) die(101, "pansim: --dist_hist_core_max must be > 0.0");
+            const double span = std::ceil(cm * (double)p.core_size);      // core_span = max(1, ceil(core_max * L))
+            hist_prm.core_span = span >= 18446744073709551615.0 ? UINT64_MAX : std::max<uint64_t>(1, (uint64_t)span);
+        }
+    }
     const uint64_t G = d.pan_size, P = p.max_distances;
     std::vector<double> avg_core(p.n_gen), avg_acc(p.n_gen), std_core(p.n_gen), std_acc(p.n_gen);
     // a fresh run goes through ps_multi (one shard: the plain run); a LOADED run is a plain ps_sim, driven by the ps_sim_*
@@ -379,6 +402,33 @@ int main(int argc, char **argv)
             fprintf(f, "mean_pairwise_distance\t%s\n", fmt(dv.mean_pairwise_distance).c_str());
             for (uint64_t m = 0; m < spec.size(); m++)
                 if (spec[m]) fprintf(f, "spectrum\t%llu\t%llu\n", (unsigned long long)m, (unsigned long long)spec[m]);
+            fclose(f);
+        }
+        if (present["print_dist_hist"]) {                              // (no counterpart in the reference: docs/DISTANCE_HISTOGRAM.md)
+            std::vector<uint64_t> joint((size_t)hist_prm.core_bins * hist_prm.acc_bins);
+            ps_pair_hist_t h;
+            CK(multi ? ps_multi_distance_histogram(multi, &hist_prm, &h, joint.data()) : ps_sim_distance_histogram(sim, &hist_prm, &h, joint.data()));
+            FILE *f = fopen((outpref + "_dist_hist.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_dist_hist.tsv");
+            for (uint32_t bc = 0; bc < h.core_bins; bc++)
+                for (uint32_t ba = 0; ba < h.acc_bins; ba++)
+                    if (joint[(size_t)bc * h.acc_bins + ba])
+                        fprintf(f, "%u\t%u\t%llu\n", bc, ba, (unsigned long long)joint[(size_t)bc * h.acc_bins + ba]);
+            fclose(f);
+            f = fopen((outpref + "_dist_hist_summary.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_dist_hist_summary.tsv");
+            const std::pair<const char *, uint64_t> fields[] = {
+                { "pop_size", h.pop_size }, { "pairs", h.pairs }, { "core_sites", h.core_sites }, { "core_genes", h.core_genes },
+                { "core_bins", h.core_bins }, { "acc_bins", h.acc_bins }, { "core_span", h.core_span },
+                { "undefined_pairs", h.undefined_pairs }, { "core_clamped", h.core_clamped }, { "core_d_min", h.core_d_min },
+                { "core_d_max", h.core_d_max }, { "core_d_sum", h.core_d_sum } };
+            for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+            // the 128-bit square sum as one decimal number
+            unsigned __int128 sq = ((unsigned __int128)h.core_d_sqsum_hi << 64) | h.core_d_sqsum_lo;
+            std::string dec;
+            do { dec.insert(dec.begin(), (char)('0' + (int)(sq % 10))); sq /= 10; } while (sq);
+            fprintf(f, "core_d_sqsum\t%s\n", dec.c_str());
+            fprintf(f, "mean_core_distance\t%s\n", fmt(h.mean_core_distance).c_str());
             fclose(f);
         }
     };

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import Config, CoreDiversity, check
+from ._lib import Config, CoreDiversity, PairHist, PairHistParams, check
 
 
 def _u32(a):
@@ -144,6 +144,65 @@ def diversity_from_counts(counts, pop_size, spectrum=False):
     if int(pop_size) < 1:
         raise ValueError("pop_size must be >= 1")
     return _diversity_call(_lib.load().ps_diversity_from_counts, pop_size, spectrum, _ptr(c), c.shape[0], int(pop_size))
+
+
+class DistanceHistogram:
+    """The result of `distance_histogram` (ps_pair_hist_t + the bins; docs/DISTANCE_HISTOGRAM.md): the summary fields as
+    integer attributes (`core_d_sqsum` one Python integer), `mean_core_distance`, `joint` -- (core_bins, acc_bins) uint64 --
+    and the two marginals `core_marginal` / `acc_marginal` (its row and column sums)."""
+    FIELDS = ("pop_size", "pairs", "core_sites", "core_genes", "core_bins", "acc_bins", "core_span", "undefined_pairs",
+              "core_clamped", "core_d_min", "core_d_max", "core_d_sum")
+
+    def __init__(self, h, joint):
+        for name in self.FIELDS:
+            setattr(self, name, int(getattr(h, name)))
+        self.core_d_sqsum = (int(h.core_d_sqsum_hi) << 64) | int(h.core_d_sqsum_lo)
+        self.mean_core_distance = float(h.mean_core_distance)
+        self.joint = joint.reshape(self.core_bins, self.acc_bins)
+        self.core_marginal = self.joint.sum(axis=1, dtype=np.uint64)
+        self.acc_marginal = self.joint.sum(axis=0, dtype=np.uint64)
+
+    def core_bin_edges(self):
+        """core_bins + 1 integers: bin k of the core axis holds the pairs with d in [edges[k], edges[k + 1]) -- edges[k] =
+        ceil(k core_span / core_bins) -- and the last bin those with d >= core_span as well (`core_clamped` of them)"""
+        return [-((-k * self.core_span) // self.core_bins) for k in range(self.core_bins + 1)]
+
+    def as_dict(self):
+        out = {name: getattr(self, name) for name in self.FIELDS + ("core_d_sqsum", "mean_core_distance")}
+        out.update(joint=self.joint, core_marginal=self.core_marginal, acc_marginal=self.acc_marginal)
+        return out
+
+
+def _hist_params(core_bins, acc_bins, core_max, core_sites, core_span=None):
+    """core_max is a distance: core_span = max(1, ceil(core_max L)); None = automatic (span 0).  core_span, in units of
+    d, overrides it."""
+    prm = PairHistParams(int(core_bins), int(acc_bins), 0)
+    if core_span is not None:
+        prm.core_span = int(core_span)
+    elif core_max is not None:
+        if not float(core_max) > 0.0:
+            raise ValueError("core_max must be > 0.0")
+        prm.core_span = max(1, int(np.ceil(float(core_max) * int(core_sites))))
+    return prm
+
+
+def _hist_call(fn, prm, *head):
+    """fn(*head, &params, &summary, joint) -> DistanceHistogram"""
+    h = PairHist()
+    joint = np.zeros(max(1, prm.core_bins * prm.acc_bins), np.uint64)      # (the library rejects bad bin counts itself)
+    check(fn(*head, C.byref(prm), C.byref(h), _ptr(joint)))
+    return DistanceHistogram(h, joint)
+
+
+def histogram_from_counts(core_h, acc_inter, acc_union, core_sites, core_genes, core_bins=64, acc_bins=64, core_max=None,
+                          core_span=None):
+    """`Population.distance_histogram` from lists of pair numerators (`pairwise_counts` of both matrices), on the host
+    alone (ps_histogram_from_counts; no device)."""
+    h, i, u = _u32(core_h).reshape(-1), _u32(acc_inter).reshape(-1), _u32(acc_union).reshape(-1)
+    if not h.size == i.size == u.size:
+        raise ValueError("one core numerator, one intersection and one union per pair")
+    prm = _hist_params(core_bins, acc_bins, core_max, core_sites, core_span)
+    return _hist_call(_lib.load().ps_histogram_from_counts, prm, _ptr(h), _ptr(i), _ptr(u), h.size, int(core_sites), int(core_genes))
 
 
 def draw_parents(weights, seed, generation):
@@ -345,6 +404,19 @@ class Population:
         ps_core_diversity_t -- pop_size, sites, other_cells, segregating_sites, pair_differences, base_cells (A, C, G, T),
         mean_pairwise_distance -- plus, on request, `spectrum`: pop_size + 1 bins of sites by minor count"""
         return _diversity_call(self._lib.ps_core_diversity, self.size, spectrum, self._h)
+
+    def distance_histogram(self, acc, core_bins=64, acc_bins=64, core_max=None, core_span=None):
+        """the joint histogram of (core distance, accessory Jaccard distance) over ALL pairs of this core population and
+        the accessory population `acc` of the same individuals (ps_distance_histogram; docs/DISTANCE_HISTOGRAM.md) -> a
+        DistanceHistogram.  `core_max`: the upper end of the core axis as a distance (None: just above the largest)."""
+        prm = _hist_params(core_bins, acc_bins, core_max, self.global_cols, core_span)
+        return _hist_call(self._lib.ps_distance_histogram, prm, self._h, acc._h)
+
+    def distance_histogram_timing(self):
+        """device ms of (the count kernels, the binning kernel) of the last distance_histogram() on this core handle"""
+        a, b = C.c_double(), C.c_double()
+        check(self._lib.ps_distance_histogram_timing(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def core_diversity_timing(self):
         """device ms of the counts kernel of the last site_allele_counts() / core_diversity() call"""

@@ -233,6 +233,13 @@ class Simulation:
         check(self._lib.ps_sim_distance_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def distance_histogram(self, core_bins=64, acc_bins=64, core_max=None, core_span=None):
+        """Population.distance_histogram() of the run's two matrices (ps_sim_distance_histogram): behind every queued
+        generation, and without a change of state -- the run continues as if it had not been asked"""
+        from .population import _hist_call, _hist_params
+        prm = _hist_params(core_bins, acc_bins, core_max, self.params.core_size, core_span)
+        return _hist_call(self._lib.ps_sim_distance_histogram, prm, self._h)
+
     def write_outputs(self, outpref):
         core, acc = self.final_distances()
         with open(outpref + ".tsv", "w") as f:                       # main.rs:474-482
@@ -319,6 +326,13 @@ class MultiSimulation:
         """Population.core_diversity() of the whole core matrix: the shards' integers and spectra added"""
         from .population import _diversity_call
         return _diversity_call(self._lib.ps_multi_core_diversity, self.params.pop_size, spectrum, self._h)
+
+    def distance_histogram(self, core_bins=64, acc_bins=64, core_max=None, core_span=None):
+        """Population.distance_histogram() over ALL core sites: the shards' band counts added on shard 0, then halved and
+        binned against its accessory replica (ps_multi_distance_histogram)"""
+        from .population import _hist_call, _hist_params
+        prm = _hist_params(core_bins, acc_bins, core_max, self.params.core_size, core_span)
+        return _hist_call(self._lib.ps_multi_distance_histogram, prm, self._h)
 
     def write(self, outpref):
         check(self._lib.ps_multi_write(self._h, str(outpref).encode()))
