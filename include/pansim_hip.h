@@ -547,6 +547,48 @@ int ps_histogram_from_counts(const uint32_t *core_h, const uint32_t *acc_inter, 
  * of both matrices, and the binning kernel (with the moments pass of an automatic span) */
 int ps_distance_histogram_timing(ps_population *core, double *counts_ms, double *binning_ms);
 
+/* Strain clusters: the connected components of the graph over ALL N individuals whose edges are the pairs closer than a
+ * threshold (docs/STRAIN_CLUSTERS.md).  The reference has no such function: it writes a SAMPLE of pairs as text
+ * (population.rs:787-837) and the clusters are read off the plotted cloud (scripts/plot_distances.R).  Per pair i < j, in
+ * integers, with the numerators of the distance histogram: core criterion d = h / 2 <= core_max_d; accessory criterion
+ * a = U - I, b = U + core_genes, b != 0 and a acc_den <= acc_num b (a pair with b == 0, the reference's NaN, is never an edge
+ * and is counted in undefined_pairs).  Equality is an edge.  A pair is an edge iff every active criterion holds; at least one
+ * must be active and acc_num <= acc_den <= 2^24, else PS_ERR_INVALID.  labels[k] (pop_size values, the reference's row order) =
+ * the smallest row of k's cluster.  Results do not depend on the launch geometry. */
+typedef struct {
+    uint64_t core_max_d;               /* in units of d; UINT64_MAX = no core criterion */
+    uint32_t acc_num, acc_den;         /* distance a / b <= acc_num / acc_den; acc_den == 0 = no accessory criterion */
+} ps_cluster_params;
+typedef struct {
+    uint64_t pop_size, pairs, core_sites, core_genes;      /* pairs: all N (N - 1) / 2, or the list's length from ps_clusters_from_counts */
+    uint64_t edges, clusters, singletons, largest_cluster;
+    uint64_t within_pairs;             /* sum over the clusters of size (size - 1) / 2 */
+    uint64_t undefined_pairs;          /* pairs with b == 0; counted only while the accessory criterion is active */
+    uint64_t rounds;                   /* label rounds taken on the device (informational; 0 from ps_clusters_from_counts) */
+} ps_cluster_t;
+/* All pairs of two handles of equal pop_size >= 2 on one device (the reference has no such function; replaces
+ * population.rs:787-837 + scripts/plot_distances.R): `core` a core handle that holds all sites, `acc` an accessory handle of at
+ * most 65535 genes (required; without an accessory criterion none of its kernels is launched).  Ordered behind all queued work
+ * of BOTH handles; changes no state.  PS_ERR_NO_DEVICE before anything else when no GPU is visible. */
+int ps_strain_clusters(ps_population *core, ps_population *acc, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels);
+/* The same for the two matrices of a simulation (the reference has no such function; population.rs:787-837 +
+ * scripts/plot_distances.R); a site shard fails with a message that points to ps_multi_strain_clusters */
+int ps_sim_strain_clusters(ps_sim *s, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels);
+/* The same for a sharded run (the reference has no such function; population.rs:787-837 + scripts/plot_distances.R): every
+ * shard counts its own sites band by band, shard 0 adds them and computes edges and labels against its accessory replica */
+int ps_multi_strain_clusters(ps_multi *m, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels);
+/* The same integer rule on the host alone (no device is touched, as ps_histogram_from_counts; the reference has no such
+ * function; population.rs:787-837 + scripts/plot_distances.R): union-find over any list of pairs (r1[k], r2[k]) with their
+ * numerators (those of an inactive criterion may be NULL), labels in the list's own index space.  An intersection above its
+ * union, an index >= pop_size or r1[k] == r2[k] is PS_ERR_INVALID. */
+int ps_clusters_from_counts(const uint32_t *r1, const uint32_t *r2, const uint32_t *core_h, const uint32_t *acc_inter,
+                            const uint32_t *acc_union, uint64_t n_pairs, uint64_t pop_size, uint64_t core_sites, uint64_t core_genes,
+                            const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels);
+/* device ms of the last ps_strain_clusters on this core handle (HIP events; the reference has no such function;
+ * population.rs:787-837 + scripts/plot_distances.R): the count kernels of both matrices, the edge kernel, the label rounds
+ * (host round trips included).  PS_ERR_STATE before any call. */
+int ps_strain_clusters_timing(ps_population *core, double *counts_ms, double *edges_ms, double *labels_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,18 @@ class PairHist(C.Structure):
                 ("core_d_sqsum_hi", C.c_uint64), ("mean_core_distance", C.c_double)]
 
 
+class ClusterParams(C.Structure):
+    """ps_cluster_params: the thresholds of ps_strain_clusters (docs/STRAIN_CLUSTERS.md); core_max_d 2^64 - 1 = no core
+    criterion, acc_den 0 = no accessory criterion"""
+    _fields_ = [("core_max_d", C.c_uint64), ("acc_num", C.c_uint32), ("acc_den", C.c_uint32)]
+
+
+class Clusters(C.Structure):
+    """ps_cluster_t: the summary of ps_strain_clusters / ps_clusters_from_counts"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "pairs", "core_sites", "core_genes", "edges", "clusters", "singletons",
+                                                 "largest_cluster", "within_pairs", "undefined_pairs", "rounds")]
+
+
 # every symbol include/pansim_hip.h declares (tests/test_host_logic.py::test_library_exports_every_declared_symbol checks the header against this)
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -188,6 +200,11 @@ SIGNATURES = {
     "ps_multi_distance_histogram": (_int, [_vp, C.POINTER(PairHistParams), C.POINTER(PairHist), _vp]),
     "ps_histogram_from_counts": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, C.POINTER(PairHistParams), C.POINTER(PairHist), _vp]),
     "ps_distance_histogram_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_strain_clusters": (_int, [_vp, _vp, C.POINTER(ClusterParams), C.POINTER(Clusters), _vp]),
+    "ps_sim_strain_clusters": (_int, [_vp, C.POINTER(ClusterParams), C.POINTER(Clusters), _vp]),
+    "ps_multi_strain_clusters": (_int, [_vp, C.POINTER(ClusterParams), C.POINTER(Clusters), _vp]),
+    "ps_clusters_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(ClusterParams), C.POINTER(Clusters), _vp]),
+    "ps_strain_clusters_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

@@ -102,7 +102,7 @@ extern "C" int ps_histogram_from_counts(const uint32_t *core_h, const uint32_t *
     return PS_OK;
 }
 
-static int pair_hist_handles(const ps_population *core, const ps_population *acc, const char *call)
+static int pair_hist_handles(const ps_population *core, const ps_population *acc, const char *call, const char *what = "a distance histogram needs")
 {
     if (!core->cfg.core || acc->cfg.core)
         return ps_fail(PS_ERR_INVALID, "%s takes a core handle first and an accessory handle second", call);
@@ -110,8 +110,8 @@ static int pair_hist_handles(const ps_population *core, const ps_population *acc
         return ps_fail(PS_ERR_INVALID, "%s: the core handle holds %llu individuals, the accessory handle %llu", call,
                        (unsigned long long)core->cfg.pop_size, (unsigned long long)acc->cfg.pop_size);
     if (core->device != acc->device) return ps_fail(PS_ERR_INVALID, "%s: the two handles live on different devices", call);
-    if (core->cfg.pop_size < 2) return ps_fail(PS_ERR_INVALID, "a distance histogram needs pop_size >= 2");
-    if (acc->d.G > 65535) return ps_fail(PS_ERR_INVALID, "a distance histogram needs at most 65535 accessory genes (u16 intersection counts)");
+    if (core->cfg.pop_size < 2) return ps_fail(PS_ERR_INVALID, "%s pop_size >= 2", what);
+    if (acc->d.G > 65535) return ps_fail(PS_ERR_INVALID, "%s at most 65535 accessory genes (u16 intersection counts)", what);
     return PS_OK;
 }
 
@@ -373,6 +373,38 @@ extern "C" int ps_distance_histogram_timing(ps_population *core, double *counts_
     return PS_OK;
 }
 
+// One band of a sharded run: every shard counts its own sites, shard 0's device adds the shards' counts into its own (where
+// they are with peer access, through the landing buffer d_land without).  Ordered on shard 0's core stream.
+static int multi_band_counts(ps_multi *m, const std::vector<core_davg_src> &src, const core_davg_bands &b, uint32_t *d_land, uint32_t lo,
+                             uint32_t nrows)
+{
+    const size_t K = m->shard.size();
+    ps_population *c0 = m->shard[0]->core;
+    const uint64_t n = (uint64_t)nrows * b.ld;
+    // (the last kernel that reads shard 0's counts has finished before any shard overwrites its own)
+    PSCHK(use_device(c0));
+    HIPCHK(hipStreamSynchronize(c0->stream));
+    PSCHK(multi_for_each(m, [&](size_t k) {
+        ps_population *c = m->shard[k]->core;
+        PSCHK(use_device(c));
+        PSCHK(core_davg_band_counts(c, src[k], b, lo, nrows, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return (int)PS_OK;
+    }));
+    PSCHK(use_device(c0));
+    for (size_t k = 1; k < K; k++) {
+        ps_population *c = m->shard[k]->core;
+        if (m->peers_ok) {
+            u32_add_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, c0->stream>>>(c0->d_cdavg, c->d_cdavg, n);
+        } else {
+            HIPCHK(hipMemcpyPeerAsync(d_land, c0->device, c->d_cdavg, c->device, n * sizeof(uint32_t), c0->stream));
+            u32_add_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, c0->stream>>>(c0->d_cdavg, d_land, n);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    return PS_OK;
+}
+
 // As ps_multi_average_distance: band by band every shard counts its own sites, shard 0's device adds the shards' counts
 // (where they are with peer access, through a landing buffer without), and the binning -- with the halving h / 2 behind
 // the sum over the shards -- runs on shard 0 against its accessory replica.
@@ -399,31 +431,7 @@ extern "C" int ps_multi_distance_histogram(ps_multi *m, const ps_pair_hist_param
     PSCHK(use_device(c0));
     uint32_t *d_land = nullptr;         // (without peer access: a peer's band counts copied over first)
     if (!m->peers_ok) HIPCHK(hipMalloc(&d_land, (uint64_t)b.band * b.ld * sizeof(uint32_t)));
-    auto band_counts = [&](uint32_t lo, uint32_t nrows) -> int {
-        const uint64_t n = (uint64_t)nrows * b.ld;
-        // (the last binning has read shard 0's counts before any shard overwrites its own)
-        PSCHK(use_device(c0));
-        HIPCHK(hipStreamSynchronize(c0->stream));
-        PSCHK(multi_for_each(m, [&](size_t k) {
-            ps_population *c = m->shard[k]->core;
-            PSCHK(use_device(c));
-            PSCHK(core_davg_band_counts(c, src[k], b, lo, nrows, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            return (int)PS_OK;
-        }));
-        PSCHK(use_device(c0));
-        for (size_t k = 1; k < K; k++) {
-            ps_population *c = m->shard[k]->core;
-            if (m->peers_ok) {
-                u32_add_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, c0->stream>>>(c0->d_cdavg, c->d_cdavg, n);
-            } else {
-                HIPCHK(hipMemcpyPeerAsync(d_land, c0->device, c->d_cdavg, c->device, n * sizeof(uint32_t), c0->stream));
-                u32_add_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, c0->stream>>>(c0->d_cdavg, d_land, n);
-            }
-            HIPCHK(hipGetLastError());
-        }
-        return PS_OK;
-    };
+    auto band_counts = [&](uint32_t lo, uint32_t nrows) { return multi_band_counts(m, src, b, d_land, lo, nrows); };
     const int rc = pair_hist_device(c0, acc, b, m->prm.core_size, prm, band_counts, out, joint);
     (void)hipSetDevice(c0->device);
     (void)hipStreamSynchronize(c0->stream);

@@ -315,6 +315,11 @@ struct ps_population {
     uint64_t ph_cap = 0;                    // (words)
     double ph_counts_ms = 0.0, ph_bin_ms = 0.0;
     bool ph_timed = false;
+    // strain clusters (strain_clusters.h), on the core handle: count words, `changed`, labels, adjacency bit matrix; the last call's times
+    void *d_cl = nullptr;
+    uint64_t cl_cap = 0;                    // (bytes)
+    double cl_ms[3] = {};                   // counts, edges, labels
+    bool cl_timed = false;
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
     unsigned long long *h_stamps = nullptr, *d_stamps = nullptr;   // diagnostic phase stamps
 };
@@ -349,7 +354,7 @@ extern "C" void ps_population_destroy(ps_population *p)
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     void *ptrs[] = { p->d_row_slot, p->state, p->state2, p->d_delta, p->hgt_ovf_img, p->G[0], p->G[1], p->I[0], p->I[1], p->I_snap, p->d_ptab[0], p->d_ptab[1], p->hgt_scratch, p->cnt, p->d_idx, p->d_idxT, p->d_work,
-                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg };
+                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg, p->d_cl };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (int c = 2; c < PS_MAX_COMP; c++)
@@ -4899,6 +4904,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // joint core x accessory distance histogram over all pairs (ps_distance_histogram, ps_histogram_from_counts, ps_multi_*)
 #include "pair_histogram.h"
+
+// single-linkage strain clusters of all pairs (ps_strain_clusters, ps_clusters_from_counts, ps_multi_*)
+#include "strain_clusters.h"
 
 // the native RCCL provider of ps_exchange_fn (ps_rccl_*, ps_exchange_rccl)
 #include "exchange_rccl.h"

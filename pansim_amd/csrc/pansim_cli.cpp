@@ -55,6 +55,9 @@ static const Flag EXT_FLAGS[] = {
     { "print_dist_hist", "Write the joint histogram of (core distance, accessory distance) over ALL pairs of the final population to <outpref>_dist_hist.tsv (core_bin, acc_bin, count per non-empty bin) and its summary to <outpref>_dist_hist_summary.tsv (docs/DISTANCE_HISTOGRAM.md), beside the usual outputs.", nullptr, false },
     { "dist_hist_bins", "Bins of --print_dist_hist as <core>,<accessory>: both at least 1, their product at most 16384.", "64,64", true },
     { "dist_hist_core_max", "Upper end of the core axis of --print_dist_hist as a distance (pairs at or above it land in the last bin and are counted as clamped). Must be > 0.0. Without it the axis ends just above the largest core distance found.", "", true },
+    { "print_clusters", "Write the strain clusters of the final population -- the connected components over ALL pairs of the graph that joins two individuals when their core distance is at most --cluster_core_max and their accessory distance at most --cluster_acc_max -- to <outpref>_clusters.tsv (row, label per individual: the label is the smallest row of its cluster) and their summary to <outpref>_clusters_summary.tsv (docs/STRAIN_CLUSTERS.md), beside the usual outputs. Needs at least one of the two thresholds.", nullptr, false },
+    { "cluster_core_max", "Largest core distance of a pair that --print_clusters joins. Must be >= 0.0. Without it the core distance is not looked at.", "", true },
+    { "cluster_acc_max", "Largest accessory distance of a pair that --print_clusters joins. Must be 0.0 <= X <= 1.0. Without it the accessory distance is not looked at.", "", true },
     { "load_state", "Start from a state file instead of a clonal population: --n_gen stays the TOTAL, generations [saved, n_gen) are run. pop_size, core_size, pan_genes and core_genes must be the file's; every other flag is this command line's (the same flags continue the saved run bit for bit, other flags branch off it). With --print_dist the earlier rows of _per_gen.tsv come from the file, which must have been saved with --print_dist. One shard only (--gpus 1).", "", true },
 };
 
@@ -320,6 +323,22 @@ int main(int argc, char **argv)
             hist_prm.core_span = span >= 18446744073709551615.0 ? UINT64_MAX : std::max<uint64_t>(1, (uint64_t)span);
         }
     }
+    // --print_clusters: its thresholds are checked whether or not it is given; the integers of docs/STRAIN_CLUSTERS.md
+    ps_cluster_params cluster_prm = { UINT64_MAX, 0, 0 };
+    if (!val["cluster_core_max"].empty()) {
+        const double cm = as_f64(val, "cluster_core_max");
+        if (!(cm >= 0.0) || !std::isfinite(cm)) die(101, "pansim: --cluster_core_max must be >= 0.0");
+        const double dmax = std::floor(cm * (double)p.core_size);      // core_max_d = floor(core_max * L)
+        cluster_prm.core_max_d = dmax >= 18446744073709551615.0 ? UINT64_MAX - 1 : (uint64_t)dmax;
+    }
+    if (!val["cluster_acc_max"].empty()) {
+        const double am = as_f64(val, "cluster_acc_max");
+        if (!(am >= 0.0 && am <= 1.0)) die(101, "pansim: --cluster_acc_max must be 0.0 <= X <= 1.0");
+        cluster_prm.acc_den = 1u << 20;                                 // acc_num / acc_den = floor(acc_max * 2^20) / 2^20
+        cluster_prm.acc_num = (uint32_t)std::floor(am * (double)cluster_prm.acc_den);
+    }
+    if (present["print_clusters"] && cluster_prm.core_max_d == UINT64_MAX && cluster_prm.acc_den == 0)
+        die(101, "pansim: --print_clusters needs --cluster_core_max, --cluster_acc_max or both");
     const uint64_t G = d.pan_size, P = p.max_distances;
     std::vector<double> avg_core(p.n_gen), avg_acc(p.n_gen), std_core(p.n_gen), std_acc(p.n_gen);
     // a fresh run goes through ps_multi (one shard: the plain run); a LOADED run is a plain ps_sim, driven by the ps_sim_*
@@ -429,6 +448,24 @@ int main(int argc, char **argv)
             do { dec.insert(dec.begin(), (char)('0' + (int)(sq % 10))); sq /= 10; } while (sq);
             fprintf(f, "core_d_sqsum\t%s\n", dec.c_str());
             fprintf(f, "mean_core_distance\t%s\n", fmt(h.mean_core_distance).c_str());
+            fclose(f);
+        }
+        if (present["print_clusters"]) {                               // (no counterpart in the reference: docs/STRAIN_CLUSTERS.md)
+            std::vector<uint32_t> labels((size_t)p.pop_size);
+            ps_cluster_t c;
+            CK(multi ? ps_multi_strain_clusters(multi, &cluster_prm, &c, labels.data()) : ps_sim_strain_clusters(sim, &cluster_prm, &c, labels.data()));
+            FILE *f = fopen((outpref + "_clusters.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_clusters.tsv");
+            for (uint64_t k = 0; k < p.pop_size; k++) fprintf(f, "%llu\t%u\n", (unsigned long long)k, labels[k]);
+            fclose(f);
+            f = fopen((outpref + "_clusters_summary.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_clusters_summary.tsv");
+            const std::pair<const char *, uint64_t> fields[] = {
+                { "pop_size", c.pop_size }, { "pairs", c.pairs }, { "core_sites", c.core_sites }, { "core_genes", c.core_genes },
+                { "edges", c.edges }, { "clusters", c.clusters }, { "singletons", c.singletons }, { "largest_cluster", c.largest_cluster },
+                { "within_pairs", c.within_pairs }, { "undefined_pairs", c.undefined_pairs }, { "core_max_d", cluster_prm.core_max_d },
+                { "acc_num", cluster_prm.acc_num }, { "acc_den", cluster_prm.acc_den } };
+            for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
             fclose(f);
         }
     };

@@ -1,0 +1,325 @@
+// strain_clusters.h -- ps_strain_clusters / ps_sim_strain_clusters / ps_multi_strain_clusters and the host restatement
+// ps_clusters_from_counts (include/pansim_hip.h; the definitions: docs/STRAIN_CLUSTERS.md).  Included by pansim_capi.hip
+// behind pair_histogram.h, whose band plan, count phases and stream ordering it reuses as they are.
+//
+// As the histogram, everything on the device runs in INTERNAL row order: per band the core numerators on the core stream,
+// the accessory intersections on the accessory stream, pair_edge_kernel on the core stream behind both; after the last band
+// the label rounds (cluster_hook_kernel, cluster_jump_kernel) until a hook round moves no label.  Only the labels are mapped
+// to the reference's row order, on the host (cluster_finish).
+#pragma once
+
+#include "cluster_kernels.h"
+
+static int cluster_check_params(const ps_cluster_params *prm, bool *core_on, bool *acc_on)
+{
+    *core_on = prm->core_max_d != UINT64_MAX;
+    *acc_on = prm->acc_den != 0;
+    if (!*core_on && !*acc_on)
+        return ps_fail(PS_ERR_INVALID, "strain clusters need at least one criterion: core_max_d below UINT64_MAX or acc_den above 0");
+    if (*acc_on && (prm->acc_num > prm->acc_den || prm->acc_den > (1u << 24)))
+        return ps_fail(PS_ERR_INVALID, "the accessory criterion needs acc_num <= acc_den <= 2^24, not %u / %u", prm->acc_num, prm->acc_den);
+    return PS_OK;
+}
+
+static ps_cl_args cluster_args(const ps_cluster_params *prm, uint64_t cg)
+{
+    ps_cl_args a;
+    a.d_max = (uint32_t)std::min<uint64_t>(prm->core_max_d, 0xffffffffull);
+    a.num = prm->acc_num;
+    a.den = prm->acc_den;
+    a.cg = cg;
+    return a;
+}
+
+// rep[k]: any value below N that is equal exactly for the members of one cluster -> labels[k] = the smallest k of the
+// cluster, and the summary fields that follow from the labels
+static void cluster_finish(const uint32_t *rep, uint64_t N, uint32_t *labels, ps_cluster_t *o)
+{
+    std::vector<uint32_t> first(N, UINT32_MAX), size(N, 0);
+    for (uint64_t k = 0; k < N; k++) {
+        if (first[rep[k]] == UINT32_MAX) first[rep[k]] = (uint32_t)k;
+        labels[k] = first[rep[k]];
+        size[labels[k]]++;
+    }
+    for (uint64_t k = 0; k < N; k++) {
+        const uint64_t s = size[k];
+        if (!s) continue;
+        o->clusters++;
+        o->singletons += s == 1 ? 1 : 0;
+        o->largest_cluster = std::max(o->largest_cluster, s);
+        o->within_pairs += s * (s - 1) / 2;
+    }
+}
+
+extern "C" int ps_clusters_from_counts(const uint32_t *r1, const uint32_t *r2, const uint32_t *core_h, const uint32_t *acc_inter,
+                                       const uint32_t *acc_union, uint64_t n_pairs, uint64_t pop_size, uint64_t core_sites,
+                                       uint64_t core_genes, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels)
+{
+    if (!prm || !out || !labels || (n_pairs && (!r1 || !r2))) return ps_fail(PS_ERR_INVALID, "null argument");
+    bool core_on, acc_on;
+    PSCHK(cluster_check_params(prm, &core_on, &acc_on));
+    if (n_pairs && ((core_on && !core_h) || (acc_on && (!acc_inter || !acc_union))))
+        return ps_fail(PS_ERR_INVALID, "null argument: an active criterion needs its numerators");
+    if (pop_size < 2 || pop_size > 0xffffffffull) return ps_fail(PS_ERR_INVALID, "strain clusters need 2 <= pop_size < 2^32");
+    for (uint64_t k = 0; k < n_pairs; k++) {
+        if (r1[k] >= pop_size || r2[k] >= pop_size)
+            return ps_fail(PS_ERR_INVALID, "pair %llu: index %u is not below pop_size %llu", (unsigned long long)k, std::max(r1[k], r2[k]),
+                           (unsigned long long)pop_size);
+        if (r1[k] == r2[k]) return ps_fail(PS_ERR_INVALID, "pair %llu: both indices are %u", (unsigned long long)k, r1[k]);
+        if (acc_on && acc_inter[k] > acc_union[k])
+            return ps_fail(PS_ERR_INVALID, "pair %llu: intersection %u above union %u", (unsigned long long)k, acc_inter[k], acc_union[k]);
+    }
+    const ps_cl_args a = cluster_args(prm, core_genes);
+    // union-find, the smaller root kept: root(k) is the smallest member of k's set
+    std::vector<uint32_t> parent(pop_size);
+    for (uint64_t k = 0; k < pop_size; k++) parent[k] = (uint32_t)k;
+    auto root = [&](uint32_t x) {
+        while (parent[x] != x) x = parent[x] = parent[parent[x]];
+        return x;
+    };
+    memset(out, 0, sizeof *out);
+    for (uint64_t k = 0; k < n_pairs; k++) {
+        const uint32_t h = core_on ? core_h[k] : 0u, in = acc_on ? acc_inter[k] : 0u, un = acc_on ? acc_union[k] : 0u;
+        bool undefined, edge;
+        if (core_on && acc_on) edge = ps_cl_edge<true, true>(h, in, un, a, &undefined);
+        else if (core_on) edge = ps_cl_edge<true, false>(h, in, un, a, &undefined);
+        else edge = ps_cl_edge<false, true>(h, in, un, a, &undefined);
+        out->undefined_pairs += undefined ? 1 : 0;
+        if (!edge) continue;
+        out->edges++;
+        const uint32_t x = root(r1[k]), y = root(r2[k]);
+        parent[std::max(x, y)] = std::min(x, y);
+    }
+    for (uint64_t k = 0; k < pop_size; k++) parent[k] = root((uint32_t)k);
+    out->pop_size = pop_size;
+    out->pairs = n_pairs;
+    out->core_sites = core_sites;
+    out->core_genes = core_genes;
+    cluster_finish(parent.data(), pop_size, labels, out);
+    return PS_OK;
+}
+
+// the scratch on the core handle: the two count words, the `changed` word, the labels, the bit matrix
+static int cluster_scratch(ps_population *c0, uint64_t N, unsigned long long **words, uint32_t **changed, uint32_t **L,
+                           unsigned long long **adj, uint64_t *bytes)
+{
+    const uint64_t W = (N + 63) / 64, head = (PS_CL_WORDS + 1) * 8, lab = (N * 4 + 7) & ~7ull;
+    const uint64_t need = head + lab + N * W * 8;
+    if (c0->cl_cap < need) {
+        if (c0->d_cl) HIPCHK(hipFree(c0->d_cl));
+        c0->d_cl = nullptr;
+        c0->cl_cap = 0;
+        if (hipMalloc(&c0->d_cl, need) != hipSuccess) {
+            (void)hipGetLastError();
+            return ps_fail(PS_ERR_OOM, "cannot allocate the %llu bytes of the adjacency bit matrix and the labels of %llu individuals",
+                           (unsigned long long)need, (unsigned long long)N);
+        }
+        c0->cl_cap = need;
+    }
+    uint8_t *base = (uint8_t *)c0->d_cl;
+    *words = (unsigned long long *)base;
+    *changed = (uint32_t *)(base + PS_CL_WORDS * 8);
+    *L = (uint32_t *)(base + head);
+    *adj = (unsigned long long *)(base + head + lab);
+    *bytes = need;
+    return PS_OK;
+}
+
+template <bool CORE, bool ACC>
+static int cluster_edge_launch(const ps_population *c0, const core_davg_bands &b, const pair_hist_acc &A, uint32_t lo, uint32_t nrows,
+                               const ps_cl_args &a, unsigned long long *adj, unsigned long long *words, hipStream_t st)
+{
+    const uint32_t N = (uint32_t)c0->cfg.pop_size;
+    // four waves per workgroup over the row's chunks, the rows over y (the grid of pair_hist_launch without bins in LDS)
+    const uint32_t nchunk = (N + 255u) / 256u, gx = std::max(1u, std::min((nchunk + 3u) / 4u, 8u));
+    const uint32_t gy = std::max(1u, std::min(std::min(nrows, 65535u), 2048u / gx));
+    hipLaunchKernelGGL((pair_edge_kernel<CORE, ACC>), dim3(gx, gy), dim3(256), 0, st, (const uint32_t *)c0->d_cdavg, b.ld,
+                       (const uint16_t *)A.In, A.ld, (const uint32_t *)A.rowcnt, N, lo, nrows, a, adj, words);
+    HIPCHK(hipGetLastError());
+    return PS_OK;
+}
+
+// The call behind the three device entries.  With a core criterion, band_counts(lo, nrows) leaves h(i, j) over ALL core
+// sites for the rows of the band in c0->d_cdavg, ordered on c0->stream; without one it is not called.  `acc` lives on c0's
+// device.  Both streams are idle on entry; `slot` is c0's current row map (rows_current).
+template <class F>
+static int cluster_device(ps_population *c0, ps_population *acc, const core_davg_bands &b, uint64_t L, const ps_cluster_params *prm,
+                          const uint32_t *slot, F &&band_counts, ps_cluster_t *out, uint32_t *labels)
+{
+    const uint32_t N = (uint32_t)c0->cfg.pop_size;
+    const uint64_t cg = acc->cfg.core_genes;
+    bool core_on, acc_on;
+    PSCHK(cluster_check_params(prm, &core_on, &acc_on));
+    const ps_cl_args a = cluster_args(prm, cg);
+    hipStream_t sc = c0->stream, sa = acc->stream;
+    PSCHK(use_device(c0));
+    unsigned long long *d_words, *d_adj;
+    uint32_t *d_changed, *d_L;
+    uint64_t bytes;
+    PSCHK(cluster_scratch(c0, N, &d_words, &d_changed, &d_L, &d_adj, &bytes));
+    HIPCHK(hipMemsetAsync(c0->d_cl, 0, bytes, sc));
+    cluster_init_kernel<<<(N + 255u) / 256u, 256, 0, sc>>>(d_L, N);
+    HIPCHK(hipGetLastError());
+    c0->cl_timed = false;
+    pair_hist_acc A;
+    if (acc_on) PSCHK(pair_hist_acc_prepare(acc, b.band, sa, &A));
+    pair_hist_events evs;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> timers[3];      // counts, edges, labels
+    auto timed = [&](int which, hipStream_t st, auto &&work) -> int {
+        hipEvent_t e0, e1;
+        PSCHK(evs.make(&e0));
+        PSCHK(evs.make(&e1));
+        HIPCHK(hipEventRecord(e0, st));
+        PSCHK(work());
+        HIPCHK(hipEventRecord(e1, st));
+        timers[which].push_back({ e0, e1 });
+        return PS_OK;
+    };
+    hipEvent_t ev_acc = nullptr, ev_edge = nullptr;
+    PSCHK(evs.make(&ev_acc));
+    PSCHK(evs.make(&ev_edge));
+    // the accessory counts of a band on their stream, behind the last edge kernel that read the scratch; the edges behind them
+    bool edged_before = false;
+    for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) {
+        const uint32_t nrows = std::min(b.band, b.c_end - lo);
+        if (core_on) PSCHK(timed(0, sc, [&]() { return band_counts(lo, nrows); }));
+        if (A.In) {
+            if (edged_before) HIPCHK(hipStreamWaitEvent(sa, ev_edge, 0));
+            PSCHK(timed(0, sa, [&]() { return pair_hist_acc_band(A, lo, nrows, sa); }));
+            HIPCHK(hipEventRecord(ev_acc, sa));
+            HIPCHK(hipStreamWaitEvent(sc, ev_acc, 0));
+        }
+        PSCHK(timed(1, sc, [&]() {
+            return core_on && acc_on ? cluster_edge_launch<true, true>(c0, b, A, lo, nrows, a, d_adj, d_words, sc)
+                   : core_on         ? cluster_edge_launch<true, false>(c0, b, A, lo, nrows, a, d_adj, d_words, sc)
+                                     : cluster_edge_launch<false, true>(c0, b, A, lo, nrows, a, d_adj, d_words, sc);
+        }));
+        HIPCHK(hipEventRecord(ev_edge, sc));
+        edged_before = true;
+    }
+    // the label rounds: labels only decrease and a label crosses at least one more edge per round, so a hook round that moves
+    // nothing comes within N rounds
+    uint64_t rounds = 0;
+    PSCHK(timed(2, sc, [&]() -> int {
+        for (;;) {
+            if (rounds == N) return ps_fail(PS_ERR_STATE, "the labels of %u individuals still moved in round %u", N, N);
+            rounds++;
+            uint32_t changed = 0;
+            HIPCHK(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), sc));
+            cluster_hook_kernel<<<std::min((N + 3u) / 4u, 2048u), 256, 0, sc>>>(d_adj, N, d_L, d_changed);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&changed, d_changed, sizeof changed, hipMemcpyDeviceToHost, sc));
+            HIPCHK(hipStreamSynchronize(sc));
+            if (!changed) return PS_OK;
+            cluster_jump_kernel<<<(N + 255u) / 256u, 256, 0, sc>>>(N, d_L);
+            HIPCHK(hipGetLastError());
+        }
+    }));
+    unsigned long long w[PS_CL_WORDS];
+    std::vector<uint32_t> rep(N);
+    HIPCHK(hipMemcpyAsync(w, d_words, sizeof w, hipMemcpyDeviceToHost, sc));
+    HIPCHK(hipMemcpyAsync(rep.data(), d_L, (uint64_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost, sc));
+    HIPCHK(hipStreamSynchronize(sa));
+    HIPCHK(hipStreamSynchronize(sc));
+    for (int which = 0; which < 3; which++) {
+        c0->cl_ms[which] = 0.0;
+        for (const auto &e : timers[which]) {
+            float ms = 0.0f;
+            HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
+            c0->cl_ms[which] += (double)ms;
+        }
+    }
+    c0->cl_timed = true;
+    rows_permute(rep.data(), slot, N);
+    memset(out, 0, sizeof *out);
+    out->pop_size = N;
+    out->pairs = (uint64_t)N * (N - 1) / 2;
+    out->core_sites = L;
+    out->core_genes = cg;
+    out->edges = w[PS_CL_EDGES];
+    out->undefined_pairs = w[PS_CL_UNDEF];
+    out->rounds = rounds;
+    cluster_finish(rep.data(), N, labels, out);
+    return PS_OK;
+}
+
+extern "C" int ps_strain_clusters(ps_population *core, ps_population *acc, const ps_cluster_params *prm, ps_cluster_t *out,
+                                  uint32_t *labels)
+{
+    PSCHK(pair_hist_needs_device());
+    if (!core || !acc || !prm || !out || !labels) return ps_fail(PS_ERR_INVALID, "null argument");
+    bool core_on, acc_on;
+    PSCHK(cluster_check_params(prm, &core_on, &acc_on));
+    PSCHK(pair_hist_handles(core, acc, "ps_strain_clusters", "strain clusters need"));
+    if (core->cfg.ncols != core->cfg.global_cols)
+        return ps_fail(PS_ERR_INVALID, "ps_strain_clusters compares over all %llu core sites; this handle is one site shard "
+                                       "([%llu, %llu)): use ps_multi_strain_clusters", (unsigned long long)core->cfg.global_cols,
+                       (unsigned long long)core->cfg.col_offset, (unsigned long long)(core->cfg.col_offset + core->cfg.ncols));
+    PSCHK(use_device(core));
+    const uint32_t *slot = nullptr;
+    PSCHK(rows_current(core, &slot));
+    // everything queued on either handle precedes the count kernels of both
+    HIPCHK(hipStreamSynchronize(acc->stream));
+    HIPCHK(hipStreamSynchronize(core->stream));
+    const uint32_t N = (uint32_t)core->cfg.pop_size;
+    const core_davg_bands b = core_davg_plan_bands(core, 0, N);
+    core_davg_src src{};
+    if (core_on) PSCHK(core_davg_prepare(core, b, core->onehot_safe && core->core_davg_form != 3, nullptr, core->stream, &src));
+    return cluster_device(core, acc, b, core->cfg.global_cols, prm, slot,
+                          [&](uint32_t lo, uint32_t nrows) { return core_davg_band_counts(core, src, b, lo, nrows, core->stream); }, out, labels);
+}
+
+extern "C" int ps_sim_strain_clusters(ps_sim *s, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels)
+{
+    PSCHK(pair_hist_needs_device());
+    if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
+    return ps_strain_clusters(s->core, s->acc, prm, out, labels);
+}
+
+extern "C" int ps_strain_clusters_timing(ps_population *core, double *counts_ms, double *edges_ms, double *labels_ms)
+{
+    if (!core) return ps_fail(PS_ERR_INVALID, "null argument");
+    if (!core->cl_timed) return ps_fail(PS_ERR_STATE, "no strain clusters have been computed on this handle");
+    if (counts_ms) *counts_ms = core->cl_ms[0];
+    if (edges_ms) *edges_ms = core->cl_ms[1];
+    if (labels_ms) *labels_ms = core->cl_ms[2];
+    return PS_OK;
+}
+
+// As ps_multi_distance_histogram: band by band the shards' counts are added on shard 0 (multi_band_counts); the edges and the
+// labels on shard 0 against its accessory replica, the row map from shard 0's simulation.
+extern "C" int ps_multi_strain_clusters(ps_multi *m, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels)
+{
+    PSCHK(pair_hist_needs_device());
+    if (!m || !prm || !out || !labels) return ps_fail(PS_ERR_INVALID, "null argument");
+    const size_t K = m->shard.size();
+    if (K == 1) return ps_sim_strain_clusters(m->shard[0], prm, out, labels);
+    bool core_on, acc_on;
+    PSCHK(cluster_check_params(prm, &core_on, &acc_on));
+    ps_population *c0 = m->shard[0]->core, *acc = m->shard[0]->acc;
+    PSCHK(pair_hist_handles(c0, acc, "ps_multi_strain_clusters", "strain clusters need"));
+    const uint32_t N = (uint32_t)m->prm.pop_size;
+    const uint32_t *slot = nullptr;
+    PSCHK(use_device(c0));
+    PSCHK(rows_current(c0, &slot));
+    PSCHK(ps_multi_sync(m));
+    const core_davg_bands b = core_davg_plan_bands(c0, 0, N);
+    bool onehot = true;
+    for (size_t k = 0; k < K; k++) onehot = onehot && m->shard[k]->core->onehot_safe && c0->core_davg_form != 3;
+    std::vector<core_davg_src> src(K);
+    if (core_on)
+        PSCHK(multi_for_each(m, [&](size_t k) {
+            ps_population *c = m->shard[k]->core;
+            PSCHK(use_device(c));
+            return core_davg_prepare(c, b, onehot, nullptr, c->stream, &src[k]);
+        }));
+    PSCHK(use_device(c0));
+    uint32_t *d_land = nullptr;         // (without peer access: a peer's band counts copied over first)
+    if (core_on && !m->peers_ok) HIPCHK(hipMalloc(&d_land, (uint64_t)b.band * b.ld * sizeof(uint32_t)));
+    auto band_counts = [&](uint32_t lo, uint32_t nrows) { return multi_band_counts(m, src, b, d_land, lo, nrows); };
+    const int rc = cluster_device(c0, acc, b, m->prm.core_size, prm, slot, band_counts, out, labels);
+    (void)hipSetDevice(c0->device);
+    (void)hipStreamSynchronize(c0->stream);
+    if (d_land) (void)hipFree(d_land);
+    return rc;
+}

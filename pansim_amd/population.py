@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import Config, CoreDiversity, PairHist, PairHistParams, check
+from ._lib import ClusterParams, Clusters, Config, CoreDiversity, PairHist, PairHistParams, check
 
 
 def _u32(a):
@@ -203,6 +203,67 @@ def histogram_from_counts(core_h, acc_inter, acc_union, core_sites, core_genes, 
         raise ValueError("one core numerator, one intersection and one union per pair")
     prm = _hist_params(core_bins, acc_bins, core_max, core_sites, core_span)
     return _hist_call(_lib.load().ps_histogram_from_counts, prm, _ptr(h), _ptr(i), _ptr(u), h.size, int(core_sites), int(core_genes))
+
+
+class StrainClusters:
+    """The result of `strain_clusters` (ps_cluster_t + the labels; docs/STRAIN_CLUSTERS.md): the summary fields as integer
+    attributes and `labels` -- pop_size uint32, labels[k] the smallest row of k's cluster."""
+    FIELDS = tuple(name for name, _ in Clusters._fields_)
+
+    def __init__(self, c, labels):
+        for name in self.FIELDS:
+            setattr(self, name, int(getattr(c, name)))
+        self.labels = labels
+
+    def sizes(self):
+        """the cluster sizes, descending"""
+        return np.sort(np.bincount(self.labels)[np.unique(self.labels)])[::-1]
+
+    def as_dict(self):
+        out = {name: getattr(self, name) for name in self.FIELDS}
+        out["labels"] = self.labels
+        return out
+
+
+def _cluster_params(core_sites, core_max=None, acc_max=None, core_max_d=None, acc_ratio=None):
+    """The integer thresholds of a call.  Distances are converted once: core_max_d = floor(core_max L), acc_num / acc_den =
+    floor(acc_max 2^20) / 2^20.  `core_max_d` (in units of d) and `acc_ratio` ((num, den)) give the integers themselves
+    and override them; a criterion that is not given is not applied."""
+    prm = ClusterParams(2**64 - 1, 0, 0)
+    if core_max_d is not None:
+        prm.core_max_d = int(core_max_d)
+    elif core_max is not None:
+        if not float(core_max) >= 0.0:
+            raise ValueError("core_max must be >= 0.0")
+        prm.core_max_d = min(2**64 - 2, int(np.floor(float(core_max) * int(core_sites))))
+    if acc_ratio is not None:
+        prm.acc_num, prm.acc_den = (int(x) for x in acc_ratio)
+    elif acc_max is not None:
+        if not 0.0 <= float(acc_max) <= 1.0:
+            raise ValueError("acc_max must be in [0.0, 1.0]")
+        prm.acc_num, prm.acc_den = int(np.floor(float(acc_max) * 2**20)), 2**20
+    return prm
+
+
+def _cluster_call(fn, prm, pop_size, *head):
+    """fn(*head, &params, &summary, labels) -> StrainClusters"""
+    c = Clusters()
+    labels = np.zeros(max(1, int(pop_size)), np.uint32)
+    check(fn(*head, C.byref(prm), C.byref(c), _ptr(labels)))
+    return StrainClusters(c, labels[:int(pop_size)])
+
+
+def clusters_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_sites, core_genes, core_max=None, acc_max=None,
+                         core_max_d=None, acc_ratio=None):
+    """`Population.strain_clusters` from any list of pairs (r1, r2) and their numerators (`pairwise_counts` of both
+    matrices), on the host alone (ps_clusters_from_counts; no device).  The numerators of a criterion that is not applied
+    may be None."""
+    arrays = [None if a is None else _u32(a).reshape(-1) for a in (r1, r2, core_h, acc_inter, acc_union)]
+    if len({a.size for a in arrays if a is not None}) != 1 or arrays[0] is None or arrays[1] is None:
+        raise ValueError("two indices, and one value of every numerator given, per pair")
+    prm = _cluster_params(core_sites, core_max, acc_max, core_max_d, acc_ratio)
+    return _cluster_call(_lib.load().ps_clusters_from_counts, prm, pop_size, *map(_ptr, arrays), arrays[0].size, int(pop_size),
+                         int(core_sites), int(core_genes))
 
 
 def draw_parents(weights, seed, generation):
@@ -417,6 +478,19 @@ class Population:
         a, b = C.c_double(), C.c_double()
         check(self._lib.ps_distance_histogram_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def strain_clusters(self, acc, core_max=None, acc_max=None, core_max_d=None, acc_ratio=None):
+        """the single-linkage clusters of ALL individuals of this core population and the accessory population `acc` of
+        the same individuals (ps_strain_clusters; docs/STRAIN_CLUSTERS.md) -> a StrainClusters.  A pair is joined when its
+        core distance is at most `core_max` and its accessory distance at most `acc_max` (either may be left out)."""
+        prm = _cluster_params(self.global_cols, core_max, acc_max, core_max_d, acc_ratio)
+        return _cluster_call(self._lib.ps_strain_clusters, prm, self.size, self._h, acc._h)
+
+    def strain_clusters_timing(self):
+        """device ms of (the count kernels, the edge kernel, the label rounds) of the last strain_clusters() on this core handle"""
+        t = [C.c_double() for _ in range(3)]
+        check(self._lib.ps_strain_clusters_timing(self._h, *map(C.byref, t)))
+        return tuple(x.value for x in t)
 
     def core_diversity_timing(self):
         """device ms of the counts kernel of the last site_allele_counts() / core_diversity() call"""

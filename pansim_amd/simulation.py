@@ -240,6 +240,13 @@ class Simulation:
         prm = _hist_params(core_bins, acc_bins, core_max, self.params.core_size, core_span)
         return _hist_call(self._lib.ps_sim_distance_histogram, prm, self._h)
 
+    def strain_clusters(self, core_max=None, acc_max=None, core_max_d=None, acc_ratio=None):
+        """Population.strain_clusters() of the run's two matrices (ps_sim_strain_clusters), labels in the reference's row
+        order: behind every queued generation, and without a change of state"""
+        from .population import _cluster_call, _cluster_params
+        prm = _cluster_params(self.params.core_size, core_max, acc_max, core_max_d, acc_ratio)
+        return _cluster_call(self._lib.ps_sim_strain_clusters, prm, self.params.pop_size, self._h)
+
     def write_outputs(self, outpref):
         core, acc = self.final_distances()
         with open(outpref + ".tsv", "w") as f:                       # main.rs:474-482
@@ -333,6 +340,13 @@ class MultiSimulation:
         from .population import _hist_call, _hist_params
         prm = _hist_params(core_bins, acc_bins, core_max, self.params.core_size, core_span)
         return _hist_call(self._lib.ps_multi_distance_histogram, prm, self._h)
+
+    def strain_clusters(self, core_max=None, acc_max=None, core_max_d=None, acc_ratio=None):
+        """Population.strain_clusters() over ALL core sites: the shards' band counts added on shard 0, edges and labels
+        against its accessory replica (ps_multi_strain_clusters)"""
+        from .population import _cluster_call, _cluster_params
+        prm = _cluster_params(self.params.core_size, core_max, acc_max, core_max_d, acc_ratio)
+        return _cluster_call(self._lib.ps_multi_strain_clusters, prm, self.params.pop_size, self._h)
 
     def write(self, outpref):
         check(self._lib.ps_multi_write(self._h, str(outpref).encode()))
