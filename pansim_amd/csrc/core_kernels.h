@@ -237,7 +237,7 @@ __global__ void __launch_bounds__(1024) core_sweep_inline_kernel(core_sweep_args
 //      operations on the plane words give the DECIDED cells (the symbol names an allele) and the RESIDUAL ones (no
 //      per-cell arithmetic at all: ps_classes);
 //   2. the symbol-decided mutations -- three of four events -- are applied in registers to the gathered child dwords
-//      before they go back to LDS (ps_apply_prepare / ps_apply_dword: byte-lane flags, two v_perm_b32 look-ups, one v_bfi);
+//      before they go back to LDS (ps_apply_prepare / ps_apply_dword: byte-lane flags, two v_perm_b32 look-ups, one v_bitop3_b32 select);
 //   3. one prefix sum over the wave pushes the residual cells of the 4 rows into a wave-private LDS queue of 16-bit
 //      entries (ps_push_scan);
 //   4. an exact pass over the residual cells: level-2 Philox, 32-bit thresholds, mutation bytes into the LDS rows; HR
@@ -308,9 +308,18 @@ __device__ __forceinline__ ps_class_words ps_classes(uint32_t p0, uint32_t p1, u
 // for the dword of cells 4j .. 4j + 3 at site parity h the three flags of a cell sit at bit s = j + 4h of its byte in
 // each word.  Five merged words put (p4, p5, dec) of a slot side by side -- value 4 + allele index in the mutated bytes,
 // 0 elsewhere -- so that per dword one shift and one mask give a byte-wise selector, two v_perm_b32 look up the allele
-// and the byte mask, and one v_bfi_b32 writes the alleles into the child dword: no per-cell work, no queue.
+// and the byte mask, and one v_bitop3_b32 (ps_bfi) writes the alleles into the child dword: no per-cell work, no queue.
 struct ps_apply_words { uint32_t y0, y1, ya, yb, yc; };
-__device__ __forceinline__ uint32_t ps_bfi(uint32_t m, uint32_t a, uint32_t b) { return (a & m) | (b & ~m); }
+// bit-field insert, a where m is set and b elsewhere: one v_bitop3_b32 on gfx950 (truth table 0xCA in the order (m, a, b);
+// the plain expression lowers to v_xor / v_and / v_and / v_or)
+PS_HD uint32_t ps_bfi(uint32_t m, uint32_t a, uint32_t b)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && __has_builtin(__builtin_amdgcn_bitop3_b32)
+    return __builtin_amdgcn_bitop3_b32(m, a, b, 0xCA);
+#else
+    return (a & m) | (b & ~m);
+#endif
+}
 __device__ __forceinline__ ps_apply_words ps_apply_prepare(uint32_t dec, uint32_t p4, uint32_t p5)
 {
     const uint32_t r1 = p5 >> 1, r2 = p4 >> 2, l1 = p5 << 1, l2 = dec << 2;
@@ -330,7 +339,7 @@ __device__ __forceinline__ uint32_t ps_apply_dword(const ps_apply_words &y, uint
     const uint32_t f = (src >> sh) & 0x07070707u;                          // 4 + allele index in the mutated bytes, else 0
     const uint32_t allele = __builtin_amdgcn_perm(0x00080402u, 0u, f);     // selector 4, 5, 6 -> 2, 4, 8; 0 -> 0
     const uint32_t mask = __builtin_amdgcn_perm(0x00FFFFFFu, 0u, f);       // ... -> 0xFF; 0 -> 0
-    return ps_bfi(mask, allele, d);
+    return ps_bfi(mask, allele, d);                                        // (allele is 0 wherever mask is: no allele & mask)
 }
 // all four dwords of the child row at site parity H of the pair
 template <uint32_t H>
@@ -398,8 +407,8 @@ __host__ __device__ constexpr uint32_t ps_wave_lds(uint32_t qcap) { return PS_BA
 // generation g, complete -- the parent rows of generation g + 1.  The wave applies generations gen .. gen + T - 1 (Philox
 // keyed on gen + t, parents idx / idx_next[t - 1]) between ONE load and ONE store of the rows: the HBM traffic per
 // generation is 2 N L / T and the results are those of T launches, bit for bit.  T = 1 is the single-generation kernel
-// unchanged (70 VGPRs, built for PS_WAVE_LB = 6 waves per SIMD); T = 2 keeps both generations' 16 parent indices in
-// registers -- unpacked: two 10-bit indices per register would save 16 VGPRs the build does not need (it takes 95 of the
+// unchanged (64-67 VGPRs, built for PS_WAVE_LB = 6 waves per SIMD); T = 2 keeps both generations' 16 parent indices in
+// registers -- unpacked: two 10-bit indices per register would save 16 VGPRs the build does not need (it takes 90-91 of the
 // 128 that 4 waves per SIMD allow, the residency the generation loop launches it at; no scratch) and cost a v_bfe per
 // gathered byte on the vector ALUs, which bound a two-generation launch (profiles/sweep_two_generations.md).
 template <bool DO_GATHER, bool DO_MUT, bool DO_HR, bool NT = false, bool WT = false, uint32_t T = 1>
