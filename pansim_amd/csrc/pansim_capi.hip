@@ -20,6 +20,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "acc_kernels.h"
@@ -329,6 +330,53 @@ static int use_device(const ps_population *p)
     HIPCHK(hipSetDevice(p->device));
     return PS_OK;
 }
+
+// Grow a scratch buffer that a handle keeps between calls.  `need` and `cap` are in the unit of the cap field: elements of T,
+// bytes for a void pointer.  The buffer is freed and both fields cleared BEFORE the allocation: a failed hipMalloc leaves the
+// handle consistent.  dev_grow_err reports the HIP error as it is (after a failed allocation the pointer is null).
+template <class T>
+static hipError_t dev_grow_err(T *&ptr, uint64_t &cap, uint64_t need)
+{
+    if (cap >= need) return hipSuccess;
+    if (ptr) {
+        const hipError_t e = hipFree(ptr);
+        if (e != hipSuccess) return e;
+    }
+    ptr = nullptr;
+    cap = 0;
+    const hipError_t e = hipMalloc(&ptr, need * sizeof(std::conditional_t<std::is_void<T>::value, char, T>));
+    if (e == hipSuccess) cap = need;
+    return e;
+}
+
+template <class T>
+static int dev_grow(T *&ptr, uint64_t &cap, uint64_t need)
+{
+    HIPCHK(dev_grow_err(ptr, cap, need));
+    return PS_OK;
+}
+
+// a device allocation that lives for one call: freed on the device it was made on, on every way out
+template <class T>
+struct dev_tmp {
+    T *p = nullptr;
+    int device = 0;
+    dev_tmp() = default;
+    dev_tmp(const dev_tmp &) = delete;
+    dev_tmp &operator=(const dev_tmp &) = delete;
+    ~dev_tmp()
+    {
+        if (!p) return;
+        (void)hipSetDevice(device);
+        (void)hipFree(p);
+    }
+    int alloc(uint64_t n)
+    {
+        HIPCHK(hipGetDevice(&device));
+        HIPCHK(hipMalloc(&p, n * sizeof(T)));
+        return PS_OK;
+    }
+};
 
 // output rows in the reference's order: row_slot current (see struct ps_population), nullptr = internal order
 static int rows_current(ps_population *p, const uint32_t **slot_out)
@@ -1510,13 +1558,7 @@ static int launch_acc_hgt(ps_population *p, uint32_t gen, hipStream_t st, hipEve
         // LONGER -- 8.3 -> 9.4 ms per generation at 1/8 of the sites -- so ps_sim leaves it off: test hook only)
         const uint64_t list_bytes = p->hgt_bin_list_in_global ? (((uint64_t)donor_blocks * list_u16 * sizeof(uint16_t) + 255) & ~255ull) : 0;
         const uint64_t need = img_bytes + bin_words * 4 + cnt_bytes + list_bytes;
-        if (p->hgt_scratch_cap < need) {
-            if (p->hgt_scratch) HIPCHK(hipFree(p->hgt_scratch));
-            p->hgt_scratch = nullptr;
-            p->hgt_scratch_cap = 0;
-            HIPCHK(hipMalloc(&p->hgt_scratch, need));
-            p->hgt_scratch_cap = need;
-        }
+        PSCHK(dev_grow(p->hgt_scratch, p->hgt_scratch_cap, need));
         if (!p->hgt_ovf_img) {
             // the overflow image of the bin pass: zero now, and left zero by every reduce pass
             HIPCHK(hipMalloc(&p->hgt_ovf_img, words * 8));
@@ -1593,13 +1635,7 @@ static int launch_acc_hgt(ps_population *p, uint32_t gen, hipStream_t st, hipEve
             // the co-running block sweep owns the CU's LDS: keep the donor lists in a per-workgroup
             // global scratch instead (hot in L2; reads of a list come from the workgroup that wrote it)
             const uint64_t need = (uint64_t)grid * list_u16 * sizeof(uint16_t);
-            if (p->hgt_scratch_cap < need) {
-                if (p->hgt_scratch) HIPCHK(hipFree(p->hgt_scratch));
-                p->hgt_scratch = nullptr;
-                p->hgt_scratch_cap = 0;
-                HIPCHK(hipMalloc(&p->hgt_scratch, need));
-                p->hgt_scratch_cap = need;
-            }
+            PSCHK(dev_grow(p->hgt_scratch, p->hgt_scratch_cap, need));
             a.list_scratch = (uint16_t *)p->hgt_scratch;
             a.list_stride = list_u16;
             dyn_lds = 0;
@@ -2054,6 +2090,43 @@ extern "C" int ps_sample_indices(ps_population *acc, uint32_t generation, int32_
 // ---------------------------------------------------------------------------
 // distances
 // ---------------------------------------------------------------------------
+// The accessory rows padded for the matrix cores (WP words a row, Npad rows) and their gene counts, in p->d_davg on `st`; the
+// u16 intersection counts of a band of rows go to p->d_davg_in with the row pitch ld.
+// (row pitch of the counts: Npad u16 + 256 bytes -- with a power-of-two pitch the 32 rows one store instruction touches, and the
+// 16 rows a phase-2 workgroup reads, fall on ONE memory channel)
+struct acc_padded { uint32_t *rowsP = nullptr, *rowcnt = nullptr; uint32_t WP = 0, Npad = 0, ld = 0; };
+
+static int acc_rows_padded(ps_population *p, hipStream_t st, acc_padded *o)
+{
+    const uint64_t N = p->cfg.pop_size;
+    o->WP = (2u * p->d.GW + 7u) & ~7u;
+    o->Npad = (uint32_t)((N + 127) & ~127ull);
+    o->ld = o->Npad + 128u;
+    PSCHK(dev_grow(p->d_davg, p->davg_cap, (uint64_t)o->Npad * o->WP * 4 + (uint64_t)o->Npad * 4 + 64));
+    o->rowsP = (uint32_t *)p->d_davg;
+    o->rowcnt = o->rowsP + (uint64_t)o->Npad * o->WP;
+    acc_rows_pad_kernel<<<(o->Npad + 3u) / 4u, 256, 0, st>>>(p->I[p->cur], o->rowsP, o->rowcnt, p->d, o->WP, o->Npad);
+    HIPCHK(hipGetLastError());
+    return PS_OK;
+}
+
+// The contraction on every SIMD: In[row - lo][j] = |row AND j| for the rows [lo, lo + rows) x all columns, in p->d_davg_in, sized
+// for bands of `band` rows (a wave stores 32 * nb whole rows, at most 128: `band` is a multiple of that).  nb = B fragments per
+// wave (4, 2, else 1).
+static int acc_intersections_band(ps_population *p, const acc_padded &R, uint32_t nb, uint64_t band, uint32_t lo, uint32_t rows, hipStream_t st)
+{
+    PSCHK(dev_grow(p->d_davg_in, p->davg_in_cap, band * R.ld * 2));
+    const uint32_t lds = 256u * 64u * 4u, steps = R.Npad / 128u, gx = (rows + 128u * nb - 1u) / (128u * nb);
+    uint32_t jsteps = 8u;
+    while (jsteps > 1u && (uint64_t)gx * ((steps + jsteps - 1u) / jsteps) < 2048u) jsteps >>= 1;
+    auto kern = nb == 4u ? acc_intersections_mfma_kernel<4u> : nb == 2u ? acc_intersections_mfma_kernel<2u> : acc_intersections_mfma_kernel<1u>;
+    HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(gx, (steps + jsteps - 1u) / jsteps), dim3(256), lds, st, (const uint32_t *)R.rowsP, R.WP, R.Npad, lo, rows,
+                       jsteps, (uint16_t *)p->d_davg_in, R.ld);
+    HIPCHK(hipGetLastError());
+    return PS_OK;
+}
+
 // D-avg (population.rs:753-784) into a device buffer of N doubles.  Rows [i_lo, i_lo + i_cnt) only (a row shard of a
 // sharded run, DESIGN.md 6: the other entries of d_out are left alone); the whole population when i_cnt == N.
 static int average_distance_device(ps_population *p, double *d_out, hipStream_t st, uint64_t i_lo = 0, uint64_t i_cnt = ~0ull)
@@ -2072,55 +2145,22 @@ static int average_distance_device(ps_population *p, double *d_out, hipStream_t 
     // counts written and read back (N = 57344: 9.95 against 10.29 ms; N = 65536: 11.1 against 13.3)
     const bool two_phase = mfma && p->davg_form != 2 && p->d.G <= 65535 && (p->davg_form == 3 || !whole || i_cnt <= 53248);      // (u16 counts)
     if (mfma) {
-        const uint32_t WP = (2u * p->d.GW + 7u) & ~7u, Npad = (uint32_t)((N + 127) & ~127ull);
-        const uint64_t need = (uint64_t)Npad * WP * 4 + (uint64_t)Npad * 4 + 64;
-        if (p->davg_cap < need) {
-            if (p->d_davg) HIPCHK(hipFree(p->d_davg));
-            p->d_davg = nullptr;
-            p->davg_cap = 0;
-            HIPCHK(hipMalloc(&p->d_davg, need));
-            p->davg_cap = need;
-        }
-        uint32_t *rowsP = (uint32_t *)p->d_davg, *rowcnt = rowsP + (uint64_t)Npad * WP;
-        acc_rows_pad_kernel<<<(Npad + 3u) / 4u, 256, 0, st>>>(p->I[p->cur], rowsP, rowcnt, p->d, WP, Npad);
-        const uint32_t lds = 256u * 64u * 4u;
+        acc_padded R;
+        PSCHK(acc_rows_padded(p, st, &R));
+        uint32_t *rowsP = R.rowsP, *rowcnt = R.rowcnt;
+        const uint32_t WP = R.WP, Npad = R.Npad, lds = 256u * 64u * 4u;
         // (the lean division needs core_genes + the largest union below 2^32: always, short of an absurd --core_genes)
         const bool fast = p->cfg.core_genes < (1ull << 31) && !p->davg_plain_division;
         const uint32_t cgi = fast ? (uint32_t)p->cfg.core_genes : 0u;
         if (two_phase) {
-            // phase 1 (contraction, every SIMD) -> u16 counts In[row][j]; phase 2 (division + the ordered fold).  Rows in
+            // phase 1 (acc_intersections_band) -> u16 counts In[row][j]; phase 2 (division + the ordered fold).  Rows in
             // bands so that the scratch stays below ~9 GB (N = 65536 whole: one band of 8.6 GB)
-            // (row pitch of the counts: Npad u16 + 256 bytes -- with a power-of-two pitch the 32 rows one store instruction
-            // touches, and the 16 rows a phase-2 workgroup reads, fall on ONE memory channel)
-            const uint32_t nb = p->davg_nb ? p->davg_nb : 2u, ld = Npad + 128u;
-            // (a wave of phase 1 stores 32 * nb whole rows, at most 128: the band -- the scratch's row count -- is a multiple of that)
-            uint64_t band = std::min<uint64_t>((i_cnt + 127) & ~127ull, std::max<uint64_t>(256, ((9ull << 30) / ((uint64_t)ld * 2)) & ~255ull));
-            const uint64_t need_in = band * ld * 2;
-            if (p->davg_in_cap < need_in) {
-                if (p->d_davg_in) HIPCHK(hipFree(p->d_davg_in));
-                p->d_davg_in = nullptr;
-                p->davg_in_cap = 0;
-                HIPCHK(hipMalloc(&p->d_davg_in, need_in));
-                p->davg_in_cap = need_in;
-            }
-            uint16_t *In = (uint16_t *)p->d_davg_in;
-            const uint32_t steps = Npad / 128u;
+            const uint32_t nb = p->davg_nb ? p->davg_nb : 2u, ld = R.ld;
+            const uint64_t band = std::min<uint64_t>((i_cnt + 127) & ~127ull, std::max<uint64_t>(256, ((9ull << 30) / ((uint64_t)ld * 2)) & ~255ull));
             for (uint64_t b0 = 0; b0 < i_cnt; b0 += band) {
                 const uint32_t rows = (uint32_t)std::min<uint64_t>(band, i_cnt - b0), lo = (uint32_t)(i_lo + b0);
-                const uint32_t gx = (rows + 128u * nb - 1u) / (128u * nb);
-                uint32_t jsteps = 8u;
-                while (jsteps > 1u && (uint64_t)gx * ((steps + jsteps - 1u) / jsteps) < 2048u) jsteps >>= 1;
-                const dim3 grid(gx, (steps + jsteps - 1u) / jsteps);
-                if (nb == 4u) {
-                    HIPCHK(hipFuncSetAttribute((const void *)acc_intersections_mfma_kernel<4u>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    acc_intersections_mfma_kernel<4u><<<grid, 256, lds, st>>>(rowsP, WP, Npad, lo, rows, jsteps, In, ld);
-                } else if (nb == 2u) {
-                    HIPCHK(hipFuncSetAttribute((const void *)acc_intersections_mfma_kernel<2u>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    acc_intersections_mfma_kernel<2u><<<grid, 256, lds, st>>>(rowsP, WP, Npad, lo, rows, jsteps, In, ld);
-                } else {
-                    HIPCHK(hipFuncSetAttribute((const void *)acc_intersections_mfma_kernel<1u>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    acc_intersections_mfma_kernel<1u><<<grid, 256, lds, st>>>(rowsP, WP, Npad, lo, rows, jsteps, In, ld);
-                }
+                PSCHK(acc_intersections_band(p, R, nb, band, lo, rows, st));
+                const uint16_t *In = (const uint16_t *)p->d_davg_in;
                 // (workgroups of 16 individuals -- four per CU, half the staging per fold -- except where 32 make exactly one round of
                 // one per CU.  N = 65536: whole 4.99 against 5.42 ms, a shard of 8 0.889 against 0.836; N = 32768 whole 3.29
                 // against 3.58 with phase 1, its shard of 8 0.65 against 0.73; N = 16384 shard 0.28 against 0.33)
@@ -2280,13 +2320,7 @@ static int upload_pairs(ps_population *p, uint64_t P, const uint32_t *r1, const 
 // partial counts of the tiled distance kernels, part[range][P]
 static int pair_partials(ps_population *p, uint64_t words, uint32_t **out)
 {
-    if (p->pair_part_cap < words) {
-        if (p->d_pair_part) HIPCHK(hipFree(p->d_pair_part));
-        p->d_pair_part = nullptr;
-        p->pair_part_cap = 0;
-        HIPCHK(hipMalloc(&p->d_pair_part, words * sizeof(uint32_t)));
-        p->pair_part_cap = words;
-    }
+    PSCHK(dev_grow(p->d_pair_part, p->pair_part_cap, words));
     *out = p->d_pair_part;
     return PS_OK;
 }
@@ -2375,13 +2409,7 @@ static int pair_counts_device(ps_population *p, uint64_t P, const uint32_t *d_r1
             const uint32_t spw = nib ? 8u : 16u;
             const uint32_t WT = ((rows + spw - 1u) / spw + PS_PT_WB - 1u) / PS_PT_WB * PS_PT_WB;
             const uint64_t need = (uint64_t)N * WT;
-            if (p->pack2_cap < need) {
-                if (p->d_pack2) HIPCHK(hipFree(p->d_pack2));
-                p->d_pack2 = nullptr;
-                p->pack2_cap = 0;
-                HIPCHK(hipMalloc(&p->d_pack2, need * sizeof(uint32_t)));
-                p->pack2_cap = need;
-            }
+            PSCHK(dev_grow(p->d_pack2, p->pack2_cap, need));
             const uint64_t ptiles = (uint64_t)((N + PS_PT_IB - 1u) / PS_PT_IB) * (WT / PS_PT_WB);
             if (ptiles > 0x7FFFFFFFull) return ps_fail(PS_ERR_INVALID, "matrix too large for the transposed distance form");
             const dim3 pgrid((uint32_t)ptiles);
@@ -2399,13 +2427,7 @@ static int pair_counts_device(ps_population *p, uint64_t P, const uint32_t *d_r1
             p->last_pair_form = PS_PAIR_FORM_ALLPAIRS_MFMA;
             const uint32_t WT = ((rows + 15u) / 16u + PS_PT_WB - 1u) / PS_PT_WB * PS_PT_WB;
             const uint64_t need = (uint64_t)((N + 31u) / 32u * 32u) * WT;       // blocked strings: whole groups of 32 individuals
-            if (p->pack2_cap < need) {
-                if (p->d_pack2) HIPCHK(hipFree(p->d_pack2));
-                p->d_pack2 = nullptr;
-                p->pack2_cap = 0;
-                HIPCHK(hipMalloc(&p->d_pack2, need * sizeof(uint32_t)));
-                p->pack2_cap = need;
-            }
+            PSCHK(dev_grow(p->d_pack2, p->pack2_cap, need));
             const uint64_t ptiles = (uint64_t)((N + PS_PT_IB - 1u) / PS_PT_IB) * (WT / PS_PT_WB);
             if (ptiles > 0x7FFFFFFFull) return ps_fail(PS_ERR_INVALID, "matrix too large for the transposed distance form");
             const uint32_t ntile = (N + PS_MF_TILE - 1u) / PS_MF_TILE;
@@ -2414,13 +2436,7 @@ static int pair_counts_device(ps_population *p, uint64_t P, const uint32_t *d_r1
             uint32_t ranges = mfma_allpairs_ranges(N, n_chunks, tile_pairs);
             const uint32_t cpr = (n_chunks + ranges - 1u) / ranges;
             ranges = (n_chunks + cpr - 1u) / cpr;          // (every range holds at least one chunk: every slice is written)
-            if (p->H_cap < (uint64_t)N * N * ranges) {
-                if (p->d_H) HIPCHK(hipFree(p->d_H));
-                p->d_H = nullptr;
-                p->H_cap = 0;
-                HIPCHK(hipMalloc(&p->d_H, (uint64_t)N * N * ranges * sizeof(uint32_t)));
-                p->H_cap = (uint64_t)N * N * ranges;
-            }
+            PSCHK(dev_grow(p->d_H, p->H_cap, (uint64_t)N * N * ranges));
             const uint32_t lds = 256u * 16u * 16u;
             // i8 (pair_mode 6), the block-scaled FP4 form on one-hot {0, 1} nibbles (the default: twice the sites per instruction
             // at the same cycles; a range must stay below 2^24 sites for the f32 sums to be exact) or (pair_mode 7) the FP4 form
@@ -2450,13 +2466,7 @@ static int pair_counts_device(ps_population *p, uint64_t P, const uint32_t *d_r1
             p->last_pair_form = PS_PAIR_FORM_ALLPAIRS;
             const uint32_t WA = 32u, ntile = (N + 127u) / 128u;
             const uint32_t lds = 2u * 128u * ((WA >> 2) + 1u) * 16u;
-            if (p->H_cap < (uint64_t)N * N) {
-                if (p->d_H) HIPCHK(hipFree(p->d_H));
-                p->d_H = nullptr;
-                p->H_cap = 0;
-                HIPCHK(hipMalloc(&p->d_H, (uint64_t)N * N * sizeof(uint32_t)));
-                p->H_cap = (uint64_t)N * N;
-            }
+            PSCHK(dev_grow(p->d_H, p->H_cap, (uint64_t)N * N));
             HIPCHK(hipMemsetAsync(p->d_H, 0, (uint64_t)N * N * sizeof(uint32_t), st));
             const uint32_t tile_pairs = ntile * (ntile + 1u) / 2u;
             const uint32_t n_chunks = (rows + WA * 8u - 1u) / (WA * 8u);
@@ -2473,13 +2483,7 @@ static int pair_counts_device(ps_population *p, uint64_t P, const uint32_t *d_r1
             constexpr uint32_t PT = 1024;
             const uint32_t n_tiles = (rows + W * 16 - 1) / (W * 16);
             const uint64_t need = (uint64_t)n_tiles * N * W;
-            if (p->pack2_cap < need) {
-                if (p->d_pack2) HIPCHK(hipFree(p->d_pack2));
-                p->d_pack2 = nullptr;
-                p->pack2_cap = 0;
-                HIPCHK(hipMalloc(&p->d_pack2, need * sizeof(uint32_t)));
-                p->pack2_cap = need;
-            }
+            PSCHK(dev_grow(p->d_pack2, p->pack2_cap, need));
             const uint32_t pack_lds = N * W * 4u;
             if (pack_lds > 64 * 1024)
                 HIPCHK(hipFuncSetAttribute((const void *)core_pack2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pack_lds));
@@ -2537,13 +2541,7 @@ static int pair_counts_device(ps_population *p, uint64_t P, const uint32_t *d_r1
         const bool all = p->pair_mode != 1 && (uint64_t)N * N * 4 <= (2ull << 30)
                          && (p->pair_mode == 2 || (double)P * 4.0 > (double)N * (double)N);
         if (all) {
-            if (p->H_cap < (uint64_t)N * N + N) {
-                if (p->d_H) HIPCHK(hipFree(p->d_H));
-                p->d_H = nullptr;
-                p->H_cap = 0;
-                HIPCHK(hipMalloc(&p->d_H, ((uint64_t)N * N + N) * sizeof(uint32_t)));
-                p->H_cap = (uint64_t)N * N + N;
-            }
+            PSCHK(dev_grow(p->d_H, p->H_cap, (uint64_t)N * N + N));
             uint32_t *rowcnt = p->d_H + (uint64_t)N * N;
             const uint32_t nt = (N + 63u) / 64u;
             acc_pair_inter_tiled_kernel<<<dim3(nt, nt), 256, 0, st>>>(p->I[p->cur], p->d_H, rowcnt, p->d);
@@ -2683,30 +2681,13 @@ static int core_davg_pack(ps_population *p, const uint32_t *d_slot, hipStream_t 
     const uint32_t N = (uint32_t)p->cfg.pop_size, rows = (uint32_t)p->cfg.ncols;
     const uint32_t WT = ((rows + 15u) / 16u + PS_PT_WB - 1u) / PS_PT_WB * PS_PT_WB;
     const uint64_t need = (uint64_t)((N + 31u) / 32u * 32u) * WT;
-    if (p->pack2_cap < need) {
-        if (p->d_pack2) HIPCHK(hipFree(p->d_pack2));
-        p->d_pack2 = nullptr;
-        p->pack2_cap = 0;
-        HIPCHK(hipMalloc(&p->d_pack2, need * sizeof(uint32_t)));
-        p->pack2_cap = need;
-    }
+    PSCHK(dev_grow(p->d_pack2, p->pack2_cap, need));
     const uint64_t ptiles = (uint64_t)((N + PS_PT_IB - 1u) / PS_PT_IB) * (WT / PS_PT_WB);
     if (ptiles > 0x7FFFFFFFull) return ps_fail(PS_ERR_INVALID, "matrix too large for the transposed distance form");
     if (d_slot) core_packT_kernel<false, true, false, true><<<dim3((uint32_t)ptiles), 256, 0, st>>>(p->state, N, p->pitch, rows, p->d_pack2, WT, d_slot);
     else core_packT_kernel<false, true><<<dim3((uint32_t)ptiles), 256, 0, st>>>(p->state, N, p->pitch, rows, p->d_pack2, WT);
     HIPCHK(hipGetLastError());
     *WT_out = WT;
-    return PS_OK;
-}
-
-static int ensure_H(ps_population *p, uint64_t words)
-{
-    if (p->H_cap >= words) return PS_OK;
-    if (p->d_H) HIPCHK(hipFree(p->d_H));
-    p->d_H = nullptr;
-    p->H_cap = 0;
-    HIPCHK(hipMalloc(&p->d_H, words * sizeof(uint32_t)));
-    p->H_cap = words;
     return PS_OK;
 }
 
@@ -2724,7 +2705,7 @@ static int core_davg_whole(ps_population *p, bool onehot, const uint32_t *d_slot
         uint32_t ranges = mfma_allpairs_ranges(N, n_chunks, tile_pairs);
         const uint32_t cpr = (n_chunks + ranges - 1u) / ranges;
         ranges = (n_chunks + cpr - 1u) / cpr;
-        PSCHK(ensure_H(p, (uint64_t)N * N * ranges));
+        PSCHK(dev_grow(p->d_H, p->H_cap, (uint64_t)N * N * ranges));
         const uint32_t lds = 256u * 16u * 16u;
         // (FP4 while a range holds fewer than 2^24 sites -- exact f32 sums --, else the i8 form: exact i32)
         if ((uint64_t)cpr * PS_MF_CHUNK_DW * 16u < (1u << 24)) {
@@ -2739,7 +2720,7 @@ static int core_davg_whole(ps_population *p, bool onehot, const uint32_t *d_slot
     } else {
         const uint32_t WA = 32u, ntile = (N + 127u) / 128u;
         const uint32_t lds = 2u * 128u * ((WA >> 2) + 1u) * 16u;
-        PSCHK(ensure_H(p, (uint64_t)N * N));
+        PSCHK(dev_grow(p->d_H, p->H_cap, (uint64_t)N * N));
         HIPCHK(hipMemsetAsync(p->d_H, 0, (uint64_t)N * N * sizeof(uint32_t), st));
         const uint32_t tile_pairs = ntile * (ntile + 1u) / 2u;
         const uint32_t n_chunks = (rows + WA * 8u - 1u) / (WA * 8u);
@@ -2775,13 +2756,7 @@ static int core_davg_prepare(ps_population *p, const core_davg_bands &b, bool fp
         o->ranges = (o->n_chunks + o->cpr - 1u) / o->cpr;
     }
     const uint64_t need = slice * o->ranges;
-    if (p->cdavg_cap < need) {
-        if (p->d_cdavg) HIPCHK(hipFree(p->d_cdavg));
-        p->d_cdavg = nullptr;
-        p->cdavg_cap = 0;
-        HIPCHK(hipMalloc(&p->d_cdavg, need * sizeof(uint32_t)));
-        p->cdavg_cap = need;
-    }
+    PSCHK(dev_grow(p->d_cdavg, p->cdavg_cap, need));
     return PS_OK;
 }
 
@@ -2834,29 +2809,22 @@ static int core_davg_form_of(const ps_population *p, uint64_t count)
     }
 }
 
-// rows [first, first + count) of the core D-avg of this handle (all sites: ncols == global_cols) into d_out (count values)
-static int core_average_distance_device(ps_population *p, uint64_t first, uint64_t count, double *d_out, hipStream_t st)
+static int core_davg_banded(ps_population *p, uint64_t first, uint64_t count, double *d_out);      // (behind core_band_source)
+
+// rows [first, first + count) of the core D-avg of this handle (all sites: ncols == global_cols) into d_out (count values), on
+// p->stream
+static int core_average_distance_device(ps_population *p, uint64_t first, uint64_t count, double *d_out)
 {
     const uint32_t N = (uint32_t)p->cfg.pop_size;
-    const double L = (double)p->cfg.global_cols;
     const uint32_t *slot = nullptr;
     PSCHK(rows_current(p, &slot));
     const uint32_t *d_slot = slot ? p->d_row_slot : nullptr;
-    int form = core_davg_form_of(p, count);
     // (form 3 on a one-hot matrix is the generic path as well: the tests force it)
-    const bool onehot = p->onehot_safe && p->cfg.ncols > 0;
-    if (form == 1) return core_davg_whole(p, true, d_slot, first, count, d_out, st);
+    const int form = core_davg_form_of(p, count);
+    if (form == 1) return core_davg_whole(p, true, d_slot, first, count, d_out, p->stream);
     if (form == 3 && p->nibble_safe && !d_slot && p->cfg.ncols > 0 && (uint64_t)N * N * 4 <= (8ull << 30))
-        return core_davg_whole(p, false, nullptr, first, count, d_out, st);
-    const core_davg_bands b = core_davg_plan_bands(p, first, count);
-    core_davg_src src;
-    PSCHK(core_davg_prepare(p, b, onehot && form == 2, d_slot, st, &src));
-    for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) {
-        const uint32_t nrows = std::min(b.band, b.c_end - lo);
-        PSCHK(core_davg_band_counts(p, src, b, lo, nrows, st));
-        PSCHK(core_davg_band_fold(p->d_cdavg, b, N, lo, nrows, first, L, d_out, st));
-    }
-    return PS_OK;
+        return core_davg_whole(p, false, nullptr, first, count, d_out, p->stream);
+    return core_davg_banded(p, first, count, d_out);
 }
 
 static int core_davg_check(const ps_population *p)
@@ -2872,12 +2840,11 @@ static int core_davg_check(const ps_population *p)
 static int core_average_distance_rows(ps_population *p, uint64_t first, uint64_t count, double *out)
 {
     PSCHK(use_device(p));
-    double *d_out = nullptr;
-    HIPCHK(hipMalloc(&d_out, count * sizeof(double)));
-    PSCHK(core_average_distance_device(p, first, count, d_out, p->stream));
-    HIPCHK(hipMemcpyAsync(out, d_out, count * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    dev_tmp<double> d_out;
+    PSCHK(d_out.alloc(count));
+    PSCHK(core_average_distance_device(p, first, count, d_out.p));
+    HIPCHK(hipMemcpyAsync(out, d_out.p, count * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
-    HIPCHK(hipFree(d_out));
     return PS_OK;
 }
 
@@ -2890,13 +2857,12 @@ extern "C" int ps_average_distance(ps_population *p, double *out)
     }
     if (p->cfg.pop_size < 2) return ps_fail(PS_ERR_INVALID, "average_distance needs pop_size >= 2");
     PSCHK(use_device(p));
-    double *d_out = nullptr;
+    dev_tmp<double> d_out;
     const uint64_t N = p->cfg.pop_size;
-    HIPCHK(hipMalloc(&d_out, N * sizeof(double)));
-    PSCHK(average_distance_device(p, d_out, p->stream));
-    HIPCHK(hipMemcpyAsync(out, d_out, N * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    PSCHK(d_out.alloc(N));
+    PSCHK(average_distance_device(p, d_out.p, p->stream));
+    HIPCHK(hipMemcpyAsync(out, d_out.p, N * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
-    HIPCHK(hipFree(d_out));
     const uint32_t *slot = nullptr;
     PSCHK(rows_current(p, &slot));
     rows_permute(out, slot, N);
@@ -2923,12 +2889,11 @@ extern "C" int ps_average_distance_rows(ps_population *p, uint64_t first, uint64
         return PS_OK;
     }
     PSCHK(use_device(p));
-    double *d_out = nullptr;
-    HIPCHK(hipMalloc(&d_out, N * sizeof(double)));
-    PSCHK(average_distance_device(p, d_out, p->stream, first, count));
-    HIPCHK(hipMemcpyAsync(out, d_out + first, count * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    dev_tmp<double> d_out;
+    PSCHK(d_out.alloc(N));
+    PSCHK(average_distance_device(p, d_out.p, p->stream, first, count));
+    HIPCHK(hipMemcpyAsync(out, d_out.p + first, count * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
-    HIPCHK(hipFree(d_out));
     return PS_OK;
 }
 
@@ -4050,13 +4015,7 @@ static int emulated_exchange(void *ctx, void *d_words, uint64_t n_words, void *h
 {
     ps_sim *s = (ps_sim *)ctx;
     const uint64_t bytes = n_words * 8;
-    if (s->emu_cap < bytes) {
-        if (s->emu_buf) HIPCHK(hipFree(s->emu_buf));
-        s->emu_buf = nullptr;
-        s->emu_cap = 0;
-        HIPCHK(hipMalloc(&s->emu_buf, bytes));
-        s->emu_cap = bytes;
-    }
+    PSCHK(dev_grow(s->emu_buf, s->emu_cap, bytes));
     if (s->emu_clock_khz == 0) {
         int khz = 0, dev = 0;
         HIPCHK(hipGetDevice(&dev));
@@ -4765,75 +4724,125 @@ extern "C" int ps_multi_pairwise_distances(ps_multi *m, double *core_out, double
     return ps_pairwise_distances(s0->acc, P, s0->r1.data(), s0->r2.data(), acc_out);
 }
 
-// Population::average_distance (population.rs:753-784) of the run's core matrix (core != 0) or of its accessory matrix.  Core:
-// band by band, every shard counts its own sites (in output order, through its own row slot), shard 0's device adds the
-// shards' counts as multi_core_counts adds the pair numerators and folds with L = core_size.  The tuning keys
-// of shard 0's core handle apply.  Accessory: the replicas are identical, shard 0's handle answers.
-extern "C" int ps_multi_average_distance(ps_multi *m, int core, double *out)
-{
-    if (!m || !out) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (!core) return ps_average_distance(m->shard[0]->acc, out);
-    const size_t K = m->shard.size();
-    if (K == 1) return ps_average_distance(m->shard[0]->core, out);
-    ps_population *c0 = m->shard[0]->core;
-    const uint32_t N = (uint32_t)m->prm.pop_size;
-    if (N < 2) return ps_fail(PS_ERR_INVALID, "average_distance needs pop_size >= 2");
-    PSCHK(ps_multi_sync(m));
-    const core_davg_bands b = core_davg_plan_bands(c0, 0, N);
-    // (one-hot on every shard: the banded FP4 form on each; otherwise the generic kernel on each)
-    bool onehot = true;
-    for (size_t k = 0; k < K; k++) onehot = onehot && m->shard[k]->core->onehot_safe && c0->core_davg_form != 3;
-    std::vector<core_davg_src> src(K);
-    PSCHK(multi_for_each(m, [&](size_t k) {
-        ps_population *c = m->shard[k]->core;
-        PSCHK(use_device(c));
-        const uint32_t *slot = nullptr;
-        PSCHK(rows_current(c, &slot));
-        return core_davg_prepare(c, b, onehot, slot ? c->d_row_slot : nullptr, c->stream, &src[k]);
-    }));
-    PSCHK(use_device(c0));
-    double *d_out = nullptr;
-    uint32_t *d_land = nullptr;         // (without peer access: a peer's band counts copied over first)
-    HIPCHK(hipMalloc(&d_out, (uint64_t)N * sizeof(double)));
-    if (!m->peers_ok) HIPCHK(hipMalloc(&d_land, (uint64_t)b.band * b.ld * sizeof(uint32_t)));
-    int rc = PS_OK;
-    for (uint32_t lo = b.c0; rc == PS_OK && lo < b.c_end; lo += b.band) {
-        const uint32_t nrows = std::min(b.band, b.c_end - lo);
+// The band counts of the banded all-pairs read-outs (core D-avg, distance histogram, strain clusters): h(i, j) over ALL core
+// sites for the rows of one band after another, from one handle that holds all sites (m == nullptr) or from the site shards of
+// a run.  Sharded: every shard counts its own sites, shard 0's device adds the shards' counts into its own (where they are with
+// peer access, through the landing buffer without).  The tuning keys of c0 (shard 0's core handle) apply.
+struct core_band_source {
+    ps_population *c0 = nullptr;
+    ps_multi *m = nullptr;
+    core_davg_bands b{};
+    std::vector<core_davg_src> src;
+    dev_tmp<uint32_t> land;             // (without peer access: a peer's band counts copied over first)
+
+    ps_population *core(size_t k) const { return m ? m->shard[k]->core : c0; }
+
+    // Rows [first, first + count) in bands.  output_order: every handle counts through its own row slot (D-avg), else in
+    // internal order (histogram, clusters).  prepare == false: the bands only, counts() is not called.  Everything queued on
+    // the handles before is complete or ordered on their streams (the caller's business).
+    int open(ps_population *core0, ps_multi *multi, uint64_t first, uint64_t count, bool output_order, bool prepare = true)
+    {
+        c0 = core0;
+        m = multi;
+        const size_t K = m ? m->shard.size() : 1;
+        b = core_davg_plan_bands(c0, first, count);
+        src.assign(K, core_davg_src{});
+        if (!prepare) return PS_OK;
+        // (one-hot on every shard: the banded FP4 form on each; otherwise -- and with form 3 forced -- the generic kernel on each)
+        bool onehot = c0->core_davg_form != 3;
+        for (size_t k = 0; k < K; k++) onehot = onehot && core(k)->onehot_safe;
+        auto prep = [&](size_t k) -> int {
+            ps_population *c = core(k);
+            PSCHK(use_device(c));
+            const uint32_t *slot = nullptr;
+            if (output_order) PSCHK(rows_current(c, &slot));
+            return core_davg_prepare(c, b, onehot, slot ? c->d_row_slot : nullptr, c->stream, &src[k]);
+        };
+        if (!m) return prep(0);
+        PSCHK(multi_for_each(m, prep));
+        PSCHK(use_device(c0));
+        if (!m->peers_ok) PSCHK(land.alloc((uint64_t)b.band * b.ld));
+        return PS_OK;
+    }
+
+    // h(i, j) of the rows [lo, lo + nrows) in c0->d_cdavg (row pitch b.ld), ordered on c0->stream
+    int counts(uint32_t lo, uint32_t nrows)
+    {
+        if (!m) return core_davg_band_counts(c0, src[0], b, lo, nrows, c0->stream);
         const uint64_t n = (uint64_t)nrows * b.ld;
-        rc = multi_for_each(m, [&](size_t k) {
-            ps_population *c = m->shard[k]->core;
+        // (the last kernel that reads shard 0's counts has finished before any shard overwrites its own)
+        PSCHK(use_device(c0));
+        HIPCHK(hipStreamSynchronize(c0->stream));
+        PSCHK(multi_for_each(m, [&](size_t k) {
+            ps_population *c = core(k);
             PSCHK(use_device(c));
             PSCHK(core_davg_band_counts(c, src[k], b, lo, nrows, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
             return (int)PS_OK;
-        });
-        if (rc != PS_OK) break;
-        rc = [&]() -> int {
-            PSCHK(use_device(c0));
-            for (size_t k = 1; k < K; k++) {
-                ps_population *c = m->shard[k]->core;
-                if (m->peers_ok) {
-                    u32_add_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, c0->stream>>>(c0->d_cdavg, c->d_cdavg, n);
-                } else {
-                    HIPCHK(hipMemcpyPeerAsync(d_land, c0->device, c->d_cdavg, c->device, n * sizeof(uint32_t), c0->stream));
-                    u32_add_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, c0->stream>>>(c0->d_cdavg, d_land, n);
-                }
-                HIPCHK(hipGetLastError());
-            }
-            PSCHK(core_davg_band_fold(c0->d_cdavg, b, N, lo, nrows, 0, (double)m->prm.core_size, d_out, c0->stream));
-            // (the shards' counts are read: the next band may overwrite them)
-            HIPCHK(hipStreamSynchronize(c0->stream));
-            return PS_OK;
-        }();
-    }
-    if (rc == PS_OK) {
+        }));
         PSCHK(use_device(c0));
-        HIPCHK(hipMemcpy(out, d_out, (uint64_t)N * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t k = 1; k < m->shard.size(); k++) {
+            ps_population *c = core(k);
+            if (m->peers_ok) {
+                u32_add_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, c0->stream>>>(c0->d_cdavg, c->d_cdavg, n);
+            } else {
+                HIPCHK(hipMemcpyPeerAsync(land.p, c0->device, c->d_cdavg, c->device, n * sizeof(uint32_t), c0->stream));
+                u32_add_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, c0->stream>>>(c0->d_cdavg, land.p, n);
+            }
+            HIPCHK(hipGetLastError());
+        }
+        return PS_OK;
     }
-    (void)hipSetDevice(c0->device);
-    (void)hipFree(d_out);
-    if (d_land) (void)hipFree(d_land);
-    return rc;
+
+    // sharded: nothing on shard 0's stream still reads the shards' counts or the landing buffer (freed behind this)
+    ~core_band_source()
+    {
+        if (!m) return;
+        (void)hipSetDevice(c0->device);
+        (void)hipStreamSynchronize(c0->stream);
+    }
+};
+
+// the banded forms of the core D-avg: the counts of a band, then its rows of the call's [first, ...) folded with L = all sites
+static int core_davg_fold_bands(core_band_source &src, uint64_t first, double L, double *d_out)
+{
+    ps_population *c0 = src.c0;
+    const core_davg_bands &b = src.b;
+    for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) {
+        const uint32_t nrows = std::min(b.band, b.c_end - lo);
+        PSCHK(src.counts(lo, nrows));
+        PSCHK(core_davg_band_fold(c0->d_cdavg, b, (uint32_t)c0->cfg.pop_size, lo, nrows, first, L, d_out, c0->stream));
+    }
+    return PS_OK;
+}
+
+static int core_davg_banded(ps_population *p, uint64_t first, uint64_t count, double *d_out)
+{
+    core_band_source src;
+    PSCHK(src.open(p, nullptr, first, count, true));
+    return core_davg_fold_bands(src, first, (double)p->cfg.global_cols, d_out);
+}
+
+// Population::average_distance (population.rs:753-784) of the run's core matrix (core != 0) or of its accessory matrix.  Core:
+// band by band through core_band_source, in output order, folded with L = core_size.  The tuning keys of
+// shard 0's core handle apply.  Accessory: the replicas are identical, shard 0's handle answers.
+extern "C" int ps_multi_average_distance(ps_multi *m, int core, double *out)
+{
+    if (!m || !out) return ps_fail(PS_ERR_INVALID, "null argument");
+    if (!core) return ps_average_distance(m->shard[0]->acc, out);
+    if (m->shard.size() == 1) return ps_average_distance(m->shard[0]->core, out);
+    ps_population *c0 = m->shard[0]->core;
+    const uint32_t N = (uint32_t)m->prm.pop_size;
+    if (N < 2) return ps_fail(PS_ERR_INVALID, "average_distance needs pop_size >= 2");
+    PSCHK(ps_multi_sync(m));
+    dev_tmp<double> d_out;      // (declared first: freed behind the source's last synchronisation)
+    core_band_source src;
+    PSCHK(src.open(c0, m, 0, N, true));
+    PSCHK(d_out.alloc(N));
+    PSCHK(core_davg_fold_bands(src, 0, (double)m->prm.core_size, d_out.p));
+    HIPCHK(hipMemcpyAsync(out, d_out.p, (uint64_t)N * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+    HIPCHK(hipStreamSynchronize(c0->stream));
+    return PS_OK;
 }
 
 // Population::write for both matrices (main.rs:550-553): every line of <outpref>_core_genome.csv is the

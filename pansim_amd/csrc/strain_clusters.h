@@ -1,6 +1,6 @@
 // strain_clusters.h -- ps_strain_clusters / ps_sim_strain_clusters / ps_multi_strain_clusters and the host restatement
 // ps_clusters_from_counts (include/pansim_hip.h; the definitions: docs/STRAIN_CLUSTERS.md).  Included by pansim_capi.hip
-// behind pair_histogram.h, whose band plan, count phases and stream ordering it reuses as they are.
+// behind pair_histogram.h, whose band source, count phases and stream ordering (pair_pipeline) it reuses as they are.
 //
 // As the histogram, everything on the device runs in INTERNAL row order: per band the core numerators on the core stream,
 // the accessory intersections on the accessory stream, pair_edge_kernel on the core stream behind both; after the last band
@@ -105,17 +105,13 @@ static int cluster_scratch(ps_population *c0, uint64_t N, unsigned long long **w
 {
     const uint64_t W = (N + 63) / 64, head = (PS_CL_WORDS + 1) * 8, lab = (N * 4 + 7) & ~7ull;
     const uint64_t need = head + lab + N * W * 8;
-    if (c0->cl_cap < need) {
-        if (c0->d_cl) HIPCHK(hipFree(c0->d_cl));
-        c0->d_cl = nullptr;
-        c0->cl_cap = 0;
-        if (hipMalloc(&c0->d_cl, need) != hipSuccess) {
-            (void)hipGetLastError();
-            return ps_fail(PS_ERR_OOM, "cannot allocate the %llu bytes of the adjacency bit matrix and the labels of %llu individuals",
-                           (unsigned long long)need, (unsigned long long)N);
-        }
-        c0->cl_cap = need;
+    const hipError_t e = dev_grow_err(c0->d_cl, c0->cl_cap, need);
+    if (e != hipSuccess && !c0->d_cl) {
+        (void)hipGetLastError();
+        return ps_fail(PS_ERR_OOM, "cannot allocate the %llu bytes of the adjacency bit matrix and the labels of %llu individuals",
+                       (unsigned long long)need, (unsigned long long)N);
     }
+    HIPCHK(e);
     uint8_t *base = (uint8_t *)c0->d_cl;
     *words = (unsigned long long *)base;
     *changed = (uint32_t *)(base + PS_CL_WORDS * 8);
@@ -126,81 +122,57 @@ static int cluster_scratch(ps_population *c0, uint64_t N, unsigned long long **w
 }
 
 template <bool CORE, bool ACC>
-static int cluster_edge_launch(const ps_population *c0, const core_davg_bands &b, const pair_hist_acc &A, uint32_t lo, uint32_t nrows,
-                               const ps_cl_args &a, unsigned long long *adj, unsigned long long *words, hipStream_t st)
+static int cluster_edge_launch(const pair_pipeline &pl, uint32_t lo, uint32_t nrows, const ps_cl_args &a, unsigned long long *adj,
+                               unsigned long long *words)
 {
-    const uint32_t N = (uint32_t)c0->cfg.pop_size;
-    // four waves per workgroup over the row's chunks, the rows over y (the grid of pair_hist_launch without bins in LDS)
-    const uint32_t nchunk = (N + 255u) / 256u, gx = std::max(1u, std::min((nchunk + 3u) / 4u, 8u));
-    const uint32_t gy = std::max(1u, std::min(std::min(nrows, 65535u), 2048u / gx));
-    hipLaunchKernelGGL((pair_edge_kernel<CORE, ACC>), dim3(gx, gy), dim3(256), 0, st, (const uint32_t *)c0->d_cdavg, b.ld,
-                       (const uint16_t *)A.In, A.ld, (const uint32_t *)A.rowcnt, N, lo, nrows, a, adj, words);
+    const uint32_t N = (uint32_t)pl.c0->cfg.pop_size;
+    // the rows over y (the grid of pair_hist_launch without bins in LDS)
+    const uint32_t gx = pair_grid_x(N), gy = std::max(1u, std::min(std::min(nrows, 65535u), 2048u / gx));
+    hipLaunchKernelGGL((pair_edge_kernel<CORE, ACC>), dim3(gx, gy), dim3(256), 0, pl.sc, (const uint32_t *)pl.c0->d_cdavg, pl.src.b.ld, pl.In(),
+                       pl.A.ld, (const uint32_t *)pl.A.rowcnt, N, lo, nrows, a, adj, words);
     HIPCHK(hipGetLastError());
     return PS_OK;
 }
 
-// The call behind the three device entries.  With a core criterion, band_counts(lo, nrows) leaves h(i, j) over ALL core
-// sites for the rows of the band in c0->d_cdavg, ordered on c0->stream; without one it is not called.  `acc` lives on c0's
-// device.  Both streams are idle on entry; `slot` is c0's current row map (rows_current).
-template <class F>
-static int cluster_device(ps_population *c0, ps_population *acc, const core_davg_bands &b, uint64_t L, const ps_cluster_params *prm,
-                          const uint32_t *slot, F &&band_counts, ps_cluster_t *out, uint32_t *labels)
+// The call behind the device entries: src holds the bands (open in internal order with a core criterion; without one its counts
+// are not asked for), `acc` lives on src.c0's device, both streams are idle; `slot` is c0's current row map (rows_current).
+static int cluster_device(core_band_source &src, ps_population *acc, uint64_t L, const ps_cluster_params *prm, const uint32_t *slot,
+                          ps_cluster_t *out, uint32_t *labels)
 {
+    ps_population *c0 = src.c0;
+    const core_davg_bands &b = src.b;
     const uint32_t N = (uint32_t)c0->cfg.pop_size;
     const uint64_t cg = acc->cfg.core_genes;
     bool core_on, acc_on;
     PSCHK(cluster_check_params(prm, &core_on, &acc_on));
     const ps_cl_args a = cluster_args(prm, cg);
-    hipStream_t sc = c0->stream, sa = acc->stream;
     PSCHK(use_device(c0));
     unsigned long long *d_words, *d_adj;
     uint32_t *d_changed, *d_L;
     uint64_t bytes;
     PSCHK(cluster_scratch(c0, N, &d_words, &d_changed, &d_L, &d_adj, &bytes));
+    pair_pipeline pl(src, acc);
+    hipStream_t sc = pl.sc;
     HIPCHK(hipMemsetAsync(c0->d_cl, 0, bytes, sc));
     cluster_init_kernel<<<(N + 255u) / 256u, 256, 0, sc>>>(d_L, N);
     HIPCHK(hipGetLastError());
     c0->cl_timed = false;
-    pair_hist_acc A;
-    if (acc_on) PSCHK(pair_hist_acc_prepare(acc, b.band, sa, &A));
-    pair_hist_events evs;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> timers[3];      // counts, edges, labels
-    auto timed = [&](int which, hipStream_t st, auto &&work) -> int {
-        hipEvent_t e0, e1;
-        PSCHK(evs.make(&e0));
-        PSCHK(evs.make(&e1));
-        HIPCHK(hipEventRecord(e0, st));
-        PSCHK(work());
-        HIPCHK(hipEventRecord(e1, st));
-        timers[which].push_back({ e0, e1 });
-        return PS_OK;
-    };
-    hipEvent_t ev_acc = nullptr, ev_edge = nullptr;
-    PSCHK(evs.make(&ev_acc));
-    PSCHK(evs.make(&ev_edge));
-    // the accessory counts of a band on their stream, behind the last edge kernel that read the scratch; the edges behind them
-    bool edged_before = false;
+    PSCHK(pl.open(acc_on));
+    // timer groups: 0 = both count phases, 1 = the edges, 2 = the labels
     for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) {
         const uint32_t nrows = std::min(b.band, b.c_end - lo);
-        if (core_on) PSCHK(timed(0, sc, [&]() { return band_counts(lo, nrows); }));
-        if (A.In) {
-            if (edged_before) HIPCHK(hipStreamWaitEvent(sa, ev_edge, 0));
-            PSCHK(timed(0, sa, [&]() { return pair_hist_acc_band(A, lo, nrows, sa); }));
-            HIPCHK(hipEventRecord(ev_acc, sa));
-            HIPCHK(hipStreamWaitEvent(sc, ev_acc, 0));
-        }
-        PSCHK(timed(1, sc, [&]() {
-            return core_on && acc_on ? cluster_edge_launch<true, true>(c0, b, A, lo, nrows, a, d_adj, d_words, sc)
-                   : core_on         ? cluster_edge_launch<true, false>(c0, b, A, lo, nrows, a, d_adj, d_words, sc)
-                                     : cluster_edge_launch<false, true>(c0, b, A, lo, nrows, a, d_adj, d_words, sc);
+        if (core_on) PSCHK(pl.core_counts(0, lo, nrows));
+        PSCHK(pl.acc_counts(0, lo, nrows));
+        PSCHK(pl.consume(1, [&]() {
+            return core_on && acc_on ? cluster_edge_launch<true, true>(pl, lo, nrows, a, d_adj, d_words)
+                   : core_on         ? cluster_edge_launch<true, false>(pl, lo, nrows, a, d_adj, d_words)
+                                     : cluster_edge_launch<false, true>(pl, lo, nrows, a, d_adj, d_words);
         }));
-        HIPCHK(hipEventRecord(ev_edge, sc));
-        edged_before = true;
     }
     // the label rounds: labels only decrease and a label crosses at least one more edge per round, so a hook round that moves
     // nothing comes within N rounds
     uint64_t rounds = 0;
-    PSCHK(timed(2, sc, [&]() -> int {
+    PSCHK(pl.timed(2, sc, [&]() -> int {
         for (;;) {
             if (rounds == N) return ps_fail(PS_ERR_STATE, "the labels of %u individuals still moved in round %u", N, N);
             rounds++;
@@ -219,16 +191,9 @@ static int cluster_device(ps_population *c0, ps_population *acc, const core_davg
     std::vector<uint32_t> rep(N);
     HIPCHK(hipMemcpyAsync(w, d_words, sizeof w, hipMemcpyDeviceToHost, sc));
     HIPCHK(hipMemcpyAsync(rep.data(), d_L, (uint64_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost, sc));
-    HIPCHK(hipStreamSynchronize(sa));
+    HIPCHK(hipStreamSynchronize(pl.sa));
     HIPCHK(hipStreamSynchronize(sc));
-    for (int which = 0; which < 3; which++) {
-        c0->cl_ms[which] = 0.0;
-        for (const auto &e : timers[which]) {
-            float ms = 0.0f;
-            HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
-            c0->cl_ms[which] += (double)ms;
-        }
-    }
+    for (int which = 0; which < 3; which++) PSCHK(pl.total_ms(which, &c0->cl_ms[which]));
     c0->cl_timed = true;
     rows_permute(rep.data(), slot, N);
     memset(out, 0, sizeof *out);
@@ -243,30 +208,25 @@ static int cluster_device(ps_population *c0, ps_population *acc, const core_davg
     return PS_OK;
 }
 
+// ps_strain_clusters (m == nullptr) and ps_multi_strain_clusters (core, acc: shard 0's handles; the edges and the labels on
+// shard 0 against its accessory replica, the row map from shard 0's simulation)
+static int cluster_entry(ps_multi *m, ps_population *core, ps_population *acc, const ps_cluster_params *prm, ps_cluster_t *out,
+                         uint32_t *labels)
+{
+    bool core_on, acc_on;
+    PSCHK(cluster_check_params(prm, &core_on, &acc_on));
+    core_band_source src;
+    const uint32_t *slot = nullptr;
+    PSCHK(pair_source_open(&src, "strain_clusters", "strain clusters need", "compares", m, core, acc, core_on, &slot));
+    return cluster_device(src, acc, m ? m->prm.core_size : core->cfg.global_cols, prm, slot, out, labels);
+}
+
 extern "C" int ps_strain_clusters(ps_population *core, ps_population *acc, const ps_cluster_params *prm, ps_cluster_t *out,
                                   uint32_t *labels)
 {
     PSCHK(pair_hist_needs_device());
     if (!core || !acc || !prm || !out || !labels) return ps_fail(PS_ERR_INVALID, "null argument");
-    bool core_on, acc_on;
-    PSCHK(cluster_check_params(prm, &core_on, &acc_on));
-    PSCHK(pair_hist_handles(core, acc, "ps_strain_clusters", "strain clusters need"));
-    if (core->cfg.ncols != core->cfg.global_cols)
-        return ps_fail(PS_ERR_INVALID, "ps_strain_clusters compares over all %llu core sites; this handle is one site shard "
-                                       "([%llu, %llu)): use ps_multi_strain_clusters", (unsigned long long)core->cfg.global_cols,
-                       (unsigned long long)core->cfg.col_offset, (unsigned long long)(core->cfg.col_offset + core->cfg.ncols));
-    PSCHK(use_device(core));
-    const uint32_t *slot = nullptr;
-    PSCHK(rows_current(core, &slot));
-    // everything queued on either handle precedes the count kernels of both
-    HIPCHK(hipStreamSynchronize(acc->stream));
-    HIPCHK(hipStreamSynchronize(core->stream));
-    const uint32_t N = (uint32_t)core->cfg.pop_size;
-    const core_davg_bands b = core_davg_plan_bands(core, 0, N);
-    core_davg_src src{};
-    if (core_on) PSCHK(core_davg_prepare(core, b, core->onehot_safe && core->core_davg_form != 3, nullptr, core->stream, &src));
-    return cluster_device(core, acc, b, core->cfg.global_cols, prm, slot,
-                          [&](uint32_t lo, uint32_t nrows) { return core_davg_band_counts(core, src, b, lo, nrows, core->stream); }, out, labels);
+    return cluster_entry(nullptr, core, acc, prm, out, labels);
 }
 
 extern "C" int ps_sim_strain_clusters(ps_sim *s, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels)
@@ -286,40 +246,10 @@ extern "C" int ps_strain_clusters_timing(ps_population *core, double *counts_ms,
     return PS_OK;
 }
 
-// As ps_multi_distance_histogram: band by band the shards' counts are added on shard 0 (multi_band_counts); the edges and the
-// labels on shard 0 against its accessory replica, the row map from shard 0's simulation.
 extern "C" int ps_multi_strain_clusters(ps_multi *m, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels)
 {
     PSCHK(pair_hist_needs_device());
     if (!m || !prm || !out || !labels) return ps_fail(PS_ERR_INVALID, "null argument");
-    const size_t K = m->shard.size();
-    if (K == 1) return ps_sim_strain_clusters(m->shard[0], prm, out, labels);
-    bool core_on, acc_on;
-    PSCHK(cluster_check_params(prm, &core_on, &acc_on));
-    ps_population *c0 = m->shard[0]->core, *acc = m->shard[0]->acc;
-    PSCHK(pair_hist_handles(c0, acc, "ps_multi_strain_clusters", "strain clusters need"));
-    const uint32_t N = (uint32_t)m->prm.pop_size;
-    const uint32_t *slot = nullptr;
-    PSCHK(use_device(c0));
-    PSCHK(rows_current(c0, &slot));
-    PSCHK(ps_multi_sync(m));
-    const core_davg_bands b = core_davg_plan_bands(c0, 0, N);
-    bool onehot = true;
-    for (size_t k = 0; k < K; k++) onehot = onehot && m->shard[k]->core->onehot_safe && c0->core_davg_form != 3;
-    std::vector<core_davg_src> src(K);
-    if (core_on)
-        PSCHK(multi_for_each(m, [&](size_t k) {
-            ps_population *c = m->shard[k]->core;
-            PSCHK(use_device(c));
-            return core_davg_prepare(c, b, onehot, nullptr, c->stream, &src[k]);
-        }));
-    PSCHK(use_device(c0));
-    uint32_t *d_land = nullptr;         // (without peer access: a peer's band counts copied over first)
-    if (core_on && !m->peers_ok) HIPCHK(hipMalloc(&d_land, (uint64_t)b.band * b.ld * sizeof(uint32_t)));
-    auto band_counts = [&](uint32_t lo, uint32_t nrows) { return multi_band_counts(m, src, b, d_land, lo, nrows); };
-    const int rc = cluster_device(c0, acc, b, m->prm.core_size, prm, slot, band_counts, out, labels);
-    (void)hipSetDevice(c0->device);
-    (void)hipStreamSynchronize(c0->stream);
-    if (d_land) (void)hipFree(d_land);
-    return rc;
+    if (m->shard.size() == 1) return ps_sim_strain_clusters(m->shard[0], prm, out, labels);
+    return cluster_entry(m, m->shard[0]->core, m->shard[0]->acc, prm, out, labels);
 }

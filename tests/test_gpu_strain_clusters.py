@@ -249,7 +249,33 @@ def test_multi_simulation_equals_the_unsharded_run(pa, sim_after_five):
     multi.close()
 
 
-CLI = dict(pop_size=100, core_size=300, pan_genes=600, core_genes=200, n_gen=4, seed=9, max_distances=500, HR_rate=0.5)
+def test_multi_simulation_over_two_bands(pa):
+    """N = 300 in two site shards with core_davg_band = 256 on shard 0: two bands (256 + 44 rows), each one the sum of both
+    shards' counts.  Against the unsharded run (one band) and the union-find over the matrices it reads back; the core
+    threshold is the lowest tenth of the host's own distances, so some pairs are edges and some are not."""
+    kw = dict(SIM, pop_size=300, seed=12)
+    sim = pa.Simulation(pa.make_params(**kw))
+    sim.run(4)
+    nums = host_numerators(sim.core_genome.read_matrix(), sim.pan_genome.read_matrix())
+    d = np.sort(nums[2] // 2)
+    core_max_d = int(d[d.size // 10])
+    multi = pa.MultiSimulation(pa.make_params(**kw), 2, devices=[0, 0])
+    multi.shards[0].core_genome.set_tuning("core_davg_band", 256)
+    multi.run(4)
+    for acc_max in (None, 0.5):
+        crit = dict(core_max_d=core_max_d, acc_max=acc_max)
+        got = multi.strain_clusters(**crit)
+        _, num, den = ref.thresholds(2000, None, acc_max)
+        ref.assert_equal(got, ref.clusters(*nums, 300, 2000, 20, core_max_d, num, den), 300)
+        one = sim.strain_clusters(**crit)
+        assert np.array_equal(got.labels, one.labels) and got.edges == one.edges
+        if acc_max is None:
+            assert 0 < got.edges < got.pairs == 300 * 299 // 2
+    sim.close()
+    multi.close()
+
+
+CLI = dict(pop_size=100,core_size=300, pan_genes=600, core_genes=200, n_gen=4, seed=9, max_distances=500, HR_rate=0.5)
 CLI_CORE_MAX, CLI_ACC_MAX = 0.2, 0.4
 USUAL = (".tsv", "_freqs.txt", "_core_genome.csv", "_pangenome.csv", "_per_gen.tsv", "_selection.tsv")
 
