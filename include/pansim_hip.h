@@ -589,6 +589,55 @@ int ps_clusters_from_counts(const uint32_t *r1, const uint32_t *r2, const uint32
  * (host round trips included).  PS_ERR_STATE before any call. */
 int ps_strain_clusters_timing(ps_population *core, double *counts_ms, double *edges_ms, double *labels_ms);
 
+/* Single-linkage tree: the minimum spanning tree of the complete graph over ALL N individuals under one distance
+ * (docs/LINKAGE_TREE.md) -- the single-linkage dendrogram, whose N - 1 sorted edge weights are the merge heights; cutting it at
+ * any threshold gives the labels of ps_strain_clusters at that threshold.  The reference has no such function: it writes a
+ * SAMPLE of pairs as text (population.rs:787-837), and a sample cannot give a spanning tree.  Per pair i < j, in integers, with
+ * the numerators of the distance histogram: core metric num = d = h / 2, den = core sites; accessory metric num = a = U - I,
+ * den = b = U + core_genes, a pair with b == 0 (the reference's NaN) reported as 0 / 0, above every defined distance and equal
+ * to every other undefined one.  Two distances compare by num1 den2 against num2 den1 in u64 (equal denominators: by the
+ * numerators); no floating point.  Edges are ordered by (distance, lo, hi), lo < hi rows of the reference's row order: the order
+ * is strict, the tree is unique and does not depend on the launch geometry.  The accessory metric needs at most 65535 accessory
+ * genes and core_genes + 65535 < 2^32, else PS_ERR_INVALID. */
+#define PS_TREE_CORE 0
+#define PS_TREE_ACC 1
+typedef struct {
+    int32_t metric;                    /* PS_TREE_CORE or PS_TREE_ACC */
+} ps_tree_params;
+typedef struct {
+    uint64_t pop_size, pairs, core_sites, core_genes;      /* pairs: all N (N - 1) / 2, or the list's length from ps_tree_from_counts */
+    uint64_t metric;
+    uint64_t edges;                    /* pop_size - 1, or fewer from a list that leaves a forest */
+    uint64_t undefined_edges;          /* tree edges with den == 0 */
+    uint64_t distinct_heights;         /* distinct distances among the edges */
+    uint64_t rounds;                   /* Boruvka rounds taken on the device (informational; 0 from ps_tree_from_counts) */
+} ps_tree_t;
+/* All pairs of two handles of equal pop_size >= 2 on one device (the reference has no such function; population.rs:787-837
+ * writes a sample): `core` a core handle that holds all sites, `acc` an accessory handle of at most 65535 genes (required; with
+ * the core metric none of its kernels is launched).  lo, hi, num, den: pop_size - 1 values each, in ascending order of
+ * (distance, lo, hi).  Ordered behind all queued work of BOTH handles; changes no state.  PS_ERR_NO_DEVICE before anything
+ * else when no GPU is visible. */
+int ps_linkage_tree(ps_population *core, ps_population *acc, const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi,
+                    uint64_t *num, uint64_t *den);
+/* The same for the two matrices of a simulation (the reference has no such function; population.rs:787-837); a site shard
+ * fails with a message that points to ps_multi_linkage_tree */
+int ps_sim_linkage_tree(ps_sim *s, const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi, uint64_t *num, uint64_t *den);
+/* The same for a sharded run (the reference has no such function; population.rs:787-837): every shard counts its own sites
+ * band by band, shard 0 adds them, keeps them and runs the rounds against its accessory replica */
+int ps_multi_linkage_tree(ps_multi *m, const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi, uint64_t *num, uint64_t *den);
+/* The same order on the host alone (no device is touched, as ps_clusters_from_counts; the reference has no such function;
+ * population.rs:787-837): Kruskal over any list of pairs (r1[k], r2[k]) with their numerators (those of the other metric may
+ * be NULL), in the list's own index space.  Duplicate pairs are allowed; a list that does not connect all of pop_size gives
+ * the minimum spanning forest, out->edges < pop_size - 1 (the arrays still have room for pop_size - 1).  An index >= pop_size,
+ * r1[k] == r2[k] or, under the accessory metric, an intersection above its union or a union above 65535 is PS_ERR_INVALID. */
+int ps_tree_from_counts(const uint32_t *r1, const uint32_t *r2, const uint32_t *core_h, const uint32_t *acc_inter,
+                        const uint32_t *acc_union, uint64_t n_pairs, uint64_t pop_size, uint64_t core_sites, uint64_t core_genes,
+                        const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi, uint64_t *num, uint64_t *den);
+/* device ms of the last ps_linkage_tree on this core handle (HIP events; the reference has no such function;
+ * population.rs:787-837): the count kernels of the metric, the store kernels, the rounds (host round trips included).
+ * PS_ERR_STATE before any call. */
+int ps_linkage_tree_timing(ps_population *core, double *counts_ms, double *store_ms, double *rounds_ms);
+
 #ifdef __cplusplus
 }
 #endif

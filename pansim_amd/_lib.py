@@ -95,6 +95,20 @@ class Clusters(C.Structure):
                                                  "largest_cluster", "within_pairs", "undefined_pairs", "rounds")]
 
 
+PS_TREE_CORE, PS_TREE_ACC = 0, 1
+
+
+class TreeParams(C.Structure):
+    """ps_tree_params: the metric of ps_linkage_tree (docs/LINKAGE_TREE.md), PS_TREE_CORE or PS_TREE_ACC"""
+    _fields_ = [("metric", C.c_int32)]
+
+
+class Tree(C.Structure):
+    """ps_tree_t: the summary of ps_linkage_tree / ps_tree_from_counts"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "pairs", "core_sites", "core_genes", "metric", "edges", "undefined_edges",
+                                                 "distinct_heights", "rounds")]
+
+
 # every symbol include/pansim_hip.h declares (tests/test_host_logic.py::test_library_exports_every_declared_symbol checks the header against this)
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -205,6 +219,11 @@ SIGNATURES = {
     "ps_multi_strain_clusters": (_int, [_vp, C.POINTER(ClusterParams), C.POINTER(Clusters), _vp]),
     "ps_clusters_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(ClusterParams), C.POINTER(Clusters), _vp]),
     "ps_strain_clusters_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_linkage_tree": (_int, [_vp, _vp, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
+    "ps_sim_linkage_tree": (_int, [_vp, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
+    "ps_multi_linkage_tree": (_int, [_vp, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
+    "ps_tree_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
+    "ps_linkage_tree_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

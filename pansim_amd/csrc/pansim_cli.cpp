@@ -58,6 +58,8 @@ static const Flag EXT_FLAGS[] = {
     { "print_clusters", "Write the strain clusters of the final population -- the connected components over ALL pairs of the graph that joins two individuals when their core distance is at most --cluster_core_max and their accessory distance at most --cluster_acc_max -- to <outpref>_clusters.tsv (row, label per individual: the label is the smallest row of its cluster) and their summary to <outpref>_clusters_summary.tsv (docs/STRAIN_CLUSTERS.md), beside the usual outputs. Needs at least one of the two thresholds.", nullptr, false },
     { "cluster_core_max", "Largest core distance of a pair that --print_clusters joins. Must be >= 0.0. Without it the core distance is not looked at.", "", true },
     { "cluster_acc_max", "Largest accessory distance of a pair that --print_clusters joins. Must be 0.0 <= X <= 1.0. Without it the accessory distance is not looked at.", "", true },
+    { "print_tree", "Write the single-linkage tree of the final population -- the minimum spanning tree over ALL pairs under the distance chosen by --tree_metric, whose sorted edge weights are the heights at which strains merge -- to <outpref>_tree.tsv (lo, hi, num, den, distance per edge, ascending; the distance is num / den, NaN for an undefined one) and its summary to <outpref>_tree_summary.tsv (docs/LINKAGE_TREE.md), beside the usual outputs.", nullptr, false },
+    { "tree_metric", "Distance of --print_tree: core or acc.", "core", true },
     { "load_state", "Start from a state file instead of a clonal population: --n_gen stays the TOTAL, generations [saved, n_gen) are run. pop_size, core_size, pan_genes and core_genes must be the file's; every other flag is this command line's (the same flags continue the saved run bit for bit, other flags branch off it). With --print_dist the earlier rows of _per_gen.tsv come from the file, which must have been saved with --print_dist. One shard only (--gpus 1).", "", true },
 };
 
@@ -339,6 +341,10 @@ int main(int argc, char **argv)
     }
     if (present["print_clusters"] && cluster_prm.core_max_d == UINT64_MAX && cluster_prm.acc_den == 0)
         die(101, "pansim: --print_clusters needs --cluster_core_max, --cluster_acc_max or both");
+    // --print_tree: its metric is checked whether or not it is given
+    ps_tree_params tree_prm = { PS_TREE_CORE };
+    if (val["tree_metric"] == "acc") tree_prm.metric = PS_TREE_ACC;
+    else if (val["tree_metric"] != "core") die(101, "pansim: --tree_metric must be core or acc, not \"" + val["tree_metric"] + "\"");
     const uint64_t G = d.pan_size, P = p.max_distances;
     std::vector<double> avg_core(p.n_gen), avg_acc(p.n_gen), std_core(p.n_gen), std_acc(p.n_gen);
     // a fresh run goes through ps_multi (one shard: the plain run); a LOADED run is a plain ps_sim, driven by the ps_sim_*
@@ -465,6 +471,28 @@ int main(int argc, char **argv)
                 { "edges", c.edges }, { "clusters", c.clusters }, { "singletons", c.singletons }, { "largest_cluster", c.largest_cluster },
                 { "within_pairs", c.within_pairs }, { "undefined_pairs", c.undefined_pairs }, { "core_max_d", cluster_prm.core_max_d },
                 { "acc_num", cluster_prm.acc_num }, { "acc_den", cluster_prm.acc_den } };
+            for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+            fclose(f);
+        }
+        if (present["print_tree"]) {                                   // (no counterpart in the reference: docs/LINKAGE_TREE.md)
+            const size_t n = (size_t)p.pop_size;
+            std::vector<uint32_t> lo(n), hi(n);
+            std::vector<uint64_t> num(n), den(n);
+            ps_tree_t t;
+            CK(multi ? ps_multi_linkage_tree(multi, &tree_prm, &t, lo.data(), hi.data(), num.data(), den.data())
+                     : ps_sim_linkage_tree(sim, &tree_prm, &t, lo.data(), hi.data(), num.data(), den.data()));
+            FILE *f = fopen((outpref + "_tree.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_tree.tsv");
+            for (uint64_t k = 0; k < t.edges; k++)
+                fprintf(f, "%u\t%u\t%llu\t%llu\t%s\n", lo[k], hi[k], (unsigned long long)num[k], (unsigned long long)den[k],
+                        den[k] ? fmt((double)num[k] / (double)den[k]).c_str() : "NaN");
+            fclose(f);
+            f = fopen((outpref + "_tree_summary.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_tree_summary.tsv");
+            const std::pair<const char *, uint64_t> fields[] = {
+                { "pop_size", t.pop_size }, { "pairs", t.pairs }, { "core_sites", t.core_sites }, { "core_genes", t.core_genes },
+                { "metric", t.metric }, { "edges", t.edges }, { "undefined_edges", t.undefined_edges },
+                { "distinct_heights", t.distinct_heights } };
             for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
             fclose(f);
         }

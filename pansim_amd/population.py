@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterParams, Clusters, Config, CoreDiversity, PairHist, PairHistParams, check
+from ._lib import ClusterParams, Clusters, Config, CoreDiversity, PairHist, PairHistParams, Tree, TreeParams, check
 
 
 def _u32(a):
@@ -266,6 +266,83 @@ def clusters_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_si
                          int(core_sites), int(core_genes))
 
 
+class LinkageTree:
+    """The result of `linkage_tree` (ps_tree_t + the edges; docs/LINKAGE_TREE.md): the summary fields as integer attributes,
+    the tree's edges in ascending order of (distance, lo, hi) -- `lo`, `hi` (uint32 rows, lo < hi), `num`, `den` (uint64; the
+    distance of edge k is num[k] / den[k], den 0 = undefined) -- and `distance` (float64, NaN where den is 0)."""
+    FIELDS = tuple(name for name, _ in Tree._fields_)
+
+    def __init__(self, t, lo, hi, num, den):
+        for name in self.FIELDS:
+            setattr(self, name, int(getattr(t, name)))
+        n = self.edges
+        self.lo, self.hi, self.num, self.den = lo[:n], hi[:n], num[:n], den[:n]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.distance = np.where(self.den == 0, np.nan, self.num.astype(np.float64) / self.den.astype(np.float64))
+
+    def _kept(self, num, den):
+        """how many edges (a prefix: they ascend) have a distance <= num / den under the integer rule: defined and
+        num[k] den <= num den[k] in whole numbers.  den == 0 keeps every edge, the undefined ones included."""
+        num, den = int(num), int(den)
+        if num < 0 or den < 0:
+            raise ValueError("a threshold is num / den with num, den >= 0")
+        k = 0
+        while k < self.edges and (den == 0 or (int(self.den[k]) != 0 and int(self.num[k]) * den <= num * int(self.den[k]))):
+            k += 1
+        return k
+
+    def cut(self, num, den):
+        """labels (pop_size uint32, labels[k] the smallest row of k's cluster) after removing the edges with a distance
+        above num / den: the labels of `strain_clusters` at that single threshold"""
+        parent = np.arange(self.pop_size, dtype=np.uint32)
+
+        def root(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        for k in range(self._kept(num, den)):
+            a, b = root(int(self.lo[k])), root(int(self.hi[k]))
+            parent[max(a, b)] = min(a, b)
+        return np.array([root(k) for k in range(self.pop_size)], np.uint32)
+
+    def clusters_at(self, num, den):
+        """the number of clusters of `cut(num, den)`: pop_size less the edges kept"""
+        return self.pop_size - self._kept(num, den)
+
+    def as_dict(self):
+        out = {name: getattr(self, name) for name in self.FIELDS}
+        out.update(lo=self.lo, hi=self.hi, num=self.num, den=self.den, distance=self.distance)
+        return out
+
+
+def _tree_params(metric):
+    if metric not in ("core", "acc"):
+        raise ValueError('metric must be "core" or "acc"')
+    return TreeParams(_lib.PS_TREE_CORE if metric == "core" else _lib.PS_TREE_ACC)
+
+
+def _tree_call(fn, prm, pop_size, *head):
+    """fn(*head, &params, &summary, lo, hi, num, den) -> LinkageTree"""
+    t = Tree()
+    n = max(1, int(pop_size))
+    lo, hi, num, den = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    check(fn(*head, C.byref(prm), C.byref(t), _ptr(lo), _ptr(hi), _ptr(num), _ptr(den)))
+    return LinkageTree(t, lo, hi, num, den)
+
+
+def tree_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_sites, core_genes, metric="core"):
+    """`Population.linkage_tree` from any list of pairs (r1, r2) and their numerators (`pairwise_counts` of both matrices),
+    on the host alone (ps_tree_from_counts; no device).  The numerators of the other metric may be None.  A list that does
+    not connect everything gives the minimum spanning forest (`edges` < pop_size - 1)."""
+    arrays = [None if a is None else _u32(a).reshape(-1) for a in (r1, r2, core_h, acc_inter, acc_union)]
+    if len({a.size for a in arrays if a is not None}) != 1 or arrays[0] is None or arrays[1] is None:
+        raise ValueError("two indices, and one value of every numerator given, per pair")
+    return _tree_call(_lib.load().ps_tree_from_counts, _tree_params(metric), pop_size, *map(_ptr, arrays), arrays[0].size, int(pop_size),
+                      int(core_sites), int(core_genes))
+
+
 def draw_parents(weights, seed, generation):
     """population.rs:440-443"""
     w = _f64(weights)
@@ -485,6 +562,18 @@ class Population:
         core distance is at most `core_max` and its accessory distance at most `acc_max` (either may be left out)."""
         prm = _cluster_params(self.global_cols, core_max, acc_max, core_max_d, acc_ratio)
         return _cluster_call(self._lib.ps_strain_clusters, prm, self.size, self._h, acc._h)
+
+    def linkage_tree(self, acc, metric="core"):
+        """the single-linkage tree -- the minimum spanning tree over ALL pairs -- of this core population and the accessory
+        population `acc` of the same individuals under the core (`"core"`) or the accessory (`"acc"`) distance
+        (ps_linkage_tree; docs/LINKAGE_TREE.md) -> a LinkageTree"""
+        return _tree_call(self._lib.ps_linkage_tree, _tree_params(metric), self.size, self._h, acc._h)
+
+    def linkage_tree_timing(self):
+        """device ms of (the count kernels, the store kernels, the rounds) of the last linkage_tree() on this core handle"""
+        t = [C.c_double() for _ in range(3)]
+        check(self._lib.ps_linkage_tree_timing(self._h, *map(C.byref, t)))
+        return tuple(x.value for x in t)
 
     def strain_clusters_timing(self):
         """device ms of (the count kernels, the edge kernel, the label rounds) of the last strain_clusters() on this core handle"""

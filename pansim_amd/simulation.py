@@ -247,6 +247,11 @@ class Simulation:
         prm = _cluster_params(self.params.core_size, core_max, acc_max, core_max_d, acc_ratio)
         return _cluster_call(self._lib.ps_sim_strain_clusters, prm, self.params.pop_size, self._h)
 
+    def linkage_tree(self, metric="core"):
+        """Population.linkage_tree() of the run's two matrices (ps_sim_linkage_tree), edges in the reference's row order"""
+        from .population import _tree_call, _tree_params
+        return _tree_call(self._lib.ps_sim_linkage_tree, _tree_params(metric), self.params.pop_size, self._h)
+
     def write_outputs(self, outpref):
         core, acc = self.final_distances()
         with open(outpref + ".tsv", "w") as f:                       # main.rs:474-482
@@ -347,6 +352,12 @@ class MultiSimulation:
         from .population import _cluster_call, _cluster_params
         prm = _cluster_params(self.params.core_size, core_max, acc_max, core_max_d, acc_ratio)
         return _cluster_call(self._lib.ps_multi_strain_clusters, prm, self.params.pop_size, self._h)
+
+    def linkage_tree(self, metric="core"):
+        """Population.linkage_tree() over ALL core sites: the shards' band counts added and kept on shard 0, the rounds
+        against its accessory replica (ps_multi_linkage_tree)"""
+        from .population import _tree_call, _tree_params
+        return _tree_call(self._lib.ps_multi_linkage_tree, _tree_params(metric), self.params.pop_size, self._h)
 
     def write(self, outpref):
         check(self._lib.ps_multi_write(self._h, str(outpref).encode()))
