@@ -638,6 +638,67 @@ int ps_tree_from_counts(const uint32_t *r1, const uint32_t *r2, const uint32_t *
  * PS_ERR_STATE before any call. */
 int ps_linkage_tree_timing(ps_population *core, double *counts_ms, double *store_ms, double *rounds_ms);
 
+/* Nearest neighbours: for every individual its k closest OTHER individuals among ALL N under one distance, and the lineages that
+ * follow from them (docs/NEAREST_NEIGHBOURS.md) -- the sparse form of the distance matrix, N k entries, and the graph of
+ * PopPUNK's lineage model.  The reference has no such function: it writes a SAMPLE of pairs as text (population.rs:787-837), and
+ * a sample holds almost none of an individual's nearest neighbours.  The metrics, their numerators, the undefined distance 0 / 0
+ * and the integer comparison are those of the linkage tree above (PS_KNN_CORE = PS_TREE_CORE, PS_KNN_ACC = PS_TREE_ACC).  The
+ * neighbours of individual i are ordered by (distance, neighbour's row), rows of the reference's row order: the order is strict,
+ * the lists are unique and do not depend on the launch geometry, the bands or the sharding; for the edges at one vertex it is
+ * the tree's order (distance, lo, hi).  Limits: 1 <= k <= min(pop_size - 1, PS_KNN_MAX_K); under the accessory metric at most
+ * 65535 accessory genes and core_genes + 65535 < 2^32; else PS_ERR_INVALID. */
+#define PS_KNN_CORE 0
+#define PS_KNN_ACC 1
+#define PS_KNN_MAX_K 128u
+typedef struct {
+    int32_t metric;                    /* PS_KNN_CORE or PS_KNN_ACC */
+    uint32_t k;                        /* neighbours per individual */
+} ps_knn_params;
+typedef struct {
+    uint64_t pop_size, pairs, core_sites, core_genes;      /* pairs: all N (N - 1) / 2, or the list's length from ps_neighbours_from_counts */
+    uint64_t metric, k;
+    uint64_t undefined_neighbours;     /* listed entries with den == 0 */
+    uint64_t graph_edges;              /* distinct unordered pairs (i, j) with j in i's list or i in j's */
+    uint64_t mutual_edges;             /* unordered pairs where both hold; graph_edges + mutual_edges = the listed entries (N k) */
+} ps_knn_t;
+typedef struct {
+    uint64_t pop_size, rank;
+    uint64_t edges;                    /* distinct unordered pairs (i, nbr[i k + q]), q < rank */
+    uint64_t lineages, largest_lineage;
+    uint64_t within_pairs;             /* pairs of individuals inside one lineage */
+} ps_lineage_t;
+/* All pairs of two handles of equal pop_size >= 2 on one device (the reference has no such function; population.rs:787-837
+ * writes a sample): `core` a core handle that holds all sites, `acc` an accessory handle of at most 65535 genes (required; with
+ * the core metric none of its kernels is launched).  nbr, num, den: pop_size * k values each; entry i k + r is the r-th nearest
+ * other individual of row i of the reference's row order, its distance num / den (0 / 0: undefined).  Every list is full.  Needs
+ * no N x N scratch: O(N k) beside the band of the count kernels.  Ordered behind all queued work of BOTH handles; changes no
+ * state.  PS_ERR_NO_DEVICE before anything else when no GPU is visible. */
+int ps_nearest_neighbours(ps_population *core, ps_population *acc, const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr, uint64_t *num,
+                          uint64_t *den);
+/* The same for the two matrices of a simulation (the reference has no such function; population.rs:787-837); a site shard
+ * fails with a message that points to ps_multi_nearest_neighbours */
+int ps_sim_nearest_neighbours(ps_sim *s, const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr, uint64_t *num, uint64_t *den);
+/* The same for a sharded run (the reference has no such function; population.rs:787-837): every shard counts its own sites
+ * band by band, shard 0 adds them and selects against its accessory replica */
+int ps_multi_nearest_neighbours(ps_multi *m, const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr, uint64_t *num, uint64_t *den);
+/* The same order on the host alone (no device is touched, as ps_tree_from_counts; the reference has no such function;
+ * population.rs:787-837): any list of pairs (r1[k], r2[k]) with their numerators (those of the other metric may be NULL), in
+ * the list's own index space; every pair is a candidate of both its ends.  An individual with fewer than k listed partners gets
+ * UINT32_MAX, 0, 0 in the unfilled slots (the limits on k are the same).  Of several copies of a pair the nearest (at equal
+ * distance the earliest) is listed, once.  The other PS_ERR_INVALID cases are those of
+ * ps_tree_from_counts. */
+int ps_neighbours_from_counts(const uint32_t *r1, const uint32_t *r2, const uint32_t *core_h, const uint32_t *acc_inter,
+                              const uint32_t *acc_union, uint64_t n_pairs, uint64_t pop_size, uint64_t core_sites, uint64_t core_genes,
+                              const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr, uint64_t *num, uint64_t *den);
+/* Lineages at rank 1 <= rank <= k (host only; the reference has no such function; population.rs:787-837): the connected
+ * components of the graph with the edges {i, nbr[i k + q]}, q < rank.  labels[i] = the smallest row of i's component, as in
+ * ps_strain_clusters.  UINT32_MAX entries are skipped; any other index >= pop_size, or a rank outside 1 .. k, is
+ * PS_ERR_INVALID. */
+int ps_lineages_from_neighbours(const uint32_t *nbr, uint64_t pop_size, uint32_t k, uint32_t rank, ps_lineage_t *out, uint32_t *labels);
+/* device ms of the last ps_nearest_neighbours on this core handle (HIP events; the reference has no such function;
+ * population.rs:787-837): the count kernels of the metric, the select kernels.  PS_ERR_STATE before any call. */
+int ps_nearest_neighbours_timing(ps_population *core, double *counts_ms, double *select_ms);
+
 #ifdef __cplusplus
 }
 #endif

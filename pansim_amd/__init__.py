@@ -5,8 +5,8 @@ over the C ABI of libpansim_hip.so (include/pansim_hip.h).  All compute runs in 
 HIP kernels; there is no CPU fallback and importing the API without the built library fails.
 """
 from ._lib import LIB_PATH, PansimError, load  # noqa: F401
-from .population import (DistanceHistogram, LinkageTree, Population, StrainClusters, clusters_from_counts, diversity_from_counts, draw_parents,  # noqa: F401
-                         fmt_f64, hamming_bitwise_fast, histogram_from_counts, init_vector, int_to_base, jaccard_distance_fast,
+from .population import (DistanceHistogram, LinkageTree, NearestNeighbours, Population, StrainClusters, clusters_from_counts, diversity_from_counts, draw_parents,  # noqa: F401
+                         fmt_f64, hamming_bitwise_fast, histogram_from_counts, init_vector, int_to_base, jaccard_distance_fast, neighbours_from_counts,
                          sample_weights, site_tables, standard_deviation, tree_from_counts)
 from .simulation import (DEFAULTS, MultiSimulation, Simulation, derive, make_params, sample_pairs,  # noqa: F401
                          selection_coefficients, state_info, validate)

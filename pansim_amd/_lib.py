@@ -109,6 +109,25 @@ class Tree(C.Structure):
                                                  "distinct_heights", "rounds")]
 
 
+PS_KNN_CORE, PS_KNN_ACC, PS_KNN_MAX_K = 0, 1, 128
+
+
+class KnnParams(C.Structure):
+    """ps_knn_params: the metric (PS_KNN_CORE or PS_KNN_ACC) and k of ps_nearest_neighbours (docs/NEAREST_NEIGHBOURS.md)"""
+    _fields_ = [("metric", C.c_int32), ("k", C.c_uint32)]
+
+
+class Knn(C.Structure):
+    """ps_knn_t: the summary of ps_nearest_neighbours / ps_neighbours_from_counts"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "pairs", "core_sites", "core_genes", "metric", "k", "undefined_neighbours",
+                                                 "graph_edges", "mutual_edges")]
+
+
+class Lineages(C.Structure):
+    """ps_lineage_t: the summary of ps_lineages_from_neighbours"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "rank", "edges", "lineages", "largest_lineage", "within_pairs")]
+
+
 # every symbol include/pansim_hip.h declares (tests/test_host_logic.py::test_library_exports_every_declared_symbol checks the header against this)
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -224,6 +243,12 @@ SIGNATURES = {
     "ps_multi_linkage_tree": (_int, [_vp, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
     "ps_tree_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
     "ps_linkage_tree_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_nearest_neighbours": (_int, [_vp, _vp, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
+    "ps_sim_nearest_neighbours": (_int, [_vp, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
+    "ps_multi_nearest_neighbours": (_int, [_vp, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
+    "ps_neighbours_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
+    "ps_lineages_from_neighbours": (_int, [_vp, _u64, C.c_uint32, C.c_uint32, C.POINTER(Lineages), _vp]),
+    "ps_nearest_neighbours_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

@@ -326,6 +326,11 @@ struct ps_population {
     uint64_t tree_cap = 0;                  // (bytes)
     double tree_ms[3] = {};                 // counts, store, rounds
     bool tree_timed = false;
+    // nearest neighbours (nearest_neighbours.h), on the core handle: out_row, then the N k listed entries; the last call's times
+    void *d_knn = nullptr;
+    uint64_t knn_cap = 0;                   // (bytes)
+    double knn_ms[2] = {};                  // counts, select
+    bool knn_timed = false;
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
     unsigned long long *h_stamps = nullptr, *d_stamps = nullptr;   // diagnostic phase stamps
 };
@@ -407,7 +412,7 @@ extern "C" void ps_population_destroy(ps_population *p)
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     void *ptrs[] = { p->d_row_slot, p->state, p->state2, p->d_delta, p->hgt_ovf_img, p->G[0], p->G[1], p->I[0], p->I[1], p->I_snap, p->d_ptab[0], p->d_ptab[1], p->hgt_scratch, p->cnt, p->d_idx, p->d_idxT, p->d_work,
-                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg, p->d_cl, p->d_tree };
+                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg, p->d_cl, p->d_tree, p->d_knn };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (int c = 2; c < PS_MAX_COMP; c++)
@@ -4924,6 +4929,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // single-linkage tree of all pairs (ps_linkage_tree, ps_tree_from_counts, ps_multi_*)
 #include "linkage_tree.h"
+
+// nearest neighbours of all pairs and rank-k lineages (ps_nearest_neighbours, ps_neighbours_from_counts, ps_lineages_from_neighbours, ps_multi_*)
+#include "nearest_neighbours.h"
 
 // the native RCCL provider of ps_exchange_fn (ps_rccl_*, ps_exchange_rccl)
 #include "exchange_rccl.h"

@@ -60,6 +60,8 @@ static const Flag EXT_FLAGS[] = {
     { "cluster_acc_max", "Largest accessory distance of a pair that --print_clusters joins. Must be 0.0 <= X <= 1.0. Without it the accessory distance is not looked at.", "", true },
     { "print_tree", "Write the single-linkage tree of the final population -- the minimum spanning tree over ALL pairs under the distance chosen by --tree_metric, whose sorted edge weights are the heights at which strains merge -- to <outpref>_tree.tsv (lo, hi, num, den, distance per edge, ascending; the distance is num / den, NaN for an undefined one) and its summary to <outpref>_tree_summary.tsv (docs/LINKAGE_TREE.md), beside the usual outputs.", nullptr, false },
     { "tree_metric", "Distance of --print_tree: core or acc.", "core", true },
+    { "print_knn", "Write the <print_knn> nearest neighbours of every individual of the final population -- among ALL others, under the distance chosen by --knn_metric, ordered by (distance, row) -- to <outpref>_knn.tsv (row, rank from 1, neighbour, num, den, distance; the distance is num / den, NaN for an undefined one), the lineages at rank <print_knn> -- the connected components of the graph of those neighbours -- to <outpref>_lineages.tsv (row, label: the smallest row of its lineage) and the summary, with the number of lineages and the largest one at every rank up to <print_knn>, to <outpref>_knn_summary.tsv (docs/NEAREST_NEIGHBOURS.md), beside the usual outputs. Must be 1 <= X <= min(pop_size - 1, 128).", "", true },
+    { "knn_metric", "Distance of --print_knn: core or acc.", "core", true },
     { "load_state", "Start from a state file instead of a clonal population: --n_gen stays the TOTAL, generations [saved, n_gen) are run. pop_size, core_size, pan_genes and core_genes must be the file's; every other flag is this command line's (the same flags continue the saved run bit for bit, other flags branch off it). With --print_dist the earlier rows of _per_gen.tsv come from the file, which must have been saved with --print_dist. One shard only (--gpus 1).", "", true },
 };
 
@@ -345,6 +347,21 @@ int main(int argc, char **argv)
     ps_tree_params tree_prm = { PS_TREE_CORE };
     if (val["tree_metric"] == "acc") tree_prm.metric = PS_TREE_ACC;
     else if (val["tree_metric"] != "core") die(101, "pansim: --tree_metric must be core or acc, not \"" + val["tree_metric"] + "\"");
+    // --print_knn: its metric is checked whether or not it is given
+    ps_knn_params knn_prm = { PS_KNN_CORE, 0 };
+    if (val["knn_metric"] == "acc") knn_prm.metric = PS_KNN_ACC;
+    else if (val["knn_metric"] != "core") die(101, "pansim: --knn_metric must be core or acc, not \"" + val["knn_metric"] + "\"");
+    const bool print_knn = !val["print_knn"].empty();
+    if (print_knn) {
+        const std::string &t = val["print_knn"];
+        unsigned long long k = 0;
+        int used = 0;
+        if (sscanf(t.c_str(), "%llu%n", &k, &used) != 1 || (size_t)used != t.size() || t.find_first_of("+- ") != std::string::npos)
+            die(101, "pansim: --print_knn must be a whole number, not \"" + t + "\"");
+        if (k < 1 || k > PS_KNN_MAX_K || k + 1 > p.pop_size)
+            die(101, "pansim: --print_knn must be 1 <= X <= min(pop_size - 1, 128), not " + t + " with --pop_size " + std::to_string(p.pop_size));
+        knn_prm.k = (uint32_t)k;
+    }
     const uint64_t G = d.pan_size, P = p.max_distances;
     std::vector<double> avg_core(p.n_gen), avg_acc(p.n_gen), std_core(p.n_gen), std_acc(p.n_gen);
     // a fresh run goes through ps_multi (one shard: the plain run); a LOADED run is a plain ps_sim, driven by the ps_sim_*
@@ -494,6 +511,38 @@ int main(int argc, char **argv)
                 { "metric", t.metric }, { "edges", t.edges }, { "undefined_edges", t.undefined_edges },
                 { "distinct_heights", t.distinct_heights } };
             for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+            fclose(f);
+        }
+        if (print_knn) {                                               // (no counterpart in the reference: docs/NEAREST_NEIGHBOURS.md)
+            const size_t n = (size_t)p.pop_size, k = knn_prm.k;
+            std::vector<uint32_t> nbr(n * k), labels(n);
+            std::vector<uint64_t> num(n * k), den(n * k);
+            ps_knn_t t;
+            CK(multi ? ps_multi_nearest_neighbours(multi, &knn_prm, &t, nbr.data(), num.data(), den.data())
+                     : ps_sim_nearest_neighbours(sim, &knn_prm, &t, nbr.data(), num.data(), den.data()));
+            FILE *f = fopen((outpref + "_knn.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_knn.tsv");
+            for (size_t e = 0; e < n * k; e++)
+                fprintf(f, "%llu\t%llu\t%u\t%llu\t%llu\t%s\n", (unsigned long long)(e / k), (unsigned long long)(e % k + 1), nbr[e],
+                        (unsigned long long)num[e], (unsigned long long)den[e], den[e] ? fmt((double)num[e] / (double)den[e]).c_str() : "NaN");
+            fclose(f);
+            f = fopen((outpref + "_knn_summary.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_knn_summary.tsv");
+            const std::pair<const char *, uint64_t> fields[] = {
+                { "pop_size", t.pop_size }, { "pairs", t.pairs }, { "core_sites", t.core_sites }, { "core_genes", t.core_genes },
+                { "metric", t.metric }, { "k", t.k }, { "undefined_neighbours", t.undefined_neighbours }, { "graph_edges", t.graph_edges },
+                { "mutual_edges", t.mutual_edges } };
+            for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+            // the lineages at every rank; the labels of the last one (rank k) are the ones written
+            for (uint32_t r = 1; r <= knn_prm.k; r++) {
+                ps_lineage_t l;
+                CK(ps_lineages_from_neighbours(nbr.data(), n, knn_prm.k, r, &l, labels.data()));
+                fprintf(f, "lineages\t%u\t%llu\t%llu\n", r, (unsigned long long)l.lineages, (unsigned long long)l.largest_lineage);
+            }
+            fclose(f);
+            f = fopen((outpref + "_lineages.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_lineages.tsv");
+            for (size_t i = 0; i < n; i++) fprintf(f, "%llu\t%u\n", (unsigned long long)i, labels[i]);
             fclose(f);
         }
     };

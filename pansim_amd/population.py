@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterParams, Clusters, Config, CoreDiversity, PairHist, PairHistParams, Tree, TreeParams, check
+from ._lib import ClusterParams, Clusters, Config, CoreDiversity, Knn, KnnParams, Lineages, PairHist, PairHistParams, Tree, TreeParams, check
 
 
 def _u32(a):
@@ -343,6 +343,67 @@ def tree_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_sites,
                       int(core_sites), int(core_genes))
 
 
+class NearestNeighbours:
+    """The result of `nearest_neighbours` (ps_knn_t + the lists; docs/NEAREST_NEIGHBOURS.md): the summary fields as integer
+    attributes and, as (pop_size, k) arrays, `nbr` (uint32: entry [i, r] is the r-th nearest other individual of row i in
+    ascending order of (distance, row); 2^32 - 1 in a slot that a pair list left unfilled), `num`, `den` (uint64; the
+    distance is num / den, den 0 = undefined) and `distance` (float64, NaN where den is 0)."""
+    FIELDS = tuple(name for name, _ in Knn._fields_)
+
+    def __init__(self, t, nbr, num, den):
+        for name in self.FIELDS:
+            setattr(self, name, int(getattr(t, name)))
+        shape = (self.pop_size, self.k)
+        self.nbr, self.num, self.den = nbr.reshape(shape), num.reshape(shape), den.reshape(shape)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.distance = np.where(self.den == 0, np.nan, self.num.astype(np.float64) / self.den.astype(np.float64))
+
+    def lineages(self, rank=None):
+        """(labels, summary) of the lineages at `rank` <= k (default k): the connected components of the graph that joins
+        every individual to its first `rank` neighbours (ps_lineages_from_neighbours; host only).  labels: pop_size uint32,
+        labels[i] the smallest row of i's lineage; summary: the fields of ps_lineage_t as a dict of ints."""
+        out = Lineages()
+        labels = np.zeros(self.pop_size, np.uint32)
+        nbr = np.ascontiguousarray(self.nbr)
+        check(_lib.load().ps_lineages_from_neighbours(_ptr(nbr), self.pop_size, self.k, self.k if rank is None else int(rank),
+                                                      C.byref(out), _ptr(labels)))
+        return labels, {name: int(getattr(out, name)) for name, _ in Lineages._fields_}
+
+    def as_dict(self):
+        out = {name: getattr(self, name) for name in self.FIELDS}
+        out.update(nbr=self.nbr, num=self.num, den=self.den, distance=self.distance)
+        return out
+
+
+def _knn_params(k, metric):
+    if metric not in ("core", "acc"):
+        raise ValueError('metric must be "core" or "acc"')
+    if not 0 <= int(k) < 2**32:
+        raise ValueError("k must fit 32 bits")
+    return KnnParams(_lib.PS_KNN_CORE if metric == "core" else _lib.PS_KNN_ACC, int(k))
+
+
+def _knn_call(fn, prm, pop_size, *head):
+    """fn(*head, &params, &summary, nbr, num, den) -> NearestNeighbours"""
+    t = Knn()
+    n = max(1, int(pop_size) * int(prm.k))
+    nbr, num, den = np.zeros(n, np.uint32), np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    check(fn(*head, C.byref(prm), C.byref(t), _ptr(nbr), _ptr(num), _ptr(den)))
+    m = int(t.pop_size) * int(t.k)
+    return NearestNeighbours(t, nbr[:m], num[:m], den[:m])
+
+
+def neighbours_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_sites, core_genes, k, metric="core"):
+    """`Population.nearest_neighbours` from any list of pairs (r1, r2) and their numerators (`pairwise_counts` of both
+    matrices), on the host alone (ps_neighbours_from_counts; no device).  The numerators of the other metric may be None.
+    An individual with fewer than k listed partners has 2^32 - 1, 0, 0 in its unfilled slots."""
+    arrays = [None if a is None else _u32(a).reshape(-1) for a in (r1, r2, core_h, acc_inter, acc_union)]
+    if len({a.size for a in arrays if a is not None}) != 1 or arrays[0] is None or arrays[1] is None:
+        raise ValueError("two indices, and one value of every numerator given, per pair")
+    return _knn_call(_lib.load().ps_neighbours_from_counts, _knn_params(k, metric), pop_size, *map(_ptr, arrays), arrays[0].size,
+                     int(pop_size), int(core_sites), int(core_genes))
+
+
 def draw_parents(weights, seed, generation):
     """population.rs:440-443"""
     w = _f64(weights)
@@ -568,6 +629,18 @@ class Population:
         population `acc` of the same individuals under the core (`"core"`) or the accessory (`"acc"`) distance
         (ps_linkage_tree; docs/LINKAGE_TREE.md) -> a LinkageTree"""
         return _tree_call(self._lib.ps_linkage_tree, _tree_params(metric), self.size, self._h, acc._h)
+
+    def nearest_neighbours(self, acc, k, metric="core"):
+        """the k nearest other individuals of every individual among ALL of this core population and the accessory population
+        `acc` of the same individuals, under the core (`"core"`) or the accessory (`"acc"`) distance, in ascending order of
+        (distance, row) (ps_nearest_neighbours; docs/NEAREST_NEIGHBOURS.md) -> a NearestNeighbours"""
+        return _knn_call(self._lib.ps_nearest_neighbours, _knn_params(k, metric), self.size, self._h, acc._h)
+
+    def nearest_neighbours_timing(self):
+        """device ms of (the count kernels, the select kernels) of the last nearest_neighbours() on this core handle"""
+        t = [C.c_double() for _ in range(2)]
+        check(self._lib.ps_nearest_neighbours_timing(self._h, *map(C.byref, t)))
+        return tuple(x.value for x in t)
 
     def linkage_tree_timing(self):
         """device ms of (the count kernels, the store kernels, the rounds) of the last linkage_tree() on this core handle"""

@@ -252,6 +252,12 @@ class Simulation:
         from .population import _tree_call, _tree_params
         return _tree_call(self._lib.ps_sim_linkage_tree, _tree_params(metric), self.params.pop_size, self._h)
 
+    def nearest_neighbours(self, k, metric="core"):
+        """Population.nearest_neighbours() of the run's two matrices (ps_sim_nearest_neighbours), rows and neighbours in the
+        reference's row order"""
+        from .population import _knn_call, _knn_params
+        return _knn_call(self._lib.ps_sim_nearest_neighbours, _knn_params(k, metric), self.params.pop_size, self._h)
+
     def write_outputs(self, outpref):
         core, acc = self.final_distances()
         with open(outpref + ".tsv", "w") as f:                       # main.rs:474-482
@@ -358,6 +364,12 @@ class MultiSimulation:
         against its accessory replica (ps_multi_linkage_tree)"""
         from .population import _tree_call, _tree_params
         return _tree_call(self._lib.ps_multi_linkage_tree, _tree_params(metric), self.params.pop_size, self._h)
+
+    def nearest_neighbours(self, k, metric="core"):
+        """Population.nearest_neighbours() over ALL core sites: the shards' band counts added on shard 0, the selection
+        against its accessory replica (ps_multi_nearest_neighbours)"""
+        from .population import _knn_call, _knn_params
+        return _knn_call(self._lib.ps_multi_nearest_neighbours, _knn_params(k, metric), self.params.pop_size, self._h)
 
     def write(self, outpref):
         check(self._lib.ps_multi_write(self._h, str(outpref).encode()))
