@@ -699,6 +699,98 @@ int ps_lineages_from_neighbours(const uint32_t *nbr, uint64_t pop_size, uint32_t
  * population.rs:787-837): the count kernels of the metric, the select kernels.  PS_ERR_STATE before any call. */
 int ps_nearest_neighbours_timing(ps_population *core, double *counts_ms, double *select_ms);
 
+/* True genealogy of a run (docs/GENEALOGY.md): the parent draws of the generations loop recorded on the device, and from them
+ * the relatedness that actually happened -- what the read-outs above infer from distances.  The reference has no such function:
+ * its parent draws (population.rs:443) are dropped after every generation.
+ * ps_sim_record_ancestry keeps the draws of the last `capacity` generations in a device ring of capacity x pop_size u32 (one
+ * stream-ordered copy per generation; the matrices of the run do not change by a bit).  capacity 0 switches the recording off
+ * and frees the ring; any call starts an empty record.  The record also starts again (depth 0) at a generation that follows a
+ * direct ps_load_matrix / ps_step / ps_next_generation on a handle of the run, and at a ps_sim_run whose first_generation is not
+ * the one after the last.  It is not written to state files: ps_sim_load returns a run that records nothing.
+ * capacity x pop_size x 4 must stay below 2^64 (PS_ERR_INVALID); an allocation that fails is PS_ERR_OOM. */
+#define PS_GEN_BEYOND 0xffffffffu
+typedef struct {
+    uint64_t pop_size, generation;     /* generation: the generations done (ps_sim_generations_done) */
+    uint64_t capacity, depth;          /* depth = min(generations recorded since the record began, capacity) */
+    uint64_t roots;                    /* 1 + the entries of coal that are PS_GEN_BEYOND */
+    uint64_t tmrca;                    /* max of coal when roots == 1, else 0 */
+} ps_genealogy_t;
+typedef struct {
+    uint64_t clusters, largest, within_pairs;      /* within_pairs: sum over the clusters of size (size - 1) / 2 */
+} ps_gen_clusters_t;
+int ps_sim_record_ancestry(ps_sim *s, uint32_t capacity);
+/* The same for a sharded run (the reference has no such function; population.rs:443): every shard draws the same parents,
+ * shard 0 records alone */
+int ps_multi_record_ancestry(ps_multi *m, uint32_t capacity);
+/* The comb of the present population (the reference has no such function; population.rs:443): order[r], r < pop_size, is the
+ * row of the reference's row order (row k = the child of draw k) stored at internal row r; coal[r], r < pop_size - 1, is the
+ * smallest t in 1 .. depth at which the ancestors t generations back of internal rows r and r + 1 are one individual, or
+ * PS_GEN_BEYOND.  Children are stored in ascending parent order, so the time of ANY two internal rows i < j is
+ * max(coal[i .. j - 1]).  Behind all queued work of the run; changes no state.  PS_ERR_NO_DEVICE before anything else when no
+ * GPU is visible; PS_ERR_STATE while nothing is recorded (the message names ps_sim_record_ancestry). */
+int ps_sim_genealogy(ps_sim *s, ps_genealogy_t *out, uint32_t *order, uint32_t *coal);
+int ps_multi_genealogy(ps_multi *m, ps_genealogy_t *out, uint32_t *order, uint32_t *coal);
+/* Host-only read-outs of a comb (no device is touched; the reference has no such function; population.rs:443).  order must be
+ * a permutation of 0 .. pop_size - 1, rows are rows of the reference's row order.
+ * _pair: the time to the most recent common ancestor of rows i and j (0 for i == j; PS_GEN_BEYOND dominates); _pairs: the
+ * same for a list. */
+int ps_genealogy_pair(const uint32_t *order, const uint32_t *coal, uint64_t pop_size, uint32_t i, uint32_t j, uint32_t *t);
+int ps_genealogy_pairs(const uint32_t *order, const uint32_t *coal, uint64_t pop_size, const uint32_t *r1, const uint32_t *r2,
+                       uint64_t n_pairs, uint32_t *t);
+/* The true clusters at look-back t <= depth (host only; the reference has no such function; population.rs:443): labels[i] =
+ * the smallest row among those that share row i's ancestor t generations back, as ps_strain_clusters labels.  t above `depth`
+ * (the depth of the comb's ps_genealogy_t) is PS_ERR_INVALID. */
+int ps_genealogy_clusters(const uint32_t *order, const uint32_t *coal, uint64_t pop_size, uint32_t depth, uint32_t t, uint32_t *labels,
+                          ps_gen_clusters_t *out);
+/* The trees of the comb in Newick form (host only; the reference has no such function; population.rs:443): one tree per root,
+ * one line each, ending in ";".  Leaves are rows; a segment of the comb splits at EVERY position of its largest time (equal
+ * times: a multifurcation), children in comb order as (child:len,...) with whole-number lengths.  *needed = the bytes of the text
+ * with its terminating zero; buf == NULL asks for the size alone, a buffer below it is PS_ERR_INVALID. */
+int ps_genealogy_newick(const uint32_t *order, const uint32_t *coal, uint64_t pop_size, char *buf, uint64_t cap, uint64_t *needed);
+
+/* Clock histogram: ALL N (N - 1) / 2 pairs binned by (divergence time, distance) -- whether distance tracks time under the
+ * run's recombination (docs/GENEALOGY.md).  The reference has no such function (population.rs:443, :787-837).  metric and its
+ * numerators as ps_nearest_neighbours; the distance axis by the integer rules of ps_distance_histogram with dist_bins bins
+ * (core: span core_span, 0 = automatic; accessory: a pair with b == 0 is in no bin and counted in undefined_pairs).  Time axis
+ * with St = time_span (0 = depth): a pair that coalesced t generations back is in row min(time_bins - 1, floor((t - 1)
+ * time_bins / St)), a pair beyond the record in the extra row time_bins.  joint[row * dist_bins + bin]: (time_bins + 1) x
+ * dist_bins values; per_time[3 row + 0, 1, 2]: the binned pairs of the row, their sum of num and of den (core: num = d = h / 2,
+ * den = core sites; accessory: num = a, den = b).  Limits: time_bins, dist_bins >= 1, time_bins <= 1024, (time_bins + 1) x
+ * dist_bins <= 16384, time_span < 2^32, the accessory limits of ps_nearest_neighbours; else PS_ERR_INVALID.  Results do not
+ * depend on the launch geometry, the bands or the sharding. */
+typedef struct {
+    int32_t metric;                    /* PS_KNN_CORE or PS_KNN_ACC */
+    uint32_t time_bins, dist_bins;
+    uint64_t time_span;                /* St >= 1 in generations; 0 = the record's depth */
+    uint64_t core_span;                /* as ps_pair_hist_params; not used by the accessory metric */
+} ps_clock_params;
+typedef struct {
+    uint64_t pop_size, pairs, core_sites, core_genes;      /* pop_size is 0 from ps_clock_from_counts */
+    uint64_t metric, time_bins, dist_bins;
+    uint64_t time_span, core_span;     /* the spans used (core_span 0 under the accessory metric) */
+    uint64_t depth;
+    uint64_t undefined_pairs, core_clamped;
+    uint64_t beyond_pairs;             /* the binned pairs of row time_bins */
+    uint64_t binned_pairs;             /* the sum of joint = pairs - undefined_pairs */
+    uint64_t num_sum, den_sum;         /* over the binned pairs */
+} ps_clock_t;
+/* The two matrices of a recording simulation against its own record.  Behind all queued work of the run; changes no state.
+ * PS_ERR_NO_DEVICE before anything else when no GPU is visible; PS_ERR_STATE while nothing is recorded (the message names
+ * ps_sim_record_ancestry); a site shard fails with a message that points to ps_multi_clock_histogram */
+int ps_sim_clock_histogram(ps_sim *s, const ps_clock_params *prm, ps_clock_t *out, uint64_t *joint, uint64_t *per_time);
+/* The same for a sharded run (the reference has no such function; population.rs:443, :787-837): every shard counts its own
+ * sites band by band, shard 0 adds them and bins against its own record and accessory replica */
+int ps_multi_clock_histogram(ps_multi *m, const ps_clock_params *prm, ps_clock_t *out, uint64_t *joint, uint64_t *per_time);
+/* The same rules on the host alone (no device is touched, as ps_histogram_from_counts; the reference has no such function;
+ * population.rs:443, :787-837): any list of pairs with their divergence times (1 .. depth or PS_GEN_BEYOND, e.g. from
+ * ps_genealogy_pairs) and numerators (those of the other metric may be NULL).  n_pairs >= 1, 1 <= depth < 2^32 - 1. */
+int ps_clock_from_counts(const uint32_t *tmrca, const uint32_t *core_h, const uint32_t *acc_inter, const uint32_t *acc_union,
+                         uint64_t n_pairs, uint64_t depth, uint64_t core_sites, uint64_t core_genes, const ps_clock_params *prm,
+                         ps_clock_t *out, uint64_t *joint, uint64_t *per_time);
+/* device ms of the last clock histogram on this core handle (HIP events; the reference has no such function;
+ * population.rs:787-837): the count kernels of the metric; the comb, the table and the binning.  PS_ERR_STATE before any call. */
+int ps_clock_histogram_timing(ps_population *core, double *counts_ms, double *binning_ms);
+
 #ifdef __cplusplus
 }
 #endif

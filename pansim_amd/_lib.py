@@ -128,6 +128,32 @@ class Lineages(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("pop_size", "rank", "edges", "lineages", "largest_lineage", "within_pairs")]
 
 
+PS_GEN_BEYOND = 0xffffffff
+
+
+class Genealogy(C.Structure):
+    """ps_genealogy_t: the summary of ps_sim_genealogy (docs/GENEALOGY.md)"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "generation", "capacity", "depth", "roots", "tmrca")]
+
+
+class GenClusters(C.Structure):
+    """ps_gen_clusters_t: the summary of ps_genealogy_clusters"""
+    _fields_ = [(name, C.c_uint64) for name in ("clusters", "largest", "within_pairs")]
+
+
+class ClockParams(C.Structure):
+    """ps_clock_params: the metric, bins and spans of ps_sim_clock_histogram (docs/GENEALOGY.md); a span of 0 = automatic"""
+    _fields_ = [("metric", C.c_int32), ("time_bins", C.c_uint32), ("dist_bins", C.c_uint32), ("time_span", C.c_uint64),
+                ("core_span", C.c_uint64)]
+
+
+class Clock(C.Structure):
+    """ps_clock_t: the summary of ps_sim_clock_histogram / ps_clock_from_counts"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "pairs", "core_sites", "core_genes", "metric", "time_bins", "dist_bins",
+                                                 "time_span", "core_span", "depth", "undefined_pairs", "core_clamped", "beyond_pairs",
+                                                 "binned_pairs", "num_sum", "den_sum")]
+
+
 # every symbol include/pansim_hip.h declares (tests/test_host_logic.py::test_library_exports_every_declared_symbol checks the header against this)
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -249,6 +275,18 @@ SIGNATURES = {
     "ps_neighbours_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
     "ps_lineages_from_neighbours": (_int, [_vp, _u64, C.c_uint32, C.c_uint32, C.POINTER(Lineages), _vp]),
     "ps_nearest_neighbours_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_sim_record_ancestry": (_int, [_vp, _u32]),
+    "ps_multi_record_ancestry": (_int, [_vp, _u32]),
+    "ps_sim_genealogy": (_int, [_vp, C.POINTER(Genealogy), _vp, _vp]),
+    "ps_multi_genealogy": (_int, [_vp, C.POINTER(Genealogy), _vp, _vp]),
+    "ps_genealogy_pair": (_int, [_vp, _vp, _u64, _u32, _u32, C.POINTER(_u32)]),
+    "ps_genealogy_pairs": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "ps_genealogy_clusters": (_int, [_vp, _vp, _u64, _u32, _u32, _vp, C.POINTER(GenClusters)]),
+    "ps_genealogy_newick": (_int, [_vp, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    "ps_sim_clock_histogram": (_int, [_vp, C.POINTER(ClockParams), C.POINTER(Clock), _vp, _vp]),
+    "ps_multi_clock_histogram": (_int, [_vp, C.POINTER(ClockParams), C.POINTER(Clock), _vp, _vp]),
+    "ps_clock_from_counts": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(ClockParams), C.POINTER(Clock), _vp, _vp]),
+    "ps_clock_histogram_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

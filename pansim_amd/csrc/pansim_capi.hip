@@ -331,6 +331,12 @@ struct ps_population {
     uint64_t knn_cap = 0;                   // (bytes)
     double knn_ms[2] = {};                  // counts, select
     bool knn_timed = false;
+    // recorded genealogy (genealogy.h, clock_histogram.h), on the core handle: the sparse table over the comb (level 0 = coal),
+    // then the words, sums and bins of the clock histogram; the last clock histogram's times
+    void *d_gen = nullptr;
+    uint64_t gen_cap = 0;                   // (bytes)
+    double clock_ms[2] = {};                // counts, comb + table + binning
+    bool clock_timed = false;
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
     unsigned long long *h_stamps = nullptr, *d_stamps = nullptr;   // diagnostic phase stamps
 };
@@ -412,7 +418,7 @@ extern "C" void ps_population_destroy(ps_population *p)
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     void *ptrs[] = { p->d_row_slot, p->state, p->state2, p->d_delta, p->hgt_ovf_img, p->G[0], p->G[1], p->I[0], p->I[1], p->I_snap, p->d_ptab[0], p->d_ptab[1], p->hgt_scratch, p->cnt, p->d_idx, p->d_idxT, p->d_work,
-                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg, p->d_cl, p->d_tree, p->d_knn };
+                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg, p->d_cl, p->d_tree, p->d_knn, p->d_gen };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (int c = 2; c < PS_MAX_COMP; c++)
@@ -3435,6 +3441,11 @@ struct ps_sim {
     uint32_t *d_idx_tsum = nullptr;              // ... and the totals / prefixes of its 1024-parent tiles
     uint32_t *d_idx_cnt = nullptr;               // device draw: children per parent, then their inclusive prefix sums (counting sort)
     int last_slot = 0;
+    // recorded ancestry (ps_sim_record_ancestry, genealogy.h): a device ring of anc_capacity rows of N parents, the row of the
+    // q-th generation recorded since the last reset at q % anc_capacity; 0 = recording off
+    uint32_t *d_anc = nullptr;
+    uint32_t anc_capacity = 0;
+    uint64_t anc_written = 0;
     // distance phase (ps_sim_pairwise_distances): pinned numerators, events around the kernels of each matrix
     uint32_t *h_cnt = nullptr;           // 3 x P: core numerators | accessory intersections | unions
     uint64_t h_cnt_cap = 0;
@@ -3483,6 +3494,7 @@ extern "C" void ps_sim_destroy(ps_sim *s)
     if (s->d_cum) (void)hipFree(s->d_cum);
     if (s->d_idx_cnt) (void)hipFree(s->d_idx_cnt);
     if (s->d_idx_tsum) (void)hipFree(s->d_idx_tsum);
+    if (s->d_anc) (void)hipFree(s->d_anc);
     if (s->h_cnt) (void)hipHostFree(s->h_cnt);
     for (auto e : s->ev_dist) if (e) (void)hipEventDestroy(e);
     if (s->d_avg) (void)hipFree(s->d_avg);
@@ -3782,6 +3794,8 @@ static int sim_accessory_half(ps_sim *s, uint32_t gen, uint32_t gens, bool light
     th0 = clk::now();
     s->prev_slot = s->step_count ? s->last_slot : -1;
     s->last_slot = slot;
+    // (a matrix loaded into a handle since the last generation: the recorded ancestors are not those of its rows)
+    if (core->rows_overridden || acc->rows_overridden) s->anc_written = 0;
     core->rows_overridden = acc->rows_overridden = false;      // (rows in the order of THIS generation's draws from here on)
     // the step leaves the pre-recombination snapshot only for the light HGT form, the one that reads it (the binned form of
     // cfg3 / cfg4 / cfg5 does not: a third N x GW x 8-byte buffer written per generation with no reader)
@@ -3830,6 +3844,12 @@ static int sim_accessory_half(ps_sim *s, uint32_t gen, uint32_t gens, bool light
     PSCHK(launch_acc_step(acc, s->m_idx[slot], gen, true, true, sa, s->d_idx[slot], want_snap));
     }
     HIPCHK(hipEventRecord(s->ev_idx[slot], sa));
+    // recorded ancestry: the slot's parents are complete on this stream (both draw paths, the G == 0 copy included) and stay
+    // until the slot's next use, which this stream orders behind the copy; behind ev_idx, so the sweep does not wait for it
+    if (s->anc_capacity) {
+        HIPCHK(hipMemcpyAsync(s->d_anc + (s->anc_written % s->anc_capacity) * N, s->d_idx[slot], N * sizeof(uint32_t), hipMemcpyDeviceToDevice, sa));
+        s->anc_written++;
+    }
     // Heavy HGT (cfg3-like rates, >= 1e7 expected events): its scattered loads and the streaming
     // sweep slow each other down far more than their sum, so they take turns on the chip:
     // HGT(g) runs after sweep(g-1) has finished and before sweep(g) starts, and the host half of
@@ -4097,6 +4117,7 @@ extern "C" int ps_sim_run(ps_sim *s, uint32_t first_generation, uint32_t count)
 {
     if (!s) return ps_fail(PS_ERR_INVALID, "null handle");
     PSCHK(use_device(s->core));
+    if ((uint64_t)first_generation != s->gens_done) s->anc_written = 0;      // (not the next generation of the recorded ones)
     // blocks of T generations per sweep launch, then the remainder one by one (a run split anywhere gives the same state:
     // every generation is keyed on its own number, whichever launch carries it)
     const uint32_t T = sim_sweep_generations(s);
@@ -4932,6 +4953,10 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // nearest neighbours of all pairs and rank-k lineages (ps_nearest_neighbours, ps_neighbours_from_counts, ps_lineages_from_neighbours, ps_multi_*)
 #include "nearest_neighbours.h"
+
+// recorded genealogy (ps_sim_record_ancestry, ps_sim_genealogy, ps_genealogy_*) and the clock histogram over all pairs
+#include "genealogy.h"
+#include "clock_histogram.h"
 
 // the native RCCL provider of ps_exchange_fn (ps_rccl_*, ps_exchange_rccl)
 #include "exchange_rccl.h"

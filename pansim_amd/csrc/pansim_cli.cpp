@@ -62,6 +62,9 @@ static const Flag EXT_FLAGS[] = {
     { "tree_metric", "Distance of --print_tree: core or acc.", "core", true },
     { "print_knn", "Write the <print_knn> nearest neighbours of every individual of the final population -- among ALL others, under the distance chosen by --knn_metric, ordered by (distance, row) -- to <outpref>_knn.tsv (row, rank from 1, neighbour, num, den, distance; the distance is num / den, NaN for an undefined one), the lineages at rank <print_knn> -- the connected components of the graph of those neighbours -- to <outpref>_lineages.tsv (row, label: the smallest row of its lineage) and the summary, with the number of lineages and the largest one at every rank up to <print_knn>, to <outpref>_knn_summary.tsv (docs/NEAREST_NEIGHBOURS.md), beside the usual outputs. Must be 1 <= X <= min(pop_size - 1, 128).", "", true },
     { "knn_metric", "Distance of --print_knn: core or acc.", "core", true },
+    { "print_genealogy", "Record the parent draws of the last <print_genealogy> generations on the device and write the true genealogy of the final population: the comb to <outpref>_genealogy.tsv (rank, row, coal per individual in the order the engine stores them: coal is the number of generations back at which the individual and the next one share an ancestor, \"beyond\" when the record does not reach it, empty on the last line), its trees to <outpref>_genealogy.nwk (Newick, one line per root, branch lengths in generations), and ALL pairs binned by (divergence time, distance) to <outpref>_clock.tsv (time_bin, dist_bin, count per non-empty bin; time bin <Bt> holds the pairs beyond the record) with the summary and the mean distance per time bin in <outpref>_clock_summary.tsv (docs/GENEALOGY.md), beside the usual outputs. Must be a whole number >= 1. After --load_state the record starts at the loaded generation.", "", true },
+    { "clock_bins", "Bins of --print_genealogy's clock histogram as <Bt>,<Bx> (time, distance): both at least 1, Bt at most 1024, (Bt + 1) x Bx at most 16384.", "32,64", true },
+    { "clock_metric", "Distance of --print_genealogy's clock histogram: core or acc.", "core", true },
     { "load_state", "Start from a state file instead of a clonal population: --n_gen stays the TOTAL, generations [saved, n_gen) are run. pop_size, core_size, pan_genes and core_genes must be the file's; every other flag is this command line's (the same flags continue the saved run bit for bit, other flags branch off it). With --print_dist the earlier rows of _per_gen.tsv come from the file, which must have been saved with --print_dist. One shard only (--gpus 1).", "", true },
 };
 
@@ -362,6 +365,32 @@ int main(int argc, char **argv)
             die(101, "pansim: --print_knn must be 1 <= X <= min(pop_size - 1, 128), not " + t + " with --pop_size " + std::to_string(p.pop_size));
         knn_prm.k = (uint32_t)k;
     }
+    // --print_genealogy: the bins and the metric of its clock histogram are checked whether or not it is given
+    ps_clock_params clock_prm = { PS_KNN_CORE, 32, 64, 0, 0 };
+    if (val["clock_metric"] == "acc") clock_prm.metric = PS_KNN_ACC;
+    else if (val["clock_metric"] != "core") die(101, "pansim: --clock_metric must be core or acc, not \"" + val["clock_metric"] + "\"");
+    {
+        const std::string &b = val["clock_bins"];
+        unsigned long long bt = 0, bx = 0;
+        int used = 0;
+        if (sscanf(b.c_str(), "%llu,%llu%n", &bt, &bx, &used) != 2 || (size_t)used != b.size() || b.find_first_of("+- ") != std::string::npos)
+            die(101, "pansim: --clock_bins must be <Bt>,<Bx> (two whole numbers), not \"" + b + "\"");
+        if (bt < 1 || bx < 1) die(101, "pansim: --clock_bins must be at least 1 on both axes");
+        if (bt > 1024 || bx > 16384 || (bt + 1) * bx > 16384)
+            die(101, "pansim: --clock_bins " + b + ": Bt must be at most 1024 and (Bt + 1) x Bx at most 16384");
+        clock_prm.time_bins = (uint32_t)bt;
+        clock_prm.dist_bins = (uint32_t)bx;
+    }
+    uint32_t record_capacity = 0;
+    if (!val["print_genealogy"].empty()) {
+        const std::string &t = val["print_genealogy"];
+        unsigned long long c = 0;
+        int used = 0;
+        if (sscanf(t.c_str(), "%llu%n", &c, &used) != 1 || (size_t)used != t.size() || t.find_first_of("+- ") != std::string::npos)
+            die(101, "pansim: --print_genealogy must be a whole number, not \"" + t + "\"");
+        if (c < 1 || c > 0xffffffffull) die(101, "pansim: --print_genealogy must be 1 <= X < 2^32 generations, not " + t);
+        record_capacity = (uint32_t)c;
+    }
     const uint64_t G = d.pan_size, P = p.max_distances;
     std::vector<double> avg_core(p.n_gen), avg_acc(p.n_gen), std_core(p.n_gen), std_acc(p.n_gen);
     // a fresh run goes through ps_multi (one shard: the plain run); a LOADED run is a plain ps_sim, driven by the ps_sim_*
@@ -392,6 +421,7 @@ int main(int argc, char **argv)
         CK(ps_multi_create(&p, (int)n_shards, nullptr, &multi));
         sim = ps_multi_shard(multi, 0);
     }
+    if (record_capacity) CK(multi ? ps_multi_record_ancestry(multi, record_capacity) : ps_sim_record_ancestry(sim, record_capacity));
     auto run = [&](uint32_t first, uint32_t count) { return multi ? ps_multi_run(multi, first, count) : ps_sim_run(sim, first, count); };
     auto sync = [&]() { return multi ? ps_multi_sync(multi) : ps_sim_sync(sim); };
     auto distances = [&](double *c, double *a) { return multi ? ps_multi_pairwise_distances(multi, c, a) : ps_sim_pairwise_distances(sim, c, a); };
@@ -544,6 +574,57 @@ int main(int argc, char **argv)
             if (!f) die(1, "Error: cannot create " + outpref + "_lineages.tsv");
             for (size_t i = 0; i < n; i++) fprintf(f, "%llu\t%u\n", (unsigned long long)i, labels[i]);
             fclose(f);
+        }
+        if (record_capacity) {                                         // (no counterpart in the reference: docs/GENEALOGY.md)
+            const size_t n = (size_t)p.pop_size;
+            std::vector<uint32_t> order(n), coal(n);
+            ps_genealogy_t g;
+            CK(multi ? ps_multi_genealogy(multi, &g, order.data(), coal.data()) : ps_sim_genealogy(sim, &g, order.data(), coal.data()));
+            FILE *f = fopen((outpref + "_genealogy.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_genealogy.tsv");
+            for (size_t r = 0; r < n; r++) {
+                if (r + 1 == n) fprintf(f, "%llu\t%u\t\n", (unsigned long long)r, order[r]);
+                else if (coal[r] == PS_GEN_BEYOND) fprintf(f, "%llu\t%u\tbeyond\n", (unsigned long long)r, order[r]);
+                else fprintf(f, "%llu\t%u\t%u\n", (unsigned long long)r, order[r], coal[r]);
+            }
+            fclose(f);
+            uint64_t need = 0;
+            CK(ps_genealogy_newick(order.data(), coal.data(), n, nullptr, 0, &need));
+            std::vector<char> text(need);
+            CK(ps_genealogy_newick(order.data(), coal.data(), n, text.data(), need, &need));
+            f = fopen((outpref + "_genealogy.nwk").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_genealogy.nwk");
+            fputs(text.data(), f);
+            fclose(f);
+            // (a run that recorded no generation -- a loaded state already at --n_gen -- has no divergence times to bin)
+            if (g.depth == 0) fprintf(stderr, "pansim: no generation was recorded: %s_clock.tsv and %s_clock_summary.tsv are not written\n", outpref.c_str(), outpref.c_str());
+            else {
+                const size_t nt = (size_t)clock_prm.time_bins + 1, bx = clock_prm.dist_bins;
+                std::vector<uint64_t> joint(nt * bx), per_time(3 * nt);
+                ps_clock_t c;
+                CK(multi ? ps_multi_clock_histogram(multi, &clock_prm, &c, joint.data(), per_time.data())
+                         : ps_sim_clock_histogram(sim, &clock_prm, &c, joint.data(), per_time.data()));
+                f = fopen((outpref + "_clock.tsv").c_str(), "w");
+                if (!f) die(1, "Error: cannot create " + outpref + "_clock.tsv");
+                for (size_t t = 0; t < nt; t++)
+                    for (size_t x = 0; x < bx; x++)
+                        if (joint[t * bx + x]) fprintf(f, "%llu\t%llu\t%llu\n", (unsigned long long)t, (unsigned long long)x, (unsigned long long)joint[t * bx + x]);
+                fclose(f);
+                f = fopen((outpref + "_clock_summary.tsv").c_str(), "w");
+                if (!f) die(1, "Error: cannot create " + outpref + "_clock_summary.tsv");
+                const std::pair<const char *, uint64_t> fields[] = {
+                    { "pop_size", c.pop_size }, { "pairs", c.pairs }, { "core_sites", c.core_sites }, { "core_genes", c.core_genes },
+                    { "metric", c.metric }, { "time_bins", c.time_bins }, { "dist_bins", c.dist_bins }, { "time_span", c.time_span },
+                    { "core_span", c.core_span }, { "generation", g.generation }, { "capacity", g.capacity }, { "depth", c.depth },
+                    { "roots", g.roots }, { "tmrca", g.tmrca }, { "undefined_pairs", c.undefined_pairs }, { "core_clamped", c.core_clamped },
+                    { "beyond_pairs", c.beyond_pairs }, { "binned_pairs", c.binned_pairs }, { "num_sum", c.num_sum }, { "den_sum", c.den_sum } };
+                for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+                for (size_t t = 0; t < nt; t++)
+                    if (per_time[3 * t])
+                        fprintf(f, "time\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)t, (unsigned long long)per_time[3 * t],
+                                (unsigned long long)per_time[3 * t + 1], (unsigned long long)per_time[3 * t + 2]);
+                fclose(f);
+            }
         }
     };
     if (!stepwise && p.n_gen > g0) CK(run((uint32_t)g0, (uint32_t)(p.n_gen - g0)));      // main.rs:429-464

@@ -258,6 +258,30 @@ class Simulation:
         from .population import _knn_call, _knn_params
         return _knn_call(self._lib.ps_sim_nearest_neighbours, _knn_params(k, metric), self.params.pop_size, self._h)
 
+    # -- the recorded genealogy (docs/GENEALOGY.md) --------------------------------------
+    def record_ancestry(self, capacity):
+        """keep the parent draws of the last `capacity` generations on the device (ps_sim_record_ancestry); 0 switches the
+        recording off.  The matrices of the run do not change by a bit."""
+        check(self._lib.ps_sim_record_ancestry(self._h, int(capacity)))
+
+    def genealogy(self):
+        """the comb of the present population from the recorded draws (ps_sim_genealogy) -> a GenealogyResult with order,
+        coal, pair(i, j), clusters(t), newick(); rows in the reference's row order"""
+        from .genealogy import _genealogy_call
+        return _genealogy_call(self._lib.ps_sim_genealogy, self.params.pop_size, self._h)
+
+    def clock_histogram(self, metric="core", time_bins=32, dist_bins=64, time_span=None, core_max=None, core_span=None):
+        """ALL pairs binned by (divergence time from the record, distance) (ps_sim_clock_histogram) -> a ClockHistogram"""
+        from .genealogy import _clock_call, _clock_params
+        prm = _clock_params(metric, time_bins, dist_bins, time_span, core_max, self.params.core_size, core_span)
+        return _clock_call(self._lib.ps_sim_clock_histogram, prm, self._h)
+
+    def clock_histogram_timing(self):
+        """device ms of (the count kernels; the comb, the table and the binning) of the last clock_histogram()"""
+        t = [C.c_double(), C.c_double()]
+        check(self._lib.ps_clock_histogram_timing(self._lib.ps_sim_core(self._h), *map(C.byref, t)))
+        return tuple(x.value for x in t)
+
     def write_outputs(self, outpref):
         core, acc = self.final_distances()
         with open(outpref + ".tsv", "w") as f:                       # main.rs:474-482
@@ -370,6 +394,27 @@ class MultiSimulation:
         against its accessory replica (ps_multi_nearest_neighbours)"""
         from .population import _knn_call, _knn_params
         return _knn_call(self._lib.ps_multi_nearest_neighbours, _knn_params(k, metric), self.params.pop_size, self._h)
+
+    def record_ancestry(self, capacity):
+        """Simulation.record_ancestry() for the sharded run: every shard draws the same parents, shard 0 records alone
+        (ps_multi_record_ancestry)"""
+        check(self._lib.ps_multi_record_ancestry(self._h, int(capacity)))
+
+    def genealogy(self):
+        """Simulation.genealogy() from shard 0's record (ps_multi_genealogy)"""
+        from .genealogy import _genealogy_call
+        return _genealogy_call(self._lib.ps_multi_genealogy, self.params.pop_size, self._h)
+
+    def clock_histogram(self, metric="core", time_bins=32, dist_bins=64, time_span=None, core_max=None, core_span=None):
+        """Simulation.clock_histogram() over ALL core sites: the shards' band counts added on shard 0, binned against its
+        record and accessory replica (ps_multi_clock_histogram)"""
+        from .genealogy import _clock_call, _clock_params
+        prm = _clock_params(metric, time_bins, dist_bins, time_span, core_max, self.params.core_size, core_span)
+        return _clock_call(self._lib.ps_multi_clock_histogram, prm, self._h)
+
+    def clock_histogram_timing(self):
+        """device ms of (the count kernels; the comb, the table and the binning) of the last clock_histogram() (shard 0's handle)"""
+        return self.shards[0].clock_histogram_timing()
 
     def write(self, outpref):
         check(self._lib.ps_multi_write(self._h, str(outpref).encode()))
