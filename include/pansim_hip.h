@@ -791,6 +791,71 @@ int ps_clock_from_counts(const uint32_t *tmrca, const uint32_t *core_h, const ui
  * population.rs:787-837): the count kernels of the metric; the comb, the table and the binning.  PS_ERR_STATE before any call. */
 int ps_clock_histogram_timing(ps_population *core, double *counts_ms, double *binning_ms);
 
+/* Linkage disequilibrium between LOCI (docs/LINKAGE_DISEQUILIBRIUM.md) -- the other axis of the two matrices: r^2 and the
+ * four-gamete test over all pairs of the selected columns, binned by r^2 and by the distance between the columns.  The reference
+ * has no such function (the signature of its recombination is read off population.rs:544-751, the counts are those of :840-863).
+ * A locus is a column: a core site (indicator: the cell equals the site's major base -- the most frequent of the bytes 1, 2, 4, 8,
+ * ties to the lowest byte; any other cell is 0) or an accessory gene (indicator: presence).  c = the ones of a locus over the N =
+ * pop_size individuals; c == 0 or c == N is monomorphic.  Selection: an explicit strictly ascending list (monomorphic entries
+ * kept), or automatically the C columns with min(c, N - c) >= min_minor in column order, all of them if C <= max_loci, else
+ * entry j = the candidate of rank floor(j C / max_loci).  Per pair a < b of the list, columns s_a < s_b, n11 = the individuals
+ * with both indicators set: a pair with a monomorphic locus is counted in undefined_pairs and nowhere else; otherwise
+ * D = N n11 - c_a c_b, den = c_a (N - c_a) c_b (N - c_b), q = floor(2^16 D^2 / den) in [0, 65536], r^2 bin = min(r2_bins - 1,
+ * (q r2_bins) >> 16), lag bin = min(lag_bins - 1, floor(log2(s_b - s_a))), hist[lag * r2_bins + r2] += 1, lag_sum_q[lag] += q.
+ * Every result but mean_r2 is an integer: nothing depends on the launch geometry, the bands, the sharding or the order of the
+ * individuals.  Limits: pop_size <= 65536, max_loci (or n_loci) <= 65536, min_minor >= 1, r2_bins >= 1, 1 <= lag_bins <= 32,
+ * r2_bins x lag_bins <= 16384; else PS_ERR_INVALID.  Fewer than two loci is not an error: no pairs. */
+#define PS_LD_CORE 0
+#define PS_LD_ACC 1
+#define PS_LD_MAX_LOCI 65536u
+typedef struct {
+    uint32_t r2_bins, lag_bins;
+    uint32_t min_minor;                /* automatic selection: candidates have min(c, N - c) >= min_minor */
+    uint32_t max_loci;                 /* automatic selection: at most this many loci */
+} ps_ld_params;
+typedef struct {
+    uint64_t pop_size, columns;
+    uint64_t candidates;               /* C of the automatic selection; the polymorphic entries of an explicit list */
+    uint64_t loci;                     /* M */
+    uint64_t pairs, defined_pairs, undefined_pairs;        /* pairs = M (M - 1) / 2 = defined + undefined */
+    uint64_t four_gamete_pairs;        /* all four combinations present */
+    uint64_t complete_pairs;           /* q == 65536 */
+    uint64_t positive_pairs, negative_pairs;               /* D > 0, D < 0 */
+    uint64_t sum_q;
+    double mean_r2;                    /* (double)sum_q / 65536.0 / (double)defined_pairs; 0.0 without defined pairs */
+    uint64_t r2_bins, lag_bins, min_minor, max_loci;
+} ps_ld_t;
+/* One handle, core or accessory by its kind (the reference has no such function; population.rs:544-751, :840-863).  loci ==
+ * NULL: automatic selection; else n_loci column indices.  locus_index, locus_count (either may be NULL): max_loci entries
+ * (n_loci when explicit), the first out->loci written.  hist: lag_bins x r2_bins values; lag_sum_q: lag_bins.  Ordered behind
+ * all queued work of the handle (a two-generation sweep launch included); changes no state.  PS_ERR_NO_DEVICE before anything
+ * else when no GPU is visible; a site shard fails with a message that points to ps_multi_locus_ld. */
+int ps_locus_ld(ps_population *p, const ps_ld_params *prm, const uint32_t *loci, uint32_t n_loci, ps_ld_t *out, uint32_t *locus_index,
+                uint32_t *locus_count, uint64_t *hist, uint64_t *lag_sum_q);
+/* The same for one matrix of a simulation, metric PS_LD_CORE or PS_LD_ACC (the reference has no such function;
+ * population.rs:544-751, :840-863) */
+int ps_sim_locus_ld(ps_sim *s, int32_t metric, const ps_ld_params *prm, const uint32_t *loci, uint32_t n_loci, ps_ld_t *out,
+                    uint32_t *locus_index, uint32_t *locus_count, uint64_t *hist, uint64_t *lag_sum_q);
+/* The same for a sharded run (the reference has no such function; population.rs:544-751, :840-863).  Core: every shard counts
+ * and packs its own selected sites (candidate ranks offset by the shards before it), the bit rows travel to shard 0, which
+ * contracts and bins; column indices are global.  Accessory: shard 0's replica. */
+int ps_multi_locus_ld(ps_multi *m, int32_t metric, const ps_ld_params *prm, const uint32_t *loci, uint32_t n_loci, ps_ld_t *out,
+                      uint32_t *locus_index, uint32_t *locus_count, uint64_t *hist, uint64_t *lag_sum_q);
+/* The automatic selection on the host alone (no device is touched, as ps_histogram_from_counts; the reference has no such
+ * function; population.rs:840-863): ones[col] = c of every column; index has room for max_loci entries. */
+int ps_ld_select_loci(const uint32_t *ones, uint64_t columns, uint64_t pop_size, uint32_t min_minor, uint32_t max_loci, uint32_t *index,
+                      uint64_t *n_loci, uint64_t *candidates);
+/* The per-pair rules on the host alone (no device is touched; the reference has no such function; population.rs:544-751,
+ * :840-863): n_loci loci with strictly ascending locus_index and their counts, n11 of the n_loci (n_loci - 1) / 2 pairs (a, b),
+ * a < b, row-major (NULL when n_loci < 2).  A count above pop_size, or an n11 that the two counts do not allow, is
+ * PS_ERR_INVALID.  out->columns and out->candidates are 0. */
+int ps_ld_from_counts(const uint32_t *locus_index, const uint32_t *locus_count, const uint32_t *n11, uint64_t n_loci, uint64_t pop_size,
+                      const ps_ld_params *prm, ps_ld_t *out, uint64_t *hist, uint64_t *lag_sum_q);
+/* device ms of the last ps_locus_ld on this handle (shard 0's core handle after ps_multi_locus_ld; HIP events; the reference has
+ * no such function; population.rs:544-751): counts and selection, packing, the contraction, the pair statistics.  PS_ERR_STATE
+ * before any call. */
+int ps_locus_ld_timing(ps_population *p, double *select_ms, double *pack_ms, double *counts_ms, double *stats_ms);
+
 #ifdef __cplusplus
 }
 #endif

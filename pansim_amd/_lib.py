@@ -141,6 +141,22 @@ class GenClusters(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("clusters", "largest", "within_pairs")]
 
 
+PS_LD_CORE, PS_LD_ACC, PS_LD_MAX_LOCI = 0, 1, 65536
+
+
+class LdParams(C.Structure):
+    """ps_ld_params: the bins and the automatic selection of ps_locus_ld (docs/LINKAGE_DISEQUILIBRIUM.md)"""
+    _fields_ = [("r2_bins", C.c_uint32), ("lag_bins", C.c_uint32), ("min_minor", C.c_uint32), ("max_loci", C.c_uint32)]
+
+
+class Ld(C.Structure):
+    """ps_ld_t: the summary of ps_locus_ld / ps_ld_from_counts"""
+    _fields_ = ([(name, C.c_uint64) for name in ("pop_size", "columns", "candidates", "loci", "pairs", "defined_pairs", "undefined_pairs",
+                                                  "four_gamete_pairs", "complete_pairs", "positive_pairs", "negative_pairs", "sum_q")]
+                + [("mean_r2", C.c_double)]
+                + [(name, C.c_uint64) for name in ("r2_bins", "lag_bins", "min_minor", "max_loci")])
+
+
 class ClockParams(C.Structure):
     """ps_clock_params: the metric, bins and spans of ps_sim_clock_histogram (docs/GENEALOGY.md); a span of 0 = automatic"""
     _fields_ = [("metric", C.c_int32), ("time_bins", C.c_uint32), ("dist_bins", C.c_uint32), ("time_span", C.c_uint64),
@@ -287,6 +303,12 @@ SIGNATURES = {
     "ps_multi_clock_histogram": (_int, [_vp, C.POINTER(ClockParams), C.POINTER(Clock), _vp, _vp]),
     "ps_clock_from_counts": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(ClockParams), C.POINTER(Clock), _vp, _vp]),
     "ps_clock_histogram_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_locus_ld": (_int, [_vp, C.POINTER(LdParams), _vp, _u32, C.POINTER(Ld), _vp, _vp, _vp, _vp]),
+    "ps_sim_locus_ld": (_int, [_vp, C.c_int32, C.POINTER(LdParams), _vp, _u32, C.POINTER(Ld), _vp, _vp, _vp, _vp]),
+    "ps_multi_locus_ld": (_int, [_vp, C.c_int32, C.POINTER(LdParams), _vp, _u32, C.POINTER(Ld), _vp, _vp, _vp, _vp]),
+    "ps_ld_select_loci": (_int, [_vp, _u64, _u64, _u32, _u32, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "ps_ld_from_counts": (_int, [_vp, _vp, _vp, _u64, _u64, C.POINTER(LdParams), C.POINTER(Ld), _vp, _vp]),
+    "ps_locus_ld_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

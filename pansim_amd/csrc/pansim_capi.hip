@@ -337,6 +337,13 @@ struct ps_population {
     uint64_t gen_cap = 0;                   // (bytes)
     double clock_ms[2] = {};                // counts, comb + table + binning
     bool clock_timed = false;
+    // linkage disequilibrium of loci (locus_ld.h), on the handle asked: the selection scratch (column counts, flags, tile sums),
+    // the call's scratch (summary words, bins, list, bit rows, landing rows, one band of n11); the last call's times
+    void *d_ld_sel = nullptr, *d_ld = nullptr;
+    uint64_t ld_sel_cap = 0, ld_cap = 0;    // (bytes)
+    uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
+    double ld_ms[4] = {};                   // select, pack, counts, stats
+    bool ld_timed = false;
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
     unsigned long long *h_stamps = nullptr, *d_stamps = nullptr;   // diagnostic phase stamps
 };
@@ -418,7 +425,7 @@ extern "C" void ps_population_destroy(ps_population *p)
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     void *ptrs[] = { p->d_row_slot, p->state, p->state2, p->d_delta, p->hgt_ovf_img, p->G[0], p->G[1], p->I[0], p->I[1], p->I_snap, p->d_ptab[0], p->d_ptab[1], p->hgt_scratch, p->cnt, p->d_idx, p->d_idxT, p->d_work,
-                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg, p->d_cl, p->d_tree, p->d_knn, p->d_gen };
+                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg, p->d_cl, p->d_tree, p->d_knn, p->d_gen, p->d_ld_sel, p->d_ld };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (int c = 2; c < PS_MAX_COMP; c++)
@@ -647,6 +654,9 @@ extern "C" int ps_set_tuning(ps_population *p, const char *key, int64_t value)
         if (value < 0 || value > 3)
             return ps_fail(PS_ERR_INVALID, "core_davg_form must be 0 (choose), 1 (whole matrix), 2 (banded) or 3 (generic)");
         p->core_davg_form = (int)value;
+    } else if (k == "ld_band") {
+        if (value < 0 || value > 65536) return ps_fail(PS_ERR_INVALID, "ld_band must be 0 (choose)..65536 rows of loci");
+        p->ld_band = (uint32_t)value;
     } else if (k == "core_davg_band") {
         if (value < 0 || value > (1ll << 31)) return ps_fail(PS_ERR_INVALID, "core_davg_band must be 0 (choose)..2^31 rows");
         p->core_davg_band = (uint32_t)value;
@@ -2129,18 +2139,25 @@ static int acc_rows_padded(ps_population *p, hipStream_t st, acc_padded *o)
 // The contraction on every SIMD: In[row - lo][j] = |row AND j| for the rows [lo, lo + rows) x all columns, in p->d_davg_in, sized
 // for bands of `band` rows (a wave stores 32 * nb whole rows, at most 128: `band` is a multiple of that).  nb = B fragments per
 // wave (4, 2, else 1).
-static int acc_intersections_band(ps_population *p, const acc_padded &R, uint32_t nb, uint64_t band, uint32_t lo, uint32_t rows, hipStream_t st)
+// The launch itself, on any padded blocked bit rows (rows of WP dwords, Npad of them) into any scratch `In` of pitch ld that holds
+// `rows` rounded up to 32 * nb whole rows: what a row means is the caller's business (individuals here, loci in locus_ld.h).
+static int acc_intersections_launch(const uint32_t *rowsP, uint32_t WP, uint32_t Npad, uint32_t ld, uint32_t nb, uint32_t lo, uint32_t rows,
+                                    uint16_t *In, hipStream_t st)
 {
-    PSCHK(dev_grow(p->d_davg_in, p->davg_in_cap, band * R.ld * 2));
-    const uint32_t lds = 256u * 64u * 4u, steps = R.Npad / 128u, gx = (rows + 128u * nb - 1u) / (128u * nb);
+    const uint32_t lds = 256u * 64u * 4u, steps = Npad / 128u, gx = (rows + 128u * nb - 1u) / (128u * nb);
     uint32_t jsteps = 8u;
     while (jsteps > 1u && (uint64_t)gx * ((steps + jsteps - 1u) / jsteps) < 2048u) jsteps >>= 1;
     auto kern = nb == 4u ? acc_intersections_mfma_kernel<4u> : nb == 2u ? acc_intersections_mfma_kernel<2u> : acc_intersections_mfma_kernel<1u>;
     HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(gx, (steps + jsteps - 1u) / jsteps), dim3(256), lds, st, (const uint32_t *)R.rowsP, R.WP, R.Npad, lo, rows,
-                       jsteps, (uint16_t *)p->d_davg_in, R.ld);
+    hipLaunchKernelGGL(kern, dim3(gx, (steps + jsteps - 1u) / jsteps), dim3(256), lds, st, rowsP, WP, Npad, lo, rows, jsteps, In, ld);
     HIPCHK(hipGetLastError());
     return PS_OK;
+}
+
+static int acc_intersections_band(ps_population *p, const acc_padded &R, uint32_t nb, uint64_t band, uint32_t lo, uint32_t rows, hipStream_t st)
+{
+    PSCHK(dev_grow(p->d_davg_in, p->davg_in_cap, band * R.ld * 2));
+    return acc_intersections_launch((const uint32_t *)R.rowsP, R.WP, R.Npad, R.ld, nb, lo, rows, (uint16_t *)p->d_davg_in, st);
 }
 
 // D-avg (population.rs:753-784) into a device buffer of N doubles.  Rows [i_lo, i_lo + i_cnt) only (a row shard of a
@@ -4957,6 +4974,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 // recorded genealogy (ps_sim_record_ancestry, ps_sim_genealogy, ps_genealogy_*) and the clock histogram over all pairs
 #include "genealogy.h"
 #include "clock_histogram.h"
+
+// linkage disequilibrium of loci (ps_locus_ld, ps_ld_select_loci, ps_ld_from_counts, ps_sim_* and ps_multi_*)
+#include "locus_ld.h"
 
 // the native RCCL provider of ps_exchange_fn (ps_rccl_*, ps_exchange_rccl)
 #include "exchange_rccl.h"

@@ -65,6 +65,11 @@ static const Flag EXT_FLAGS[] = {
     { "print_genealogy", "Record the parent draws of the last <print_genealogy> generations on the device and write the true genealogy of the final population: the comb to <outpref>_genealogy.tsv (rank, row, coal per individual in the order the engine stores them: coal is the number of generations back at which the individual and the next one share an ancestor, \"beyond\" when the record does not reach it, empty on the last line), its trees to <outpref>_genealogy.nwk (Newick, one line per root, branch lengths in generations), and ALL pairs binned by (divergence time, distance) to <outpref>_clock.tsv (time_bin, dist_bin, count per non-empty bin; time bin <Bt> holds the pairs beyond the record) with the summary and the mean distance per time bin in <outpref>_clock_summary.tsv (docs/GENEALOGY.md), beside the usual outputs. Must be a whole number >= 1. After --load_state the record starts at the loaded generation.", "", true },
     { "clock_bins", "Bins of --print_genealogy's clock histogram as <Bt>,<Bx> (time, distance): both at least 1, Bt at most 1024, (Bt + 1) x Bx at most 16384.", "32,64", true },
     { "clock_metric", "Distance of --print_genealogy's clock histogram: core or acc.", "core", true },
+    { "print_ld", "Write the linkage disequilibrium between the loci of the final population -- r^2 and the four-gamete test over all pairs of the selected core sites or accessory genes (--ld_metric) -- to <outpref>_ld.tsv (lag_bin, r2_bin, count per non-empty bin; the lag bin is the floor of log2 of the distance between the two columns), its summary with the pairs and the sum of 65536 r^2 per lag bin to <outpref>_ld_summary.tsv and the selected loci to <outpref>_ld_loci.tsv (column, count) (docs/LINKAGE_DISEQUILIBRIUM.md), beside the usual outputs.", nullptr, false },
+    { "ld_metric", "Loci of --print_ld: core (sites) or acc (genes).", "core", true },
+    { "ld_max_loci", "Largest number of loci of --print_ld; more candidates are thinned evenly. Must be 1 <= X <= 65536.", "4096", true },
+    { "ld_min_minor", "Smallest minor count of a locus of --print_ld. Must be a whole number >= 1.", "1", true },
+    { "ld_bins", "Bins of --print_ld as <r2>,<lag>: both at least 1, lag at most 32, their product at most 16384.", "64,1", true },
     { "load_state", "Start from a state file instead of a clonal population: --n_gen stays the TOTAL, generations [saved, n_gen) are run. pop_size, core_size, pan_genes and core_genes must be the file's; every other flag is this command line's (the same flags continue the saved run bit for bit, other flags branch off it). With --print_dist the earlier rows of _per_gen.tsv come from the file, which must have been saved with --print_dist. One shard only (--gpus 1).", "", true },
 };
 
@@ -381,6 +386,33 @@ int main(int argc, char **argv)
         clock_prm.time_bins = (uint32_t)bt;
         clock_prm.dist_bins = (uint32_t)bx;
     }
+    // --print_ld: its metric, bins and selection are checked whether or not it is given
+    ps_ld_params ld_prm = { 64, 1, 1, 4096 };
+    int32_t ld_metric = PS_LD_CORE;
+    if (val["ld_metric"] == "acc") ld_metric = PS_LD_ACC;
+    else if (val["ld_metric"] != "core") die(101, "pansim: --ld_metric must be core or acc, not \"" + val["ld_metric"] + "\"");
+    {
+        const std::string &b = val["ld_bins"];
+        unsigned long long br = 0, bl = 0;
+        int used = 0;
+        if (sscanf(b.c_str(), "%llu,%llu%n", &br, &bl, &used) != 2 || (size_t)used != b.size() || b.find_first_of("+- ") != std::string::npos)
+            die(101, "pansim: --ld_bins must be <r2>,<lag> (two whole numbers), not \"" + b + "\"");
+        if (br < 1 || bl < 1) die(101, "pansim: --ld_bins must be at least 1 on both axes");
+        if (bl > 32 || br > 16384 || br * bl > 16384)
+            die(101, "pansim: --ld_bins " + b + ": lag must be at most 32 and the product of the two at most 16384");
+        ld_prm.r2_bins = (uint32_t)br;
+        ld_prm.lag_bins = (uint32_t)bl;
+        const std::pair<const char *, uint32_t *> whole[] = { { "ld_max_loci", &ld_prm.max_loci }, { "ld_min_minor", &ld_prm.min_minor } };
+        for (const auto &w : whole) {
+            const std::string &t = val[w.first];
+            unsigned long long v = 0;
+            if (sscanf(t.c_str(), "%llu%n", &v, &used) != 1 || (size_t)used != t.size() || t.find_first_of("+- ") != std::string::npos)
+                die(101, std::string("pansim: --") + w.first + " must be a whole number, not \"" + t + "\"");
+            if (v < 1 || v > 0xffffffffull) die(101, std::string("pansim: --") + w.first + " must be at least 1 and below 2^32, not " + t);
+            *w.second = (uint32_t)v;
+        }
+        if (ld_prm.max_loci > PS_LD_MAX_LOCI) die(101, "pansim: --ld_max_loci must be 1 <= X <= 65536, not " + val["ld_max_loci"]);
+    }
     uint32_t record_capacity = 0;
     if (!val["print_genealogy"].empty()) {
         const std::string &t = val["print_genealogy"];
@@ -573,6 +605,40 @@ int main(int argc, char **argv)
             f = fopen((outpref + "_lineages.tsv").c_str(), "w");
             if (!f) die(1, "Error: cannot create " + outpref + "_lineages.tsv");
             for (size_t i = 0; i < n; i++) fprintf(f, "%llu\t%u\n", (unsigned long long)i, labels[i]);
+            fclose(f);
+        }
+        if (present["print_ld"]) {                                     // (no counterpart in the reference: docs/LINKAGE_DISEQUILIBRIUM.md)
+            const size_t nl = ld_prm.lag_bins, nr = ld_prm.r2_bins;
+            std::vector<uint32_t> index(ld_prm.max_loci), count(ld_prm.max_loci);
+            std::vector<uint64_t> hist(nl * nr), lag_sum(nl);
+            ps_ld_t t;
+            CK(multi ? ps_multi_locus_ld(multi, ld_metric, &ld_prm, nullptr, 0, &t, index.data(), count.data(), hist.data(), lag_sum.data())
+                     : ps_sim_locus_ld(sim, ld_metric, &ld_prm, nullptr, 0, &t, index.data(), count.data(), hist.data(), lag_sum.data()));
+            FILE *f = fopen((outpref + "_ld.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_ld.tsv");
+            for (size_t l = 0; l < nl; l++)
+                for (size_t r = 0; r < nr; r++)
+                    if (hist[l * nr + r]) fprintf(f, "%llu\t%llu\t%llu\n", (unsigned long long)l, (unsigned long long)r, (unsigned long long)hist[l * nr + r]);
+            fclose(f);
+            f = fopen((outpref + "_ld_summary.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_ld_summary.tsv");
+            const std::pair<const char *, uint64_t> fields[] = {
+                { "pop_size", t.pop_size }, { "metric", (uint64_t)ld_metric }, { "columns", t.columns }, { "candidates", t.candidates }, { "loci", t.loci },
+                { "pairs", t.pairs }, { "defined_pairs", t.defined_pairs }, { "undefined_pairs", t.undefined_pairs },
+                { "four_gamete_pairs", t.four_gamete_pairs }, { "complete_pairs", t.complete_pairs }, { "positive_pairs", t.positive_pairs },
+                { "negative_pairs", t.negative_pairs }, { "sum_q", t.sum_q }, { "r2_bins", t.r2_bins }, { "lag_bins", t.lag_bins },
+                { "min_minor", t.min_minor }, { "max_loci", t.max_loci } };
+            for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+            fprintf(f, "mean_r2\t%s\n", fmt(t.mean_r2).c_str());
+            for (size_t l = 0; l < nl; l++) {
+                uint64_t n = 0;
+                for (size_t r = 0; r < nr; r++) n += hist[l * nr + r];
+                if (n) fprintf(f, "lag\t%llu\t%llu\t%llu\n", (unsigned long long)l, (unsigned long long)n, (unsigned long long)lag_sum[l]);
+            }
+            fclose(f);
+            f = fopen((outpref + "_ld_loci.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_ld_loci.tsv");
+            for (uint64_t k = 0; k < t.loci; k++) fprintf(f, "%u\t%u\n", index[k], count[k]);
             fclose(f);
         }
         if (record_capacity) {                                         // (no counterpart in the reference: docs/GENEALOGY.md)

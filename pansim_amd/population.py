@@ -654,6 +654,20 @@ class Population:
         check(self._lib.ps_strain_clusters_timing(self._h, *map(C.byref, t)))
         return tuple(x.value for x in t)
 
+    def locus_ld(self, r2_bins=64, lag_bins=1, min_minor=1, max_loci=4096, loci=None):
+        """linkage disequilibrium between the columns of this handle -- core sites or accessory genes by its kind
+        (ps_locus_ld; docs/LINKAGE_DISEQUILIBRIUM.md) -> a LocusLd: r^2 and the four-gamete test over all pairs of the
+        selected loci, binned by r^2 and by log2 of the distance between the columns.  `loci`: an explicit strictly
+        ascending list of columns (None: the columns with minor count >= min_minor, thinned evenly to max_loci)."""
+        from .linkage import _ld_call, _ld_params
+        return _ld_call(self._lib.ps_locus_ld, _ld_params(r2_bins, lag_bins, min_minor, max_loci), loci, self._h)
+
+    def locus_ld_timing(self):
+        """device ms of (counts and selection, packing, the contraction, the pair statistics) of the last locus_ld()"""
+        t = [C.c_double() for _ in range(4)]
+        check(self._lib.ps_locus_ld_timing(self._h, *map(C.byref, t)))
+        return tuple(x.value for x in t)
+
     def core_diversity_timing(self):
         """device ms of the counts kernel of the last site_allele_counts() / core_diversity() call"""
         ms = C.c_double()

@@ -276,6 +276,13 @@ class Simulation:
         prm = _clock_params(metric, time_bins, dist_bins, time_span, core_max, self.params.core_size, core_span)
         return _clock_call(self._lib.ps_sim_clock_histogram, prm, self._h)
 
+    def locus_ld(self, metric="core", r2_bins=64, lag_bins=1, min_minor=1, max_loci=4096, loci=None):
+        """linkage disequilibrium between the core sites or the accessory genes of the run (ps_sim_locus_ld;
+        docs/LINKAGE_DISEQUILIBRIUM.md) -> a LocusLd"""
+        from .linkage import _ld_call, _ld_params, _metric
+        m = _metric(metric)
+        return _ld_call(self._lib.ps_sim_locus_ld, _ld_params(r2_bins, lag_bins, min_minor, max_loci), loci, self._h, m)
+
     def clock_histogram_timing(self):
         """device ms of (the count kernels; the comb, the table and the binning) of the last clock_histogram()"""
         t = [C.c_double(), C.c_double()]
@@ -411,6 +418,13 @@ class MultiSimulation:
         from .genealogy import _clock_call, _clock_params
         prm = _clock_params(metric, time_bins, dist_bins, time_span, core_max, self.params.core_size, core_span)
         return _clock_call(self._lib.ps_multi_clock_histogram, prm, self._h)
+
+    def locus_ld(self, metric="core", r2_bins=64, lag_bins=1, min_minor=1, max_loci=4096, loci=None):
+        """Simulation.locus_ld() over ALL core sites (every shard selects and packs its own, shard 0 contracts and bins) or
+        over shard 0's accessory replica (ps_multi_locus_ld); columns are global"""
+        from .linkage import _ld_call, _ld_params, _metric
+        m = _metric(metric)
+        return _ld_call(self._lib.ps_multi_locus_ld, _ld_params(r2_bins, lag_bins, min_minor, max_loci), loci, self._h, m)
 
     def clock_histogram_timing(self):
         """device ms of (the count kernels; the comb, the table and the binning) of the last clock_histogram() (shard 0's handle)"""
