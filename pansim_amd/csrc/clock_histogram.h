@@ -136,13 +136,10 @@ static int clock_launch(const pair_pipeline &pl, uint32_t lo, uint32_t nrows, co
 {
     const uint32_t N = (uint32_t)pl.c0->cfg.pop_size;
     const uint32_t nt = a.Bt + 1u, lds = nt * a.d.Bc * 4u + nt * 16u;
-    // the grid of pair_hist_launch: the rows over y, as many workgroups as the LDS lets a CU hold
-    const uint32_t gx = pair_grid_x(N);
-    const uint32_t per_cu = std::max(1u, std::min(8u, (160u * 1024u) / (lds + 256u)));
-    const uint32_t gy = std::max(1u, std::min(std::min(nrows, 65535u), 256u * per_cu / gx));
     auto kern = pair_clock_kernel<ACC>;
-    if (lds > 32768u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), lds, pl.sc, (const uint32_t *)pl.c0->d_cdavg, pl.src.b.ld, pl.In(), pl.A.ld,
+    dim3 grid;
+    PSCHK(bin_grid((const void *)kern, N, nrows, lds, 256u, &grid));
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, pl.sc, (const uint32_t *)pl.c0->d_cdavg, pl.src.b.ld, pl.In(), pl.A.ld,
                        (const uint32_t *)pl.A.rowcnt, table, N, lo, nrows, a, words, sums, joint);
     HIPCHK(hipGetLastError());
     return PS_OK;
@@ -170,7 +167,8 @@ static int clock_device(core_band_source &src, ps_sim *s, uint64_t L, const ps_c
     unsigned long long *words = (unsigned long long *)tail, *sums = words + PS_CK_WORDS, *d_joint = sums + 2 * nt;
     pair_pipeline pl(src, acc);
     hipStream_t sc = pl.sc;
-    c0->clock_timed = false;
+    readout_slot &ro = c0->ro[PS_RO_GEN];
+    ro.timed = false;
     HIPCHK(hipMemsetAsync(words, 0, n_words * sizeof(unsigned long long), sc));
     // timer groups: 0 = the count phase, 1 = the comb, the table and the binning
     PSCHK(pl.timed(1, sc, [&]() -> int {
@@ -181,10 +179,6 @@ static int clock_device(core_band_source &src, ps_sim *s, uint64_t L, const ps_c
         return PS_OK;
     }));
     PSCHK(pl.open(acc_metric));
-    auto for_bands = [&](auto &&body) -> int {
-        for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) PSCHK(body(lo, std::min(b.band, b.c_end - lo)));
-        return PS_OK;
-    };
     const uint64_t St = prm->time_span ? prm->time_span : depth;
     uint64_t S = acc_metric ? 1 : prm->core_span;
     auto bin_band = [&](uint32_t lo, uint32_t nrows) -> int {
@@ -194,24 +188,25 @@ static int clock_device(core_band_source &src, ps_sim *s, uint64_t L, const ps_c
         });
     };
     if (acc_metric) {
-        PSCHK(for_bands([&](uint32_t lo, uint32_t nrows) -> int {
+        PSCHK(pl.for_bands([&](uint32_t lo, uint32_t nrows) -> int {
             PSCHK(pl.acc_counts(0, lo, nrows));
             return bin_band(lo, nrows);
         }));
     } else if (S) {
-        PSCHK(for_bands([&](uint32_t lo, uint32_t nrows) -> int {
+        PSCHK(pl.for_bands([&](uint32_t lo, uint32_t nrows) -> int {
             PSCHK(pl.core_counts(0, lo, nrows));
             return bin_band(lo, nrows);
         }));
     } else {
         // the automatic span, as the histogram finds it: the moments pass of pair_hist_kernel into the histogram's own words
         // first; over one band the bins come from the same counts, over several the core contraction runs twice
-        PSCHK(dev_grow(c0->d_ph, c0->ph_cap, (uint64_t)PS_PH_WORDS));
-        unsigned long long *d_ph = c0->d_ph;
+        readout_slot &hist = c0->ro[PS_RO_HIST];
+        PSCHK(dev_grow(hist.d, hist.cap, PS_PH_WORDS * sizeof(unsigned long long)));
+        unsigned long long *d_ph = (unsigned long long *)hist.d;
         HIPCHK(hipMemsetAsync(d_ph, 0, PS_PH_WORDS * sizeof(unsigned long long), sc));
         HIPCHK(hipMemsetAsync(d_ph + PS_PH_MIN, 0xff, sizeof(unsigned long long), sc));
         const bool one_band = b.c_end - b.c0 <= b.band;
-        PSCHK(for_bands([&](uint32_t lo, uint32_t nrows) -> int {
+        PSCHK(pl.for_bands([&](uint32_t lo, uint32_t nrows) -> int {
             PSCHK(pl.core_counts(0, lo, nrows));
             return pl.consume(1, [&]() { return pair_hist_launch<false, true>(pl, lo, nrows, ps_ph_args{}, d_ph); });
         }));
@@ -219,7 +214,7 @@ static int clock_device(core_band_source &src, ps_sim *s, uint64_t L, const ps_c
         HIPCHK(hipMemcpyAsync(&mx, d_ph + PS_PH_MAX, sizeof mx, hipMemcpyDeviceToHost, sc));
         HIPCHK(hipStreamSynchronize(sc));
         S = mx + 1;
-        PSCHK(for_bands([&](uint32_t lo, uint32_t nrows) -> int {
+        PSCHK(pl.for_bands([&](uint32_t lo, uint32_t nrows) -> int {
             if (!one_band) PSCHK(pl.core_counts(0, lo, nrows));
             return bin_band(lo, nrows);
         }));
@@ -230,10 +225,7 @@ static int clock_device(core_band_source &src, ps_sim *s, uint64_t L, const ps_c
     HIPCHK(hipMemcpyAsync(w, words, sizeof w, hipMemcpyDeviceToHost, sc));
     HIPCHK(hipMemcpyAsync(hs.data(), sums, 2 * nt * sizeof(unsigned long long), hipMemcpyDeviceToHost, sc));
     HIPCHK(hipMemcpyAsync(joint, d_joint, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, sc));
-    HIPCHK(hipStreamSynchronize(pl.sa));
-    HIPCHK(hipStreamSynchronize(sc));
-    for (int which = 0; which < 2; which++) PSCHK(pl.total_ms(which, &c0->clock_ms[which]));
-    c0->clock_timed = true;
+    PSCHK(pl.finish(ro, 2));
     clock_fill(out, N, (uint64_t)N * (N - 1) / 2, L, cg, prm, St, S, depth);
     out->undefined_pairs = w[PS_CK_UNDEF];
     out->core_clamped = w[PS_CK_CLAMP];
@@ -259,14 +251,14 @@ static int clock_entry(ps_multi *m, ps_sim *s, const ps_clock_params *prm, ps_cl
 
 extern "C" int ps_sim_clock_histogram(ps_sim *s, const ps_clock_params *prm, ps_clock_t *out, uint64_t *joint, uint64_t *per_time)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!s || !prm || !out || !joint || !per_time) return ps_fail(PS_ERR_INVALID, "null argument");
     return clock_entry(nullptr, s, prm, out, joint, per_time);
 }
 
 extern "C" int ps_multi_clock_histogram(ps_multi *m, const ps_clock_params *prm, ps_clock_t *out, uint64_t *joint, uint64_t *per_time)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!m || !prm || !out || !joint || !per_time) return ps_fail(PS_ERR_INVALID, "null argument");
     if (m->shard.size() == 1) return ps_sim_clock_histogram(m->shard[0], prm, out, joint, per_time);
     return clock_entry(m, m->shard[0], prm, out, joint, per_time);
@@ -275,8 +267,5 @@ extern "C" int ps_multi_clock_histogram(ps_multi *m, const ps_clock_params *prm,
 extern "C" int ps_clock_histogram_timing(ps_population *core, double *counts_ms, double *binning_ms)
 {
     if (!core) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (!core->clock_timed) return ps_fail(PS_ERR_STATE, "no clock histogram has been computed on this handle");
-    if (counts_ms) *counts_ms = core->clock_ms[0];
-    if (binning_ms) *binning_ms = core->clock_ms[1];
-    return PS_OK;
+    return readout_timing(core->ro[PS_RO_GEN], "no clock histogram has been computed on this handle", { counts_ms, binning_ms });
 }

@@ -8,14 +8,6 @@
 
 #include "diversity_kernels.h"
 
-static int diversity_needs_device(void)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return ps_fail(PS_ERR_NO_DEVICE, "no HIP device is visible: libpansim_hip has no CPU path");
-    return PS_OK;
-}
-
 static int diversity_core_handle(const ps_population *p, const char *call)
 {
     if (!p->cfg.core)
@@ -68,7 +60,7 @@ static int launch_site_counts(ps_population *p, hipStream_t st)
 
 extern "C" int ps_site_allele_counts(ps_population *p, uint32_t *counts)
 {
-    PSCHK(diversity_needs_device());
+    PSCHK(ps_needs_device());
     if (!p || !counts) return ps_fail(PS_ERR_INVALID, "null argument");
     PSCHK(diversity_core_handle(p, "ps_site_allele_counts"));
     PSCHK(use_device(p));
@@ -81,7 +73,7 @@ extern "C" int ps_site_allele_counts(ps_population *p, uint32_t *counts)
 
 extern "C" int ps_core_diversity(ps_population *p, ps_core_diversity_t *out, uint64_t *spectrum)
 {
-    PSCHK(diversity_needs_device());
+    PSCHK(ps_needs_device());
     if (!p || !out) return ps_fail(PS_ERR_INVALID, "null argument");
     PSCHK(diversity_core_handle(p, "ps_core_diversity"));
     PSCHK(use_device(p));
@@ -146,7 +138,7 @@ extern "C" int ps_diversity_from_counts(const uint32_t *counts, uint64_t sites, 
 // the double is formed once over core_size.
 extern "C" int ps_multi_site_allele_counts(ps_multi *m, uint32_t *counts)
 {
-    PSCHK(diversity_needs_device());
+    PSCHK(ps_needs_device());
     if (!m || !counts) return ps_fail(PS_ERR_INVALID, "null argument");
     return multi_for_each(m, [&](size_t k) {
         ps_population *c = m->shard[k]->core;
@@ -156,7 +148,7 @@ extern "C" int ps_multi_site_allele_counts(ps_multi *m, uint32_t *counts)
 
 extern "C" int ps_multi_core_diversity(ps_multi *m, ps_core_diversity_t *out, uint64_t *spectrum)
 {
-    PSCHK(diversity_needs_device());
+    PSCHK(ps_needs_device());
     if (!m || !out) return ps_fail(PS_ERR_INVALID, "null argument");
     const size_t K = m->shard.size();
     const uint64_t bins = m->prm.pop_size + 1;

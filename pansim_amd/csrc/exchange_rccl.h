@@ -170,8 +170,7 @@ extern "C" int ps_rccl_exchange_create(const uint8_t *id, int rank, int world, i
     ps_rccl::api *a = ps_rccl::load();
     if (!a) return ps_fail(PS_ERR_NO_DEVICE, "%s", ps_rccl::why_not().c_str());
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return ps_fail(PS_ERR_NO_DEVICE, "no HIP device is visible: libpansim_hip has no CPU path");
+    PSCHK(ps_needs_device(&ndev));
     if (device < 0) HIPCHK(hipGetDevice(&device));
     if (device >= ndev) return ps_fail(PS_ERR_INVALID, "device %d out of range", device);
     HIPCHK(hipSetDevice(device));

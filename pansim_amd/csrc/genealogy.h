@@ -206,7 +206,7 @@ extern "C" int ps_genealogy_newick(const uint32_t *order, const uint32_t *coal, 
 
 extern "C" int ps_sim_record_ancestry(ps_sim *s, uint32_t capacity)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
     const uint64_t N = s->prm.pop_size;
     // capacity x N x 4 bytes in u64 arithmetic
@@ -222,23 +222,18 @@ extern "C" int ps_sim_record_ancestry(ps_sim *s, uint32_t capacity)
     s->anc_written = 0;
     if (!capacity) return PS_OK;
     const uint64_t bytes = (uint64_t)capacity * N * sizeof(uint32_t);
-    uint64_t cap = 0;
-    void *log = nullptr;
-    const hipError_t e = dev_grow_err(log, cap, bytes);
-    if (e != hipSuccess && !log) {
-        (void)hipGetLastError();
-        return ps_fail(PS_ERR_OOM, "cannot allocate the %llu bytes of a record of %u generations of %llu individuals", (unsigned long long)bytes, capacity,
-                       (unsigned long long)N);
-    }
-    HIPCHK(e);
-    s->d_anc = (uint32_t *)log;
+    readout_slot log;       // (only the holder of the allocation, which s->d_anc keeps)
+    uint8_t *base = nullptr;
+    PSCHK(scratch_get(log, bytes, &base, "cannot allocate the %llu bytes of a record of %u generations of %llu individuals", capacity,
+                      (unsigned long long)N));
+    s->d_anc = (uint32_t *)base;
     s->anc_capacity = capacity;
     return PS_OK;
 }
 
 extern "C" int ps_multi_record_ancestry(ps_multi *m, uint32_t capacity)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!m) return ps_fail(PS_ERR_INVALID, "null argument");
     // every shard draws the same parents: shard 0 records alone
     return ps_sim_record_ancestry(m->shard[0], capacity);
@@ -256,15 +251,12 @@ static int gen_recording(const ps_sim *s, const char *call, bool need_depth)
 // the table over the comb in the scratch of the core handle, `extra` bytes behind it: levels x N u32, level 0 = coal
 static int gen_scratch_get(ps_population *c0, uint64_t N, uint32_t levels, uint64_t extra, uint32_t **table, void **tail)
 {
-    const uint64_t tab = ((uint64_t)levels * N * 4 + 15) & ~15ull, need = tab + extra;
-    const hipError_t e = dev_grow_err(c0->d_gen, c0->gen_cap, need);
-    if (e != hipSuccess && !c0->d_gen) {
-        (void)hipGetLastError();
-        return ps_fail(PS_ERR_OOM, "cannot allocate the %llu bytes of the genealogy of %llu individuals", (unsigned long long)need, (unsigned long long)N);
-    }
-    HIPCHK(e);
-    *table = (uint32_t *)c0->d_gen;
-    if (tail) *tail = (uint8_t *)c0->d_gen + tab;
+    scratch_layout lay;
+    const uint64_t o_tab = lay.add((uint64_t)levels * N * 4, 16), o_tail = lay.add(extra, 1);
+    uint8_t *base = nullptr;
+    PSCHK(scratch_get(c0->ro[PS_RO_GEN], lay.bytes, &base, "cannot allocate the %llu bytes of the genealogy of %llu individuals", (unsigned long long)N));
+    *table = (uint32_t *)(base + o_tab);
+    if (tail) *tail = base + o_tail;
     return PS_OK;
 }
 
@@ -307,7 +299,7 @@ static int gen_device(ps_sim *s, ps_genealogy_t *out, uint32_t *order, uint32_t 
 
 extern "C" int ps_sim_genealogy(ps_sim *s, ps_genealogy_t *out, uint32_t *order, uint32_t *coal)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!s || !out || !order || !coal) return ps_fail(PS_ERR_INVALID, "null argument");
     PSCHK(gen_recording(s, "ps_sim_genealogy", false));
     return gen_device(s, out, order, coal);
@@ -315,7 +307,7 @@ extern "C" int ps_sim_genealogy(ps_sim *s, ps_genealogy_t *out, uint32_t *order,
 
 extern "C" int ps_multi_genealogy(ps_multi *m, ps_genealogy_t *out, uint32_t *order, uint32_t *coal)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!m || !out || !order || !coal) return ps_fail(PS_ERR_INVALID, "null argument");
     PSCHK(gen_recording(m->shard[0], "ps_multi_genealogy", false));
     PSCHK(ps_multi_sync(m));

@@ -107,26 +107,23 @@ enum { PS_TR_COMP = 0, PS_TR_PARENT, PS_TR_OUT, PS_TR_BEST, PS_TR_CJ, PS_TR_CNUM
 struct tree_scratch {
     uint32_t *count = nullptr, *arr[PS_TR_ARRAYS] = {};
     void *M = nullptr;
-    uint64_t ldm = 0, head = 0;         // (head: the bytes in front of the matrix)
+    uint64_t ldm = 0;
 };
 
 static int tree_scratch_get(ps_population *c0, uint64_t N, bool acc, tree_scratch *s)
 {
-    const uint64_t lab = (N * 4 + 15) & ~15ull;
+    scratch_layout lay;
+    uint64_t o_arr[PS_TR_ARRAYS];
     s->ldm = (N + 63) & ~63ull;
-    s->head = 16 + PS_TR_ARRAYS * lab;
-    const uint64_t need = s->head + N * s->ldm * (acc ? 2 : 4);
-    const hipError_t e = dev_grow_err(c0->d_tree, c0->tree_cap, need);
-    if (e != hipSuccess && !c0->d_tree) {
-        (void)hipGetLastError();
-        return ps_fail(PS_ERR_OOM, "cannot allocate the %llu bytes of the distance numerators of all pairs of %llu individuals",
-                       (unsigned long long)need, (unsigned long long)N);
-    }
-    HIPCHK(e);
-    uint8_t *base = (uint8_t *)c0->d_tree;
-    s->count = (uint32_t *)base;
-    for (int k = 0; k < PS_TR_ARRAYS; k++) s->arr[k] = (uint32_t *)(base + 16 + k * lab);
-    s->M = base + s->head;
+    const uint64_t o_count = lay.add(16, 16);
+    for (uint64_t &o : o_arr) o = lay.add(N * 4, 16);
+    const uint64_t o_M = lay.add(N * s->ldm * (acc ? 2 : 4), 16);
+    uint8_t *base = nullptr;
+    PSCHK(scratch_get(c0->ro[PS_RO_TREE], lay.bytes, &base, "cannot allocate the %llu bytes of the distance numerators of all pairs of %llu individuals",
+                      (unsigned long long)N));
+    s->count = (uint32_t *)(base + o_count);
+    for (int k = 0; k < PS_TR_ARRAYS; k++) s->arr[k] = (uint32_t *)(base + o_arr[k]);
+    s->M = base + o_M;
     return PS_OK;
 }
 
@@ -146,7 +143,6 @@ static int tree_device(core_band_source &src, ps_population *acc, uint64_t L, co
                        uint32_t *lo_out, uint32_t *hi_out, uint64_t *num_out, uint64_t *den_out)
 {
     ps_population *c0 = src.c0;
-    const core_davg_bands &b = src.b;
     const uint32_t N = (uint32_t)c0->cfg.pop_size;
     const uint64_t cg = acc->cfg.core_genes;
     const bool acc_metric = prm->metric == PS_TREE_ACC;
@@ -157,23 +153,23 @@ static int tree_device(core_band_source &src, ps_population *acc, uint64_t L, co
     // out_row[i] = the output row of internal row i
     std::vector<uint32_t> out_row(N);
     for (uint32_t k = 0; k < N; k++) out_row[slot ? slot[k] : k] = k;
+    readout_slot &ro = c0->ro[PS_RO_TREE];
     pair_pipeline pl(src, acc);
     hipStream_t sc = pl.sc;
     HIPCHK(hipMemsetAsync(s.count, 0, 16, sc));
     HIPCHK(hipMemcpyAsync(s.arr[PS_TR_OUT], out_row.data(), (uint64_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, sc));
     tree_init_kernel<<<(N + 255u) / 256u, 256, 0, sc>>>(s.arr[PS_TR_COMP], s.arr[PS_TR_PARENT], N);
     HIPCHK(hipGetLastError());
-    c0->tree_timed = false;
+    ro.timed = false;
     PSCHK(pl.open(acc_metric));
     const bool have_in = acc_metric && pl.acc_on;          // (no accessory genes: I = U = 0 for every pair, nothing to store)
     // timer groups: 0 = the count phase, 1 = the store kernels, 2 = the rounds
-    for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) {
-        const uint32_t nrows = std::min(b.band, b.c_end - lo);
+    PSCHK(pl.for_bands([&](uint32_t lo, uint32_t nrows) -> int {
         if (!acc_metric) PSCHK(pl.core_counts(0, lo, nrows));
         else PSCHK(pl.acc_counts(0, lo, nrows));
-        if (acc_metric && !have_in) continue;
-        PSCHK(pl.consume(1, [&]() { return tree_store_launch(pl, acc_metric, lo, nrows, s); }));
-    }
+        if (acc_metric && !have_in) return PS_OK;
+        return pl.consume(1, [&]() { return tree_store_launch(pl, acc_metric, lo, nrows, s); });
+    }));
     // (the rows' gene counts beside the intersections: the core stream is behind the accessory stream's padding kernel here)
     if (have_in) HIPCHK(hipMemcpyAsync(s.arr[PS_TR_ROWCNT], pl.A.rowcnt, (uint64_t)N * sizeof(uint32_t), hipMemcpyDeviceToDevice, sc));
     // the rounds: every component hooks to another, so a round at least halves their number
@@ -213,10 +209,7 @@ static int tree_device(core_band_source &src, ps_population *acc, uint64_t L, co
     HIPCHK(hipMemcpyAsync(ej.data(), s.arr[PS_TR_EJ], eb, hipMemcpyDeviceToHost, sc));
     HIPCHK(hipMemcpyAsync(en.data(), s.arr[PS_TR_ENUM], eb, hipMemcpyDeviceToHost, sc));
     HIPCHK(hipMemcpyAsync(ed.data(), s.arr[PS_TR_EDEN], eb, hipMemcpyDeviceToHost, sc));
-    HIPCHK(hipStreamSynchronize(pl.sa));
-    HIPCHK(hipStreamSynchronize(sc));
-    for (int which = 0; which < 3; which++) PSCHK(pl.total_ms(which, &c0->tree_ms[which]));
-    c0->tree_timed = true;
+    PSCHK(pl.finish(ro, 3));
     std::vector<ps_tr_edge> e(N - 1u);
     for (uint32_t k = 0; k + 1u < N; k++) {
         if (ei[k] >= N || ej[k] >= N) return ps_fail(PS_ERR_STATE, "edge %u of the tree joins rows %u and %u of %u", k, ei[k], ej[k], N);
@@ -252,7 +245,7 @@ static int tree_entry(ps_multi *m, ps_population *core, ps_population *acc, cons
 extern "C" int ps_linkage_tree(ps_population *core, ps_population *acc, const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi,
                                uint64_t *num, uint64_t *den)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!core || !acc || !prm || !out || !lo || !hi || !num || !den) return ps_fail(PS_ERR_INVALID, "null argument");
     return tree_entry(nullptr, core, acc, prm, out, lo, hi, num, den);
 }
@@ -260,7 +253,7 @@ extern "C" int ps_linkage_tree(ps_population *core, ps_population *acc, const ps
 extern "C" int ps_sim_linkage_tree(ps_sim *s, const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi, uint64_t *num,
                                    uint64_t *den)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
     return ps_linkage_tree(s->core, s->acc, prm, out, lo, hi, num, den);
 }
@@ -268,17 +261,13 @@ extern "C" int ps_sim_linkage_tree(ps_sim *s, const ps_tree_params *prm, ps_tree
 extern "C" int ps_linkage_tree_timing(ps_population *core, double *counts_ms, double *store_ms, double *rounds_ms)
 {
     if (!core) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (!core->tree_timed) return ps_fail(PS_ERR_STATE, "no linkage tree has been computed on this handle");
-    if (counts_ms) *counts_ms = core->tree_ms[0];
-    if (store_ms) *store_ms = core->tree_ms[1];
-    if (rounds_ms) *rounds_ms = core->tree_ms[2];
-    return PS_OK;
+    return readout_timing(core->ro[PS_RO_TREE], "no linkage tree has been computed on this handle", { counts_ms, store_ms, rounds_ms });
 }
 
 extern "C" int ps_multi_linkage_tree(ps_multi *m, const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi, uint64_t *num,
                                      uint64_t *den)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!m || !prm || !out || !lo || !hi || !num || !den) return ps_fail(PS_ERR_INVALID, "null argument");
     if (m->shard.size() == 1) return ps_sim_linkage_tree(m->shard[0], prm, out, lo, hi, num, den);
     return tree_entry(m, m->shard[0]->core, m->shard[0]->acc, prm, out, lo, hi, num, den);

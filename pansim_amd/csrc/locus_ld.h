@@ -148,38 +148,7 @@ extern "C" int ps_ld_from_counts(const uint32_t *locus_index, const uint32_t *lo
     return PS_OK;
 }
 
-// HIP events around pieces of work of four groups (select, pack, counts, stats), all on one device
-struct ld_timer {
-    std::vector<hipEvent_t> pool;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> t[4];
-    ~ld_timer() { for (hipEvent_t e : pool) (void)hipEventDestroy(e); }
-    template <class W>
-    int timed(int group, hipStream_t st, W &&work)
-    {
-        hipEvent_t e[2] = { nullptr, nullptr };
-        for (hipEvent_t &x : e) {
-            HIPCHK(hipEventCreate(&x));
-            pool.push_back(x);
-        }
-        HIPCHK(hipEventRecord(e[0], st));
-        PSCHK(work());
-        HIPCHK(hipEventRecord(e[1], st));
-        t[group].push_back({ e[0], e[1] });
-        return PS_OK;
-    }
-    int total_ms(int group, double *out)
-    {
-        *out = 0.0;
-        for (const auto &e : t[group]) {
-            float ms = 0.0f;
-            HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
-            *out += (double)ms;
-        }
-        return PS_OK;
-    }
-};
-
-// The ones of every column of `p` and the inclusive prefix sums of its candidate flags, in p->d_ld_sel on its stream; *C = its
+// The ones of every column of `p` and the inclusive prefix sums of its candidate flags, in its selection scratch on its stream; *C = its
 // candidates (one u32 through the host: the stream is synchronised).  *d_incl is null for a handle without columns.
 static int ld_count_candidates(ps_population *p, uint32_t min_minor, uint32_t **d_incl, uint64_t *C)
 {
@@ -193,8 +162,9 @@ static int ld_count_candidates(ps_population *p, uint32_t min_minor, uint32_t **
     if (tiles > 256u * 64u)
         return ps_fail(PS_ERR_INVALID, "the automatic selection of loci scans at most 2^24 columns per handle, not %llu", (unsigned long long)ncols);
     const uint64_t n_cnt = (core ? 4 : 1) * ncols, n_cnt_pad = (n_cnt + 3) & ~3ull;
-    PSCHK(dev_grow(p->d_ld_sel, p->ld_sel_cap, (n_cnt_pad + ncols + tiles) * sizeof(uint32_t)));
-    uint32_t *colcnt = (uint32_t *)p->d_ld_sel, *flag = colcnt + n_cnt_pad, *tsum = flag + ncols;
+    readout_slot &sel = p->ro[PS_RO_LD_SEL];
+    PSCHK(dev_grow(sel.d, sel.cap, (n_cnt_pad + ncols + tiles) * sizeof(uint32_t)));
+    uint32_t *colcnt = (uint32_t *)sel.d, *flag = colcnt + n_cnt_pad, *tsum = flag + ncols;
     hipStream_t st = p->stream;
     if (core) {
         const uint32_t rows = (uint32_t)ncols, grid = std::max(1u, std::min((rows + 3u) / 4u, 256u * 8u));
@@ -218,27 +188,155 @@ static int ld_count_candidates(ps_population *p, uint32_t min_minor, uint32_t **
     return PS_OK;
 }
 
+// What the phases of ld_run share: the kind of the columns, the list (M loci of C candidates; `loci`: the caller's own list) and
+// the sizes that follow from it
+struct ld_geom {
+    bool core = false;
+    const uint32_t *loci = nullptr;         // (nullptr: the automatic selection)
+    uint32_t N = 0, max_loci = 0, Mpad = 0, WP = 0, ldi = 0;
+    uint64_t C = 0, M = 0, band = 0, n_words = 0, row_words = 0;
+    size_t K = 1;
+};
+
+// the call's scratch on one part: sel | cnt | idx | rows; in front of them on part 0 the words, behind them the landing rows (with
+// several parts) and one band of n11
+struct ld_scratch {
+    unsigned long long *words = nullptr;
+    uint32_t *sel = nullptr, *cnt = nullptr, *idx = nullptr, *rows = nullptr, *land = nullptr;
+    uint16_t *in = nullptr;
+};
+
+static int ld_scratch_get(ps_population *p, const ld_geom &g, bool first, ld_scratch *s)
+{
+    scratch_layout lay;
+    const uint64_t o_words = lay.add(first ? g.n_words * 8 : 0, 8);
+    const uint64_t o_sel = lay.add(g.Mpad * 4ull, 4), o_cnt = lay.add(g.Mpad * 4ull, 4), o_idx = lay.add(g.Mpad * 4ull, 4);
+    const uint64_t o_rows = lay.add(g.row_words * 4, 4);
+    const uint64_t o_land = lay.add(first && g.K > 1 ? g.row_words * 4 : 0, 4), o_in = lay.add(first ? g.band * g.ldi * 2 : 0, 2);
+    uint8_t *base = nullptr;
+    PSCHK(scratch_get(p->ro[PS_RO_LD], lay.bytes, &base, nullptr));
+    s->sel = (uint32_t *)(base + o_sel);
+    s->cnt = (uint32_t *)(base + o_cnt);
+    s->idx = (uint32_t *)(base + o_idx);
+    s->rows = (uint32_t *)(base + o_rows);
+    s->words = (unsigned long long *)(base + o_words);      // (the three of part 0 are empty on the others)
+    s->land = (uint32_t *)(base + o_land);
+    s->in = (uint16_t *)(base + o_in);
+    return PS_OK;
+}
+
+// The list entries [j_lo, j_lo + rows_k) that part `p` holds: selected on its device, packed into bit rows at their positions in
+// the list and counted, on its own stream (pad dwords, pad rows and monomorphic rows stay zero); their columns and counts in
+// h_idx / h_cnt once the stream has been synchronised.  tm: part 0, whose select and pack are timed (groups 0 and 1).
+static int ld_select_pack(ps_population *p, const ld_geom &g, const ld_scratch &s, event_timer *tm, const uint32_t *d_incl, uint64_t rank_lo,
+                          uint32_t j_lo, uint32_t rows_k, uint32_t *h_idx, uint32_t *h_cnt)
+{
+    hipStream_t st = p->stream;
+    std::vector<uint32_t> h_sel(rows_k);
+    auto select = [&]() -> int {
+        if (!rows_k) return PS_OK;
+        if (!g.loci) {
+            ld_select_kernel<<<(rows_k + 255u) / 256u, 256, 0, st>>>(d_incl, (uint32_t)p->cfg.ncols, g.C, rank_lo, j_lo, rows_k, g.max_loci, s.sel);
+            HIPCHK(hipGetLastError());
+        } else {
+            for (uint32_t t = 0; t < rows_k; t++) h_sel[t] = (uint32_t)(g.loci[j_lo + t] - p->cfg.col_offset);
+            HIPCHK(hipMemcpyAsync(s.sel, h_sel.data(), rows_k * 4ull, hipMemcpyHostToDevice, st));
+        }
+        return PS_OK;
+    };
+    auto pack = [&]() -> int {
+        if (!rows_k) return PS_OK;
+        if (g.core) {
+            ld_pack_core_kernel<<<(rows_k + 3u) / 4u, 256, 0, st>>>((const uint8_t *)p->state, p->pitch, g.N, s.sel, rows_k, j_lo, g.WP, s.rows, s.cnt);
+        } else {
+            PSCHK(ensure_gene_major(p, st));
+            ld_pack_acc_kernel<<<(rows_k + 3u) / 4u, 256, 0, st>>>(p->G[0], p->d, s.sel, rows_k, j_lo, g.WP, s.rows, s.cnt);
+        }
+        HIPCHK(hipGetLastError());
+        return PS_OK;
+    };
+    HIPCHK(hipMemsetAsync(s.sel, 0, (3ull * g.Mpad + g.row_words) * 4, st));
+    PSCHK(tm ? tm->timed(0, st, select) : select());
+    PSCHK(tm ? tm->timed(1, st, pack) : pack());
+    if (rows_k) {
+        if (!g.loci) HIPCHK(hipMemcpyAsync(h_sel.data(), s.sel, rows_k * 4ull, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_cnt + j_lo, s.cnt + j_lo, rows_k * 4ull, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (uint32_t t = 0; t < rows_k; t++) h_idx[j_lo + t] = (uint32_t)(h_sel[t] + p->cfg.col_offset);
+    return PS_OK;
+}
+
+// The pair phase, queued on part 0's stream (the caller synchronises it): the other parts' rows join part 0's (their streams
+// are idle), the whole list goes up, per band the contraction (group 2) and ld_pair_kernel (group 3), then the words, the lag
+// sums and the bins come back.
+static int ld_pair_phase(const std::vector<ps_population *> &parts, const ld_geom &g, const std::vector<ld_scratch> &S,
+                         const std::vector<uint32_t> &j_cnt, event_timer &tm, const ps_ld_params *prm, const uint32_t *h_idx,
+                         const uint32_t *h_cnt, unsigned long long *w, uint64_t *hist, uint64_t *lag_sum_q)
+{
+    ps_population *p0 = parts[0];
+    hipStream_t s0 = p0->stream;
+    const ld_scratch &s = S[0];
+    const uint64_t nbins = (uint64_t)prm->r2_bins * prm->lag_bins;
+    for (size_t k = 1; k < g.K; k++) {
+        if (!j_cnt[k]) continue;
+        PSCHK(tm.timed(1, s0, [&]() -> int {
+            HIPCHK(hipMemcpyPeerAsync(s.land, p0->device, S[k].rows, parts[k]->device, g.row_words * 4, s0));
+            ld_or_kernel<<<(uint32_t)((g.row_words + 255) / 256), 256, 0, s0>>>(s.rows, s.land, g.row_words);
+            HIPCHK(hipGetLastError());
+            return PS_OK;
+        }));
+    }
+    HIPCHK(hipMemcpyAsync(s.idx, h_idx, g.M * 4, hipMemcpyHostToDevice, s0));
+    if (g.K > 1) HIPCHK(hipMemcpyAsync(s.cnt, h_cnt, g.M * 4, hipMemcpyHostToDevice, s0));
+    unsigned long long *d_lag = s.words + PS_LD_WORDS, *d_hist = d_lag + PS_LD_MAX_LAGS;
+    const uint32_t Mu = (uint32_t)g.M, lds = (uint32_t)nbins * 4u;
+    for (uint32_t lo = 0; lo + 1u < Mu; lo += (uint32_t)g.band) {
+        const uint32_t nrows = std::min<uint32_t>((uint32_t)g.band, Mu - lo);
+        dim3 grid;
+        PSCHK(bin_grid((const void *)ld_pair_kernel, Mu, nrows, lds, 512u, &grid));
+        PSCHK(tm.timed(2, s0, [&]() { return acc_intersections_launch(s.rows, g.WP, g.Mpad, g.ldi, 2u, lo, nrows, s.in, s0); }));
+        PSCHK(tm.timed(3, s0, [&]() -> int {
+            hipLaunchKernelGGL(ld_pair_kernel, grid, dim3(256), lds, s0, (const uint16_t *)s.in, g.ldi, (const uint32_t *)s.cnt,
+                               (const uint32_t *)s.idx, g.N, Mu, lo, nrows, prm->r2_bins, prm->lag_bins, d_hist, d_lag, s.words);
+            HIPCHK(hipGetLastError());
+            return PS_OK;
+        }));
+    }
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the bins are copied as they are");
+    HIPCHK(hipMemcpyAsync(w, s.words, PS_LD_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s0));
+    HIPCHK(hipMemcpyAsync(lag_sum_q, d_lag, prm->lag_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
+    HIPCHK(hipMemcpyAsync(hist, d_hist, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
+    return PS_OK;
+}
+
 // Everything queued on every part is complete or ordered on its own stream before this is called; parts[0] computes.
 static int ld_run(const std::vector<ps_population *> &parts, uint64_t columns, const ps_ld_params *prm, const uint32_t *loci, uint32_t n_loci,
                   ps_ld_t *out, uint32_t *locus_index, uint32_t *locus_count, uint64_t *hist, uint64_t *lag_sum_q)
 {
     ps_population *p0 = parts[0];
     const size_t K = parts.size();
-    const bool core = p0->cfg.core != 0, automatic = loci == nullptr;
+    const bool automatic = loci == nullptr;
     const uint64_t N64 = p0->cfg.pop_size;
     PSCHK(ld_check_params(prm, automatic));
     PSCHK(ld_check_pop(N64));
     if (!automatic) PSCHK(ld_check_list(loci, n_loci, std::max<uint64_t>(columns, 1)));
     if (!automatic && n_loci && columns == 0) return ps_fail(PS_ERR_INVALID, "the handle has no columns to list");
-    const uint32_t N = (uint32_t)N64;
+    ld_geom g;
+    g.core = p0->cfg.core != 0;
+    g.loci = loci;
+    g.N = (uint32_t)N64;
+    g.max_loci = prm->max_loci;
+    g.K = K;
     const uint64_t nbins = (uint64_t)prm->r2_bins * prm->lag_bins;
-    ld_timer tm;
-    p0->ld_timed = false;
+    // timer groups: 0 = counts and selection, 1 = packing, 2 = the contraction, 3 = the pair statistics
+    event_timer tm;
+    readout_slot &ro = p0->ro[PS_RO_LD];
+    ro.timed = false;
     // the rows of the list every part holds: [j_lo, j_lo + j_cnt)
     std::vector<uint32_t> j_lo(K, 0), j_cnt(K, 0);
     std::vector<uint32_t *> d_incl(K, nullptr);
     std::vector<uint64_t> rank_lo(K + 1, 0);
-    uint64_t C = 0, M = 0;
     if (automatic) {
         for (size_t k = 0; k < K; k++) {
             PSCHK(use_device(parts[k]));
@@ -247,165 +345,60 @@ static int ld_run(const std::vector<ps_population *> &parts, uint64_t columns, c
             else PSCHK(ld_count_candidates(parts[k], prm->min_minor, &d_incl[k], &ck));
             rank_lo[k + 1] = rank_lo[k] + ck;
         }
-        C = rank_lo[K];
-        M = std::min<uint64_t>(C, prm->max_loci);
+        const uint64_t C = g.C = rank_lo[K], M = g.M = std::min<uint64_t>(C, prm->max_loci);
         auto first_j = [&](uint64_t rank) { return C <= prm->max_loci ? rank : (rank * prm->max_loci + C - 1) / C; };
         for (size_t k = 0; k < K; k++) {
             j_lo[k] = (uint32_t)std::min(M, first_j(rank_lo[k]));
             j_cnt[k] = (uint32_t)std::min(M, first_j(rank_lo[k + 1])) - j_lo[k];
         }
     } else {
-        M = n_loci;
+        g.M = n_loci;
         for (size_t k = 0; k < K; k++) {
             const uint64_t off = parts[k]->cfg.col_offset, end = off + parts[k]->cfg.ncols;
             j_lo[k] = (uint32_t)(std::lower_bound(loci, loci + n_loci, (uint32_t)std::min<uint64_t>(off, 0xffffffffull)) - loci);
             j_cnt[k] = (uint32_t)(std::lower_bound(loci, loci + n_loci, (uint32_t)std::min<uint64_t>(end, 0xffffffffull)) - loci) - j_lo[k];
         }
     }
-    const uint32_t Mpad = (uint32_t)((std::max<uint64_t>(M, 1) + 127) & ~127ull), WP = ((N + 31u) / 32u + 7u) & ~7u, ldi = Mpad + 128u;
+    const uint64_t M = g.M;
+    g.Mpad = (uint32_t)((std::max<uint64_t>(M, 1) + 127) & ~127ull);
+    g.WP = ((g.N + 31u) / 32u + 7u) & ~7u;
+    g.ldi = g.Mpad + 128u;
     // rows of loci per band: the u16 counts of a band stay below 128 MB unless asked otherwise; a wave of the contraction stores 64
     // whole rows, so a band is a multiple of that
-    uint64_t band = p0->ld_band ? ((uint64_t)p0->ld_band + 63) & ~63ull : std::max<uint64_t>(256, ((64ull << 20) / ldi) & ~255ull);
-    band = std::min<uint64_t>(band, Mpad);
-    const uint64_t n_words = (PS_LD_WORDS + PS_LD_MAX_LAGS + nbins + 1) & ~1ull, row_words = (uint64_t)Mpad * WP;
+    g.band = p0->ld_band ? ((uint64_t)p0->ld_band + 63) & ~63ull : std::max<uint64_t>(256, ((64ull << 20) / g.ldi) & ~255ull);
+    g.band = std::min<uint64_t>(g.band, g.Mpad);
+    g.n_words = (PS_LD_WORDS + PS_LD_MAX_LAGS + nbins + 1) & ~1ull;
+    g.row_words = (uint64_t)g.Mpad * g.WP;
     std::vector<uint32_t> h_idx(M), h_cnt(M);
-    std::vector<std::vector<uint32_t>> h_sel(K);
-    std::vector<uint32_t *> d_rows(K, nullptr);
-    unsigned long long *d_words = nullptr;
-    uint32_t *d_cnt0 = nullptr, *d_idx0 = nullptr, *d_land = nullptr;
-    uint16_t *d_in = nullptr;
+    std::vector<ld_scratch> S(K);
     for (size_t k = 0; k < K && M > 0; k++) {
         ps_population *p = parts[k];
         if (k && !j_cnt[k]) continue;
         PSCHK(use_device(p));
-        hipStream_t st = p->stream;
-        // part 0: words | sel | cnt | idx | rows | landing rows | one band of n11; the others: sel | cnt | rows
-        uint64_t bytes = (3ull * Mpad + row_words) * 4;
-        if (k == 0) bytes += n_words * 8 + (K > 1 ? row_words * 4 : 0) + band * ldi * 2;
-        PSCHK(dev_grow(p->d_ld, p->ld_cap, bytes));
-        uint32_t *base = (uint32_t *)p->d_ld;
-        if (k == 0) {
-            d_words = (unsigned long long *)base;
-            base += 2 * n_words;
-        }
-        uint32_t *d_sel = base, *d_cnt = base + Mpad, *d_idx = base + 2ull * Mpad, *rows = base + 3ull * Mpad;
-        d_rows[k] = rows;
-        if (k == 0) {
-            d_cnt0 = d_cnt;
-            d_idx0 = d_idx;
-            d_land = rows + row_words;
-            d_in = (uint16_t *)(d_land + (K > 1 ? row_words : 0));
-            HIPCHK(hipMemsetAsync(d_words, 0, n_words * 8, st));
-        }
-        const uint32_t rows_k = j_cnt[k];
-        // the list entries of this part on its device, then their bit rows and counts (pad dwords, pad rows and monomorphic rows
-        // stay zero)
-        auto select = [&]() -> int {
-            if (!rows_k) return PS_OK;
-            if (automatic) {
-                ld_select_kernel<<<(rows_k + 255u) / 256u, 256, 0, st>>>(d_incl[k], (uint32_t)p->cfg.ncols, C, rank_lo[k], j_lo[k], rows_k,
-                                                                        prm->max_loci, d_sel);
-                HIPCHK(hipGetLastError());
-            } else {
-                h_sel[k].resize(rows_k);
-                for (uint32_t t = 0; t < rows_k; t++) h_sel[k][t] = (uint32_t)(loci[j_lo[k] + t] - p->cfg.col_offset);
-                HIPCHK(hipMemcpyAsync(d_sel, h_sel[k].data(), rows_k * 4ull, hipMemcpyHostToDevice, st));
-            }
-            return PS_OK;
-        };
-        auto pack = [&]() -> int {
-            if (!rows_k) return PS_OK;
-            if (core) {
-                ld_pack_core_kernel<<<(rows_k + 3u) / 4u, 256, 0, st>>>((const uint8_t *)p->state, p->pitch, N, d_sel, rows_k, j_lo[k], WP, rows, d_cnt);
-            } else {
-                PSCHK(ensure_gene_major(p, st));
-                ld_pack_acc_kernel<<<(rows_k + 3u) / 4u, 256, 0, st>>>(p->G[0], p->d, d_sel, rows_k, j_lo[k], WP, rows, d_cnt);
-            }
-            HIPCHK(hipGetLastError());
-            return PS_OK;
-        };
-        HIPCHK(hipMemsetAsync(d_sel, 0, (3ull * Mpad + row_words) * 4, st));
-        if (k == 0) {
-            PSCHK(tm.timed(0, st, select));
-            PSCHK(tm.timed(1, st, pack));
-        } else {
-            PSCHK(select());
-            PSCHK(pack());
-        }
-        if (rows_k) {
-            if (automatic) {
-                h_sel[k].resize(rows_k);
-                HIPCHK(hipMemcpyAsync(h_sel[k].data(), d_sel, rows_k * 4ull, hipMemcpyDeviceToHost, st));
-            }
-            HIPCHK(hipMemcpyAsync(h_cnt.data() + j_lo[k], d_cnt + j_lo[k], rows_k * 4ull, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
-        for (uint32_t t = 0; t < rows_k; t++) h_idx[j_lo[k] + t] = (uint32_t)(h_sel[k][t] + p->cfg.col_offset);
+        PSCHK(ld_scratch_get(p, g, k == 0, &S[k]));
+        if (k == 0) HIPCHK(hipMemsetAsync(S[0].words, 0, g.n_words * 8, p->stream));
+        PSCHK(ld_select_pack(p, g, S[k], k == 0 ? &tm : nullptr, d_incl[k], rank_lo[k], j_lo[k], j_cnt[k], h_idx.data(), h_cnt.data()));
     }
     uint64_t poly = 0;
-    for (uint64_t a = 0; a < M; a++) poly += ps_ld_monomorphic(h_cnt[a], N) ? 0 : 1;
-    ld_fill(out, N, columns, automatic ? C : poly, M, prm);
+    for (uint64_t a = 0; a < M; a++) poly += ps_ld_monomorphic(h_cnt[a], g.N) ? 0 : 1;
+    ld_fill(out, g.N, columns, automatic ? g.C : poly, M, prm);
     memset(hist, 0, nbins * sizeof(uint64_t));
     memset(lag_sum_q, 0, prm->lag_bins * sizeof(uint64_t));
     if (locus_index && M) memcpy(locus_index, h_idx.data(), M * sizeof(uint32_t));
     if (locus_count && M) memcpy(locus_count, h_cnt.data(), M * sizeof(uint32_t));
     unsigned long long w[PS_LD_WORDS] = {};
     PSCHK(use_device(p0));
-    hipStream_t s0 = p0->stream;
-    if (M >= 2) {
-        // the other parts' rows join part 0's (their streams are idle: synchronised above), the whole list goes up
-        for (size_t k = 1; k < K; k++) {
-            if (!j_cnt[k]) continue;
-            PSCHK(tm.timed(1, s0, [&]() -> int {
-                HIPCHK(hipMemcpyPeerAsync(d_land, p0->device, d_rows[k], parts[k]->device, row_words * 4, s0));
-                ld_or_kernel<<<(uint32_t)((row_words + 255) / 256), 256, 0, s0>>>(d_rows[0], d_land, row_words);
-                HIPCHK(hipGetLastError());
-                return PS_OK;
-            }));
-        }
-        HIPCHK(hipMemcpyAsync(d_idx0, h_idx.data(), M * 4, hipMemcpyHostToDevice, s0));
-        if (K > 1) HIPCHK(hipMemcpyAsync(d_cnt0, h_cnt.data(), M * 4, hipMemcpyHostToDevice, s0));
-        unsigned long long *d_lag = d_words + PS_LD_WORDS, *d_hist = d_lag + PS_LD_MAX_LAGS;
-        const uint32_t Mu = (uint32_t)M, lds = (uint32_t)nbins * 4u;
-        const uint32_t gx = pair_grid_x(Mu);
-        const uint32_t per_cu = std::max(1u, std::min(8u, (160u * 1024u) / (lds + 512u)));
-        auto kern = ld_pair_kernel;
-        if (lds > 32768u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        for (uint32_t lo = 0; lo + 1u < Mu; lo += (uint32_t)band) {
-            const uint32_t nrows = std::min<uint32_t>((uint32_t)band, Mu - lo);
-            PSCHK(tm.timed(2, s0, [&]() { return acc_intersections_launch(d_rows[0], WP, Mpad, ldi, 2u, lo, nrows, d_in, s0); }));
-            PSCHK(tm.timed(3, s0, [&]() -> int {
-                const uint32_t gy = std::max(1u, std::min(std::min(nrows, 65535u), 256u * per_cu / gx));
-                hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), lds, s0, (const uint16_t *)d_in, ldi, (const uint32_t *)d_cnt0,
-                                   (const uint32_t *)d_idx0, N, Mu, lo, nrows, prm->r2_bins, prm->lag_bins, d_hist, d_lag, d_words);
-                HIPCHK(hipGetLastError());
-                return PS_OK;
-            }));
-        }
-        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the bins are copied as they are");
-        HIPCHK(hipMemcpyAsync(w, d_words, sizeof w, hipMemcpyDeviceToHost, s0));
-        HIPCHK(hipMemcpyAsync(lag_sum_q, d_lag, prm->lag_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
-        HIPCHK(hipMemcpyAsync(hist, d_hist, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
-    }
-    HIPCHK(hipStreamSynchronize(s0));
-    for (int g = 0; g < 4; g++) PSCHK(tm.total_ms(g, &p0->ld_ms[g]));
-    p0->ld_timed = true;
+    if (M >= 2) PSCHK(ld_pair_phase(parts, g, S, j_cnt, tm, prm, h_idx.data(), h_cnt.data(), w, hist, lag_sum_q));
+    HIPCHK(hipStreamSynchronize(p0->stream));
+    PSCHK(tm.collect(ro, 4));
     ld_finish(out, w, hist, lag_sum_q);
-    return PS_OK;
-}
-
-static int ld_needs_device(void)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return ps_fail(PS_ERR_NO_DEVICE, "no HIP device is visible: libpansim_hip has no CPU path");
     return PS_OK;
 }
 
 extern "C" int ps_locus_ld(ps_population *p, const ps_ld_params *prm, const uint32_t *loci, uint32_t n_loci, ps_ld_t *out,
                            uint32_t *locus_index, uint32_t *locus_count, uint64_t *hist, uint64_t *lag_sum_q)
 {
-    PSCHK(ld_needs_device());
+    PSCHK(ps_needs_device());
     if (!p || !prm || !out || !hist || !lag_sum_q) return ps_fail(PS_ERR_INVALID, "null argument");
     if (p->cfg.ncols != p->cfg.global_cols)
         return ps_fail(PS_ERR_INVALID, "ps_locus_ld pairs loci over all %llu core sites; this handle is one site shard ([%llu, %llu)): use "
@@ -424,7 +417,7 @@ static int ld_check_metric(int32_t metric)
 extern "C" int ps_sim_locus_ld(ps_sim *s, int32_t metric, const ps_ld_params *prm, const uint32_t *loci, uint32_t n_loci, ps_ld_t *out,
                                uint32_t *locus_index, uint32_t *locus_count, uint64_t *hist, uint64_t *lag_sum_q)
 {
-    PSCHK(ld_needs_device());
+    PSCHK(ps_needs_device());
     if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
     PSCHK(ld_check_metric(metric));
     PSCHK(ps_sim_sync(s));
@@ -434,7 +427,7 @@ extern "C" int ps_sim_locus_ld(ps_sim *s, int32_t metric, const ps_ld_params *pr
 extern "C" int ps_multi_locus_ld(ps_multi *m, int32_t metric, const ps_ld_params *prm, const uint32_t *loci, uint32_t n_loci, ps_ld_t *out,
                                  uint32_t *locus_index, uint32_t *locus_count, uint64_t *hist, uint64_t *lag_sum_q)
 {
-    PSCHK(ld_needs_device());
+    PSCHK(ps_needs_device());
     if (!m || !prm || !out || !hist || !lag_sum_q) return ps_fail(PS_ERR_INVALID, "null argument");
     PSCHK(ld_check_metric(metric));
     if (m->shard.size() == 1 || metric == PS_LD_ACC)
@@ -450,10 +443,5 @@ extern "C" int ps_multi_locus_ld(ps_multi *m, int32_t metric, const ps_ld_params
 extern "C" int ps_locus_ld_timing(ps_population *p, double *select_ms, double *pack_ms, double *counts_ms, double *stats_ms)
 {
     if (!p) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (!p->ld_timed) return ps_fail(PS_ERR_STATE, "no linkage disequilibrium has been computed on this handle");
-    if (select_ms) *select_ms = p->ld_ms[0];
-    if (pack_ms) *pack_ms = p->ld_ms[1];
-    if (counts_ms) *counts_ms = p->ld_ms[2];
-    if (stats_ms) *stats_ms = p->ld_ms[3];
-    return PS_OK;
+    return readout_timing(p->ro[PS_RO_LD], "no linkage disequilibrium has been computed on this handle", { select_ms, pack_ms, counts_ms, stats_ms });
 }

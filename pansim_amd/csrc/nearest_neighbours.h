@@ -195,20 +195,16 @@ struct knn_scratch {
 
 static int knn_scratch_get(ps_population *c0, uint64_t N, uint32_t k, bool acc, knn_scratch *s)
 {
-    const uint64_t head = (N * 4 + 15) & ~15ull, list = (N * k * 4 + 15) & ~15ull;
-    const uint64_t need = head + (acc ? 3 : 2) * list;
-    const hipError_t e = dev_grow_err(c0->d_knn, c0->knn_cap, need);
-    if (e != hipSuccess && !c0->d_knn) {
-        (void)hipGetLastError();
-        return ps_fail(PS_ERR_OOM, "cannot allocate the %llu bytes of the %u nearest neighbours of %llu individuals", (unsigned long long)need, k,
-                       (unsigned long long)N);
-    }
-    HIPCHK(e);
-    uint8_t *base = (uint8_t *)c0->d_knn;
-    s->out_row = (uint32_t *)base;
-    s->j = (uint32_t *)(base + head);
-    s->num = (uint32_t *)(base + head + list);
-    s->den = acc ? (uint32_t *)(base + head + 2 * list) : nullptr;
+    scratch_layout lay;
+    const uint64_t o_row = lay.add(N * 4, 16), o_j = lay.add(N * k * 4, 16), o_num = lay.add(N * k * 4, 16);
+    const uint64_t o_den = acc ? lay.add(N * k * 4, 16) : 0;
+    uint8_t *base = nullptr;
+    PSCHK(scratch_get(c0->ro[PS_RO_KNN], lay.bytes, &base, "cannot allocate the %llu bytes of the %u nearest neighbours of %llu individuals", k,
+                      (unsigned long long)N));
+    s->out_row = (uint32_t *)(base + o_row);
+    s->j = (uint32_t *)(base + o_j);
+    s->num = (uint32_t *)(base + o_num);
+    s->den = acc ? (uint32_t *)(base + o_den) : nullptr;
     return PS_OK;
 }
 
@@ -233,7 +229,6 @@ static int knn_device(core_band_source &src, ps_population *acc, uint64_t L, con
                       uint32_t *nbr_out, uint64_t *num_out, uint64_t *den_out)
 {
     ps_population *c0 = src.c0;
-    const core_davg_bands &b = src.b;
     const uint32_t N = (uint32_t)c0->cfg.pop_size, k = prm->k;
     const uint64_t cg = acc->cfg.core_genes, nk = (uint64_t)N * k;
     const bool acc_metric = prm->metric == PS_KNN_ACC;
@@ -244,28 +239,25 @@ static int knn_device(core_band_source &src, ps_population *acc, uint64_t L, con
     // out_row[i] = the output row of internal row i
     std::vector<uint32_t> out_row(N);
     for (uint32_t r = 0; r < N; r++) out_row[slot ? slot[r] : r] = r;
+    readout_slot &ro = c0->ro[PS_RO_KNN];
     pair_pipeline pl(src, acc);
     hipStream_t sc = pl.sc;
     HIPCHK(hipMemcpyAsync(s.out_row, out_row.data(), (uint64_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, sc));
     // (a row that no band covered would read as UINT32_MAX and fail the check below)
     HIPCHK(hipMemsetAsync(s.j, 0xff, nk * sizeof(uint32_t), sc));
-    c0->knn_timed = false;
+    ro.timed = false;
     PSCHK(pl.open(acc_metric));
     // timer groups: 0 = the count phase, 1 = the select kernels
-    for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) {
-        const uint32_t nrows = std::min(b.band, b.c_end - lo);
+    PSCHK(pl.for_bands([&](uint32_t lo, uint32_t nrows) -> int {
         if (!acc_metric) PSCHK(pl.core_counts(0, lo, nrows));
         else PSCHK(pl.acc_counts(0, lo, nrows));
-        PSCHK(pl.consume(1, [&]() { return knn_select_launch(pl, acc_metric, cg, lo, nrows, k, s); }));
-    }
+        return pl.consume(1, [&]() { return knn_select_launch(pl, acc_metric, cg, lo, nrows, k, s); });
+    }));
     std::vector<uint32_t> hj(nk), hn(nk), hd(acc_metric ? nk : 0);
     HIPCHK(hipMemcpyAsync(hj.data(), s.j, nk * sizeof(uint32_t), hipMemcpyDeviceToHost, sc));
     HIPCHK(hipMemcpyAsync(hn.data(), s.num, nk * sizeof(uint32_t), hipMemcpyDeviceToHost, sc));
     if (acc_metric) HIPCHK(hipMemcpyAsync(hd.data(), s.den, nk * sizeof(uint32_t), hipMemcpyDeviceToHost, sc));
-    HIPCHK(hipStreamSynchronize(pl.sa));
-    HIPCHK(hipStreamSynchronize(sc));
-    for (int which = 0; which < 2; which++) PSCHK(pl.total_ms(which, &c0->knn_ms[which]));
-    c0->knn_timed = true;
+    PSCHK(pl.finish(ro, 2));
     // internal rows -> output rows, for the lists and for their entries; L back as the core den
     for (uint32_t i = 0; i < N; i++) {
         const uint64_t from = (uint64_t)i * k, to = (uint64_t)out_row[i] * k;
@@ -303,14 +295,14 @@ static int knn_entry(ps_multi *m, ps_population *core, ps_population *acc, const
 extern "C" int ps_nearest_neighbours(ps_population *core, ps_population *acc, const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr,
                                      uint64_t *num, uint64_t *den)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!core || !acc || !prm || !out || !nbr || !num || !den) return ps_fail(PS_ERR_INVALID, "null argument");
     return knn_entry(nullptr, core, acc, prm, out, nbr, num, den);
 }
 
 extern "C" int ps_sim_nearest_neighbours(ps_sim *s, const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr, uint64_t *num, uint64_t *den)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
     return ps_nearest_neighbours(s->core, s->acc, prm, out, nbr, num, den);
 }
@@ -318,15 +310,12 @@ extern "C" int ps_sim_nearest_neighbours(ps_sim *s, const ps_knn_params *prm, ps
 extern "C" int ps_nearest_neighbours_timing(ps_population *core, double *counts_ms, double *select_ms)
 {
     if (!core) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (!core->knn_timed) return ps_fail(PS_ERR_STATE, "no nearest neighbours have been computed on this handle");
-    if (counts_ms) *counts_ms = core->knn_ms[0];
-    if (select_ms) *select_ms = core->knn_ms[1];
-    return PS_OK;
+    return readout_timing(core->ro[PS_RO_KNN], "no nearest neighbours have been computed on this handle", { counts_ms, select_ms });
 }
 
 extern "C" int ps_multi_nearest_neighbours(ps_multi *m, const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr, uint64_t *num, uint64_t *den)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!m || !prm || !out || !nbr || !num || !den) return ps_fail(PS_ERR_INVALID, "null argument");
     if (m->shard.size() == 1) return ps_sim_nearest_neighbours(m->shard[0], prm, out, nbr, num, den);
     return knn_entry(m, m->shard[0]->core, m->shard[0]->acc, prm, out, nbr, num, den);

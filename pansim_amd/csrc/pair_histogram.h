@@ -115,37 +115,19 @@ static int pair_hist_handles(const ps_population *core, const ps_population *acc
     return PS_OK;
 }
 
-// four waves per workgroup over the 256-column chunks of a row: the x extent of the grids of pair_hist_kernel and pair_edge_kernel
-static uint32_t pair_grid_x(uint32_t N)
-{
-    const uint32_t nchunk = (N + 255u) / 256u;
-    return std::max(1u, std::min((nchunk + 3u) / 4u, 8u));
-}
-
 // The per-band pipeline of the all-pairs read-outs (histogram, clusters) over the core stream of src.c0 and the stream of the
 // accessory handle on the same device; both idle on entry.  Per band: core_counts() on the core stream, acc_counts() on the
 // accessory stream behind the last consumer that read the scratch, consume() on the core stream behind both.  Every piece of
-// work is timed into a group; total_ms() after both streams have been synchronised.
-struct pair_pipeline {
+// work is timed into a group (event_timer); finish() synchronises both streams and leaves the groups' totals in the read-out's slot.
+struct pair_pipeline : event_timer {
     core_band_source &src;
     ps_population *c0, *acc;
     hipStream_t sc, sa;
     acc_padded A;                   // (all null without accessory counts: the kernels take I = U = 0)
     bool acc_on = false, consumed = false;
     hipEvent_t ev_acc = nullptr, ev_used = nullptr;
-    std::vector<hipEvent_t> pool;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> timers[3];
 
     pair_pipeline(core_band_source &s, ps_population *a) : src(s), c0(s.c0), acc(a), sc(s.c0->stream), sa(a->stream) {}
-    ~pair_pipeline() { for (hipEvent_t e : pool) (void)hipEventDestroy(e); }
-    int make(hipEvent_t *out)
-    {
-        hipEvent_t e = nullptr;
-        HIPCHK(hipEventCreate(&e));
-        pool.push_back(e);
-        *out = e;
-        return PS_OK;
-    }
     // want_acc: the accessory counts are read at all; the padded rows and row counts on the accessory stream (G == 0: nothing)
     int open(bool want_acc)
     {
@@ -155,16 +137,12 @@ struct pair_pipeline {
         return make(&ev_used);
     }
     const uint16_t *In() const { return acc_on ? (const uint16_t *)acc->d_davg_in : nullptr; }
-    template <class W>
-    int timed(int group, hipStream_t st, W &&work)
+    // body(lo, nrows) for every band of the source
+    template <class B>
+    int for_bands(B &&body)
     {
-        hipEvent_t e0, e1;
-        PSCHK(make(&e0));
-        PSCHK(make(&e1));
-        HIPCHK(hipEventRecord(e0, st));
-        PSCHK(work());
-        HIPCHK(hipEventRecord(e1, st));
-        timers[group].push_back({ e0, e1 });
+        const core_davg_bands &b = src.b;
+        for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) PSCHK(body(lo, std::min(b.band, b.c_end - lo)));
         return PS_OK;
     }
     int core_counts(int group, uint32_t lo, uint32_t nrows)
@@ -189,15 +167,12 @@ struct pair_pipeline {
         consumed = true;
         return PS_OK;
     }
-    int total_ms(int group, double *out)
+    // the end of a read-out: everything queued on both streams complete, the first `groups` totals in its slot
+    int finish(readout_slot &ro, int groups)
     {
-        *out = 0.0;
-        for (const auto &e : timers[group]) {
-            float ms = 0.0f;
-            HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
-            *out += (double)ms;
-        }
-        return PS_OK;
+        HIPCHK(hipStreamSynchronize(sa));
+        HIPCHK(hipStreamSynchronize(sc));
+        return collect(ro, groups);
     }
 };
 
@@ -206,14 +181,11 @@ static int pair_hist_launch(const pair_pipeline &pl, uint32_t lo, uint32_t nrows
 {
     const uint32_t N = (uint32_t)pl.c0->cfg.pop_size;
     const uint32_t lds = BIN ? a.Bc * a.Ba * 4u : 0u;
-    // the rows over y; as many workgroups as the bins' LDS lets a CU hold
     // (a workgroup's u32 bins cannot overflow: a band holds fewer than 2^32 pairs)
-    const uint32_t gx = pair_grid_x(N);
-    const uint32_t per_cu = std::max(1u, std::min(8u, (160u * 1024u) / (lds + 256u)));
-    const uint32_t gy = std::max(1u, std::min(std::min(nrows, 65535u), 256u * per_cu / gx));
     auto kern = pair_hist_kernel<BIN, MOM>;
-    if (lds > 32768u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), lds, pl.sc, (const uint32_t *)pl.c0->d_cdavg, pl.src.b.ld, pl.In(), pl.A.ld,
+    dim3 grid;
+    PSCHK(bin_grid((const void *)kern, N, nrows, lds, 256u, &grid));
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, pl.sc, (const uint32_t *)pl.c0->d_cdavg, pl.src.b.ld, pl.In(), pl.A.ld,
                        (const uint32_t *)pl.A.rowcnt, N, lo, nrows, a, d_ph + PS_PH_WORDS, d_ph);
     HIPCHK(hipGetLastError());
     return PS_OK;
@@ -228,21 +200,18 @@ static int pair_hist_device(core_band_source &src, ps_population *acc, uint64_t 
     const uint64_t N = c0->cfg.pop_size, nbins = (uint64_t)prm->core_bins * prm->acc_bins, cg = acc->cfg.core_genes;
     PSCHK(use_device(c0));
     const uint64_t need = PS_PH_WORDS + nbins;
-    PSCHK(dev_grow(c0->d_ph, c0->ph_cap, need));
-    unsigned long long *d_ph = c0->d_ph;
+    readout_slot &ro = c0->ro[PS_RO_HIST];
+    PSCHK(dev_grow(ro.d, ro.cap, need * sizeof(unsigned long long)));
+    unsigned long long *d_ph = (unsigned long long *)ro.d;
     pair_pipeline pl(src, acc);
     hipStream_t sc = pl.sc;
     HIPCHK(hipMemsetAsync(d_ph, 0, need * sizeof(unsigned long long), sc));
     HIPCHK(hipMemsetAsync(d_ph + PS_PH_MIN, 0xff, sizeof(unsigned long long), sc));
-    c0->ph_timed = false;
+    ro.timed = false;
     PSCHK(pl.open(true));
     const bool automatic = prm->core_span == 0;
     const bool one_band = b.c_end - b.c0 <= b.band;
     uint64_t S = prm->core_span;
-    auto for_bands = [&](auto &&body) -> int {
-        for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) PSCHK(body(lo, std::min(b.band, b.c_end - lo)));
-        return PS_OK;
-    };
     auto read_span = [&]() -> int {
         unsigned long long mx = 0;
         HIPCHK(hipMemcpyAsync(&mx, d_ph + PS_PH_MAX, sizeof mx, hipMemcpyDeviceToHost, sc));
@@ -261,7 +230,7 @@ static int pair_hist_device(core_band_source &src, ps_population *acc, uint64_t 
         return pl.consume(1, [&]() { return pair_hist_launch<false, true>(pl, lo, nrows, ps_ph_args{}, d_ph); });
     };
     if (!automatic) {
-        PSCHK(for_bands([&](uint32_t lo, uint32_t nrows) -> int {
+        PSCHK(pl.for_bands([&](uint32_t lo, uint32_t nrows) -> int {
             PSCHK(pl.core_counts(0, lo, nrows));
             PSCHK(pl.acc_counts(0, lo, nrows));
             return bin_band(lo, nrows, true);
@@ -275,12 +244,12 @@ static int pair_hist_device(core_band_source &src, ps_population *acc, uint64_t 
         PSCHK(bin_band(b.c0, b.c_end - b.c0, false));
     } else {
         // ... over several bands: the core contraction runs twice (docs/DISTANCE_HISTOGRAM.md)
-        PSCHK(for_bands([&](uint32_t lo, uint32_t nrows) -> int {
+        PSCHK(pl.for_bands([&](uint32_t lo, uint32_t nrows) -> int {
             PSCHK(pl.core_counts(0, lo, nrows));
             return moments_band(lo, nrows);
         }));
         PSCHK(read_span());
-        PSCHK(for_bands([&](uint32_t lo, uint32_t nrows) -> int {
+        PSCHK(pl.for_bands([&](uint32_t lo, uint32_t nrows) -> int {
             PSCHK(pl.core_counts(0, lo, nrows));
             PSCHK(pl.acc_counts(0, lo, nrows));
             return bin_band(lo, nrows, false);
@@ -290,11 +259,7 @@ static int pair_hist_device(core_band_source &src, ps_population *acc, uint64_t 
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the bins are copied as they are");
     HIPCHK(hipMemcpyAsync(w, d_ph, sizeof w, hipMemcpyDeviceToHost, sc));
     HIPCHK(hipMemcpyAsync(joint, d_ph + PS_PH_WORDS, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, sc));
-    HIPCHK(hipStreamSynchronize(pl.sa));
-    HIPCHK(hipStreamSynchronize(sc));
-    PSCHK(pl.total_ms(0, &c0->ph_counts_ms));
-    PSCHK(pl.total_ms(1, &c0->ph_bin_ms));
-    c0->ph_timed = true;
+    PSCHK(pl.finish(ro, 2));
     memset(out, 0, sizeof *out);
     out->pop_size = N;
     out->pairs = N * (N - 1) / 2;
@@ -304,14 +269,6 @@ static int pair_hist_device(core_band_source &src, ps_population *acc, uint64_t 
     out->acc_bins = prm->acc_bins;
     out->core_span = S;
     pair_hist_finish(out, w);
-    return PS_OK;
-}
-
-static int pair_hist_needs_device(void)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return ps_fail(PS_ERR_NO_DEVICE, "no HIP device is visible: libpansim_hip has no CPU path");
     return PS_OK;
 }
 
@@ -354,14 +311,14 @@ static int pair_hist_entry(ps_multi *m, ps_population *core, ps_population *acc,
 extern "C" int ps_distance_histogram(ps_population *core, ps_population *acc, const ps_pair_hist_params *prm, ps_pair_hist_t *out,
                                      uint64_t *joint)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!core || !acc || !prm || !out || !joint) return ps_fail(PS_ERR_INVALID, "null argument");
     return pair_hist_entry(nullptr, core, acc, prm, out, joint);
 }
 
 extern "C" int ps_sim_distance_histogram(ps_sim *s, const ps_pair_hist_params *prm, ps_pair_hist_t *out, uint64_t *joint)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
     return ps_distance_histogram(s->core, s->acc, prm, out, joint);
 }
@@ -369,15 +326,12 @@ extern "C" int ps_sim_distance_histogram(ps_sim *s, const ps_pair_hist_params *p
 extern "C" int ps_distance_histogram_timing(ps_population *core, double *counts_ms, double *binning_ms)
 {
     if (!core) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (!core->ph_timed) return ps_fail(PS_ERR_STATE, "no distance histogram has been computed on this handle");
-    if (counts_ms) *counts_ms = core->ph_counts_ms;
-    if (binning_ms) *binning_ms = core->ph_bin_ms;
-    return PS_OK;
+    return readout_timing(core->ro[PS_RO_HIST], "no distance histogram has been computed on this handle", { counts_ms, binning_ms });
 }
 
 extern "C" int ps_multi_distance_histogram(ps_multi *m, const ps_pair_hist_params *prm, ps_pair_hist_t *out, uint64_t *joint)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!m || !prm || !out || !joint) return ps_fail(PS_ERR_INVALID, "null argument");
     if (m->shard.size() == 1) return ps_sim_distance_histogram(m->shard[0], prm, out, joint);
     return pair_hist_entry(m, m->shard[0]->core, m->shard[0]->acc, prm, out, joint);

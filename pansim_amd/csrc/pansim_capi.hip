@@ -186,6 +186,16 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // struct Population (population.rs:164-170)
 // ---------------------------------------------------------------------------
+// What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
+// ms of the last call's timer groups (`timed`: a call has completed)
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_COUNT };
+struct readout_slot {
+    void *d = nullptr;
+    uint64_t cap = 0;       // (bytes)
+    double ms[4] = {};
+    bool timed = false;
+};
+
 struct ps_population {
     ps_config cfg{};
     int device = 0;
@@ -311,39 +321,18 @@ struct ps_population {
     unsigned long long *d_div = nullptr;    // ps_core_diversity: the summary words, then the pop_size + 1 spectrum bins
     hipEvent_t div_ev[2] = {};              // around the last launch of the counts kernel (ps_core_diversity_timing)
     bool div_timed = false;
-    // joint distance histogram (pair_histogram.h), on the core handle: the summary words, then the bins; the last call's times
-    unsigned long long *d_ph = nullptr;
-    uint64_t ph_cap = 0;                    // (words)
-    double ph_counts_ms = 0.0, ph_bin_ms = 0.0;
-    bool ph_timed = false;
-    // strain clusters (strain_clusters.h), on the core handle: count words, `changed`, labels, adjacency bit matrix; the last call's times
-    void *d_cl = nullptr;
-    uint64_t cl_cap = 0;                    // (bytes)
-    double cl_ms[3] = {};                   // counts, edges, labels
-    bool cl_timed = false;
-    // linkage tree (linkage_tree.h), on the core handle: the edge counter, the per-row arrays, the N x N numerators; the last call's times
-    void *d_tree = nullptr;
-    uint64_t tree_cap = 0;                  // (bytes)
-    double tree_ms[3] = {};                 // counts, store, rounds
-    bool tree_timed = false;
-    // nearest neighbours (nearest_neighbours.h), on the core handle: out_row, then the N k listed entries; the last call's times
-    void *d_knn = nullptr;
-    uint64_t knn_cap = 0;                   // (bytes)
-    double knn_ms[2] = {};                  // counts, select
-    bool knn_timed = false;
-    // recorded genealogy (genealogy.h, clock_histogram.h), on the core handle: the sparse table over the comb (level 0 = coal),
-    // then the words, sums and bins of the clock histogram; the last clock histogram's times
-    void *d_gen = nullptr;
-    uint64_t gen_cap = 0;                   // (bytes)
-    double clock_ms[2] = {};                // counts, comb + table + binning
-    bool clock_timed = false;
-    // linkage disequilibrium of loci (locus_ld.h), on the handle asked: the selection scratch (column counts, flags, tile sums),
-    // the call's scratch (summary words, bins, list, bit rows, landing rows, one band of n11); the last call's times
-    void *d_ld_sel = nullptr, *d_ld = nullptr;
-    uint64_t ld_sel_cap = 0, ld_cap = 0;    // (bytes)
+    // The device read-outs on the handle asked (the core handle of a pair), one slot each:
+    //   PS_RO_HIST      joint distance histogram (pair_histogram.h): the summary words, then the bins; ms: counts, binning
+    //   PS_RO_CLUSTERS  strain clusters (strain_clusters.h): count words, `changed`, labels, adjacency bit matrix; ms: counts, edges, labels
+    //   PS_RO_TREE      linkage tree (linkage_tree.h): the edge counter, the per-row arrays, the N x N numerators; ms: counts, store, rounds
+    //   PS_RO_KNN       nearest neighbours (nearest_neighbours.h): out_row, then the N k listed entries; ms: counts, select
+    //   PS_RO_GEN       recorded genealogy (genealogy.h, clock_histogram.h): the sparse table over the comb (level 0 = coal), then the
+    //                   words, sums and bins of the clock histogram; ms of the last clock histogram: counts, comb + table + binning
+    //   PS_RO_LD_SEL    linkage disequilibrium (locus_ld.h), the selection scratch: column counts, flags, tile sums
+    //   PS_RO_LD        ... the call's scratch: summary words, bins, list, bit rows, landing rows, one band of n11; ms: select, pack,
+    //                   counts, stats
+    readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
-    double ld_ms[4] = {};                   // select, pack, counts, stats
-    bool ld_timed = false;
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
     unsigned long long *h_stamps = nullptr, *d_stamps = nullptr;   // diagnostic phase stamps
 };
@@ -378,6 +367,9 @@ static int dev_grow(T *&ptr, uint64_t &cap, uint64_t need)
     HIPCHK(dev_grow_err(ptr, cap, need));
     return PS_OK;
 }
+
+// the device check, the scratch slots, the event timer and the grids that the read-outs share
+#include "readout_common.h"
 
 // a device allocation that lives for one call: freed on the device it was made on, on every way out
 template <class T>
@@ -425,7 +417,7 @@ extern "C" void ps_population_destroy(ps_population *p)
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     void *ptrs[] = { p->d_row_slot, p->state, p->state2, p->d_delta, p->hgt_ovf_img, p->G[0], p->G[1], p->I[0], p->I[1], p->I_snap, p->d_ptab[0], p->d_ptab[1], p->hgt_scratch, p->cnt, p->d_idx, p->d_idxT, p->d_work,
-                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg, p->d_cl, p->d_tree, p->d_knn, p->d_gen, p->d_ld_sel, p->d_ld };
+                     p->d_log1p, p->d_num_genes, p->d_logw, p->d_pairs, p->d_H, p->d_Dt, p->d_davg, p->d_davg_in, p->d_pack2, p->d_pair_part, p->d_cdavg };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (int c = 2; c < PS_MAX_COMP; c++)
@@ -434,7 +426,8 @@ extern "C" void ps_population_destroy(ps_population *p)
     if (p->d_gene_tab) (void)hipFree(p->d_gene_tab);
     if (p->d_site_counts) (void)hipFree(p->d_site_counts);
     if (p->d_div) (void)hipFree(p->d_div);
-    if (p->d_ph) (void)hipFree(p->d_ph);
+    for (readout_slot &r : p->ro)
+        if (r.d) (void)hipFree(r.d);
     for (hipEvent_t e : p->div_ev)
         if (e) (void)hipEventDestroy(e);
     if (p->h_flag) (void)hipHostFree(p->h_flag);
@@ -454,8 +447,7 @@ extern "C" void ps_population_destroy(ps_population *p)
 static int pop_create_impl(const ps_config *cfg, const uint8_t *init_vec, ps_population *p)
 {
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return ps_fail(PS_ERR_NO_DEVICE, "no HIP device is visible: libpansim_hip has no CPU path");
+    PSCHK(ps_needs_device(&ndev));
     if (cfg->device >= 0) {
         if (cfg->device >= ndev) return ps_fail(PS_ERR_INVALID, "device %d out of range", cfg->device);
         p->device = cfg->device;
@@ -2974,9 +2966,7 @@ extern "C" int ps_calc_gene_freq(ps_population *p, double *out)
 static int slice_counts(const uint8_t *x, const uint8_t *y, size_t n, uint32_t out[3])
 {
     out[0] = out[1] = out[2] = 0;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return ps_fail(PS_ERR_NO_DEVICE, "no HIP device is visible: libpansim_hip has no CPU path");
+    PSCHK(ps_needs_device());
     if (n == 0) return PS_OK;
     if (!x || !y) return ps_fail(PS_ERR_INVALID, "null slice");
     uint8_t *d = nullptr;
@@ -4596,8 +4586,7 @@ extern "C" int ps_multi_create(const ps_sim_params *p, int n_shards, const int *
     if (p->shard_count != 1 || p->shard_rank != 0)
         return ps_fail(PS_ERR_INVALID, "ps_multi_create shards the run itself: pass shard_rank 0, shard_count 1");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return ps_fail(PS_ERR_NO_DEVICE, "no HIP device is visible: libpansim_hip has no CPU path");
+    PSCHK(ps_needs_device(&ndev));
     ps_multi *m = new ps_multi();
     m->prm = *p;
     m->shard.assign((size_t)n_shards, nullptr);

@@ -490,9 +490,7 @@ extern "C" int ps_sim_load(const char *path, const ps_sim_params *params, ps_sim
 {
     if (!path || !out) return ps_fail(PS_ERR_INVALID, "null argument");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return ps_fail(PS_ERR_NO_DEVICE, "no HIP device is visible: libpansim_hip has no CPU path");
+    PSCHK(ps_needs_device());
     FILE *f = fopen(path, "rb");
     if (!f) return ps_fail(PS_ERR_IO, "cannot open %s", path);
     state_hdr h;

@@ -103,21 +103,17 @@ extern "C" int ps_clusters_from_counts(const uint32_t *r1, const uint32_t *r2, c
 static int cluster_scratch(ps_population *c0, uint64_t N, unsigned long long **words, uint32_t **changed, uint32_t **L,
                            unsigned long long **adj, uint64_t *bytes)
 {
-    const uint64_t W = (N + 63) / 64, head = (PS_CL_WORDS + 1) * 8, lab = (N * 4 + 7) & ~7ull;
-    const uint64_t need = head + lab + N * W * 8;
-    const hipError_t e = dev_grow_err(c0->d_cl, c0->cl_cap, need);
-    if (e != hipSuccess && !c0->d_cl) {
-        (void)hipGetLastError();
-        return ps_fail(PS_ERR_OOM, "cannot allocate the %llu bytes of the adjacency bit matrix and the labels of %llu individuals",
-                       (unsigned long long)need, (unsigned long long)N);
-    }
-    HIPCHK(e);
-    uint8_t *base = (uint8_t *)c0->d_cl;
-    *words = (unsigned long long *)base;
-    *changed = (uint32_t *)(base + PS_CL_WORDS * 8);
-    *L = (uint32_t *)(base + head);
-    *adj = (unsigned long long *)(base + head + lab);
-    *bytes = need;
+    scratch_layout lay;
+    const uint64_t o_words = lay.add(PS_CL_WORDS * 8, 8), o_changed = lay.add(8, 8), o_lab = lay.add(N * 4, 8);
+    const uint64_t o_adj = lay.add(N * ((N + 63) / 64) * 8, 8);
+    uint8_t *base = nullptr;
+    PSCHK(scratch_get(c0->ro[PS_RO_CLUSTERS], lay.bytes, &base, "cannot allocate the %llu bytes of the adjacency bit matrix and the labels of %llu individuals",
+                      (unsigned long long)N));
+    *words = (unsigned long long *)(base + o_words);
+    *changed = (uint32_t *)(base + o_changed);
+    *L = (uint32_t *)(base + o_lab);
+    *adj = (unsigned long long *)(base + o_adj);
+    *bytes = lay.bytes;
     return PS_OK;
 }
 
@@ -140,7 +136,6 @@ static int cluster_device(core_band_source &src, ps_population *acc, uint64_t L,
                           ps_cluster_t *out, uint32_t *labels)
 {
     ps_population *c0 = src.c0;
-    const core_davg_bands &b = src.b;
     const uint32_t N = (uint32_t)c0->cfg.pop_size;
     const uint64_t cg = acc->cfg.core_genes;
     bool core_on, acc_on;
@@ -153,22 +148,22 @@ static int cluster_device(core_band_source &src, ps_population *acc, uint64_t L,
     PSCHK(cluster_scratch(c0, N, &d_words, &d_changed, &d_L, &d_adj, &bytes));
     pair_pipeline pl(src, acc);
     hipStream_t sc = pl.sc;
-    HIPCHK(hipMemsetAsync(c0->d_cl, 0, bytes, sc));
+    readout_slot &ro = c0->ro[PS_RO_CLUSTERS];
+    HIPCHK(hipMemsetAsync(d_words, 0, bytes, sc));
     cluster_init_kernel<<<(N + 255u) / 256u, 256, 0, sc>>>(d_L, N);
     HIPCHK(hipGetLastError());
-    c0->cl_timed = false;
+    ro.timed = false;
     PSCHK(pl.open(acc_on));
     // timer groups: 0 = both count phases, 1 = the edges, 2 = the labels
-    for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) {
-        const uint32_t nrows = std::min(b.band, b.c_end - lo);
+    PSCHK(pl.for_bands([&](uint32_t lo, uint32_t nrows) -> int {
         if (core_on) PSCHK(pl.core_counts(0, lo, nrows));
         PSCHK(pl.acc_counts(0, lo, nrows));
-        PSCHK(pl.consume(1, [&]() {
+        return pl.consume(1, [&]() {
             return core_on && acc_on ? cluster_edge_launch<true, true>(pl, lo, nrows, a, d_adj, d_words)
                    : core_on         ? cluster_edge_launch<true, false>(pl, lo, nrows, a, d_adj, d_words)
                                      : cluster_edge_launch<false, true>(pl, lo, nrows, a, d_adj, d_words);
-        }));
-    }
+        });
+    }));
     // the label rounds: labels only decrease and a label crosses at least one more edge per round, so a hook round that moves
     // nothing comes within N rounds
     uint64_t rounds = 0;
@@ -191,10 +186,7 @@ static int cluster_device(core_band_source &src, ps_population *acc, uint64_t L,
     std::vector<uint32_t> rep(N);
     HIPCHK(hipMemcpyAsync(w, d_words, sizeof w, hipMemcpyDeviceToHost, sc));
     HIPCHK(hipMemcpyAsync(rep.data(), d_L, (uint64_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost, sc));
-    HIPCHK(hipStreamSynchronize(pl.sa));
-    HIPCHK(hipStreamSynchronize(sc));
-    for (int which = 0; which < 3; which++) PSCHK(pl.total_ms(which, &c0->cl_ms[which]));
-    c0->cl_timed = true;
+    PSCHK(pl.finish(ro, 3));
     rows_permute(rep.data(), slot, N);
     memset(out, 0, sizeof *out);
     out->pop_size = N;
@@ -224,14 +216,14 @@ static int cluster_entry(ps_multi *m, ps_population *core, ps_population *acc, c
 extern "C" int ps_strain_clusters(ps_population *core, ps_population *acc, const ps_cluster_params *prm, ps_cluster_t *out,
                                   uint32_t *labels)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!core || !acc || !prm || !out || !labels) return ps_fail(PS_ERR_INVALID, "null argument");
     return cluster_entry(nullptr, core, acc, prm, out, labels);
 }
 
 extern "C" int ps_sim_strain_clusters(ps_sim *s, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
     return ps_strain_clusters(s->core, s->acc, prm, out, labels);
 }
@@ -239,16 +231,12 @@ extern "C" int ps_sim_strain_clusters(ps_sim *s, const ps_cluster_params *prm, p
 extern "C" int ps_strain_clusters_timing(ps_population *core, double *counts_ms, double *edges_ms, double *labels_ms)
 {
     if (!core) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (!core->cl_timed) return ps_fail(PS_ERR_STATE, "no strain clusters have been computed on this handle");
-    if (counts_ms) *counts_ms = core->cl_ms[0];
-    if (edges_ms) *edges_ms = core->cl_ms[1];
-    if (labels_ms) *labels_ms = core->cl_ms[2];
-    return PS_OK;
+    return readout_timing(core->ro[PS_RO_CLUSTERS], "no strain clusters have been computed on this handle", { counts_ms, edges_ms, labels_ms });
 }
 
 extern "C" int ps_multi_strain_clusters(ps_multi *m, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels)
 {
-    PSCHK(pair_hist_needs_device());
+    PSCHK(ps_needs_device());
     if (!m || !prm || !out || !labels) return ps_fail(PS_ERR_INVALID, "null argument");
     if (m->shard.size() == 1) return ps_sim_strain_clusters(m->shard[0], prm, out, labels);
     return cluster_entry(m, m->shard[0]->core, m->shard[0]->acc, prm, out, labels);
