@@ -638,6 +638,61 @@ int ps_tree_from_counts(const uint32_t *r1, const uint32_t *r2, const uint32_t *
  * PS_ERR_STATE before any call. */
 int ps_linkage_tree_timing(ps_population *core, double *counts_ms, double *store_ms, double *rounds_ms);
 
+/* Average-linkage (UPGMA) tree: the dendrogram of ALL N individuals under one distance in which the distance of two clusters is
+ * the average over all their cross pairs (docs/UPGMA_TREE.md) -- under a strict clock the consistent estimator of the genealogy
+ * that ps_sim_genealogy records.  The reference has no such function: it writes a SAMPLE of pairs as text
+ * (population.rs:787-837), from which no tree can be built.  In integers, with the numerators of the distance histogram and the
+ * metrics of the linkage tree (ps_tree_params as it is): a cluster's id is its smallest row; the distance of clusters A, B is
+ * num / den with, core metric, num = sum of d = h / 2 over A x B and den = |A| |B| core_sites, accessory metric, num = sum of
+ * a = U - I and den = sum of b = U + core_genes (the pooled distance).  Two distances compare by num1 den2 against num2 den1 in 128
+ * bits; no floating point.  The tree is the one of the sequential algorithm: N - 1 times, merge the pair of clusters that is
+ * smallest under (distance, lo id, hi id); the order is strict, so the tree is unique and does not depend on the launch geometry.
+ * Merge k (in the order the sequential algorithm performs them) creates node pop_size + k, the leaves being the rows 0 ..
+ * pop_size - 1: left[k], right[k] its children (left: the cluster with the smaller id), size[k] its members, num[k] / den[k]
+ * its distance, non-decreasing in k -- scipy's linkage matrix with exact fractions.  Limits, else PS_ERR_INVALID: pop_size <=
+ * 16384 (every sum below 2^58); under the accessory metric core_genes >= 1 (no pair is 0 / 0), at most 65535 accessory genes and
+ * core_genes + 65535 < 2^32. */
+typedef struct {
+    uint64_t pop_size, pairs, core_sites, core_genes;      /* pairs: all N (N - 1) / 2 */
+    uint64_t metric;
+    uint64_t merges;                   /* pop_size - 1 */
+    uint64_t distinct_heights;         /* distinct distances among the merges */
+    uint64_t root_num, root_den;       /* the distance of the last merge */
+    uint64_t rounds;                   /* rounds of mutual nearest neighbours on the device (informational; 0 from ps_upgma_from_counts) */
+} ps_upgma_t;
+/* All pairs of two handles of equal pop_size >= 2 on one device (the reference has no such function; population.rs:787-837
+ * writes a sample): `core` a core handle that holds all sites, `acc` an accessory handle of at most 65535 genes (required; with
+ * the core metric none of its kernels is launched).  left, right, size, num, den: pop_size - 1 values each.  Ordered behind all
+ * queued work of BOTH handles; changes no state.  PS_ERR_NO_DEVICE before anything else when no GPU is visible. */
+int ps_upgma_tree(ps_population *core, ps_population *acc, const ps_tree_params *prm, ps_upgma_t *out, uint32_t *left, uint32_t *right,
+                  uint32_t *size, uint64_t *num, uint64_t *den);
+/* The same for the two matrices of a simulation (the reference has no such function; population.rs:787-837); a site shard
+ * fails with a message that points to ps_multi_upgma_tree */
+int ps_sim_upgma_tree(ps_sim *s, const ps_tree_params *prm, ps_upgma_t *out, uint32_t *left, uint32_t *right, uint32_t *size, uint64_t *num,
+                      uint64_t *den);
+/* The same for a sharded run (the reference has no such function; population.rs:787-837): every shard counts its own sites
+ * band by band, shard 0 adds them, keeps them and runs the rounds against its accessory replica */
+int ps_multi_upgma_tree(ps_multi *m, const ps_tree_params *prm, ps_upgma_t *out, uint32_t *left, uint32_t *right, uint32_t *size,
+                        uint64_t *num, uint64_t *den);
+/* The sequential algorithm on the host alone (no device is touched; the reference has no such function;
+ * population.rs:787-837; O(pop_size^3) at worst): over the COMPLETE list of pairs (r1[k], r2[k]) with their numerators (those of the other
+ * metric may be NULL), in any order and orientation.  A missing or duplicate pair (average linkage is undefined on a partial
+ * list), an index >= pop_size, r1[k] == r2[k], an intersection above its union and the metric's limits are PS_ERR_INVALID. */
+int ps_upgma_from_counts(const uint32_t *r1, const uint32_t *r2, const uint32_t *core_h, const uint32_t *acc_inter,
+                         const uint32_t *acc_union, uint64_t n_pairs, uint64_t pop_size, uint64_t core_sites, uint64_t core_genes,
+                         const ps_tree_params *prm, ps_upgma_t *out, uint32_t *left, uint32_t *right, uint32_t *size, uint64_t *num,
+                         uint64_t *den);
+/* The tree as one line of Newick text (host only; the reference has no such function; population.rs:787-837): leaves are rows,
+ * children left then right, "(child:len,child:len)" up to the closing ";", len = 0.5 * ((double)num / den of the parent - that
+ * of the child), a leaf's distance being 0, written with ps_fmt_f64.  `needed` counts the terminating zero; buf == NULL asks for
+ * the size alone, a buffer below it is PS_ERR_INVALID. */
+int ps_upgma_newick(const uint32_t *left, const uint32_t *right, const uint64_t *num, const uint64_t *den, uint64_t pop_size, char *buf,
+                    uint64_t cap, uint64_t *needed);
+/* device ms of the last ps_upgma_tree on this core handle (HIP events; the reference has no such function;
+ * population.rs:787-837): the count kernels of the metric, the store kernels, the rounds (host round trips included).
+ * PS_ERR_STATE before any call. */
+int ps_upgma_tree_timing(ps_population *core, double *counts_ms, double *store_ms, double *rounds_ms);
+
 /* Nearest neighbours: for every individual its k closest OTHER individuals among ALL N under one distance, and the lineages that
  * follow from them (docs/NEAREST_NEIGHBOURS.md) -- the sparse form of the distance matrix, N k entries, and the graph of
  * PopPUNK's lineage model.  The reference has no such function: it writes a SAMPLE of pairs as text (population.rs:787-837), and

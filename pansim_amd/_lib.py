@@ -109,6 +109,12 @@ class Tree(C.Structure):
                                                  "distinct_heights", "rounds")]
 
 
+class Upgma(C.Structure):
+    """ps_upgma_t: the summary of ps_upgma_tree / ps_upgma_from_counts (docs/UPGMA_TREE.md)"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "pairs", "core_sites", "core_genes", "metric", "merges", "distinct_heights",
+                                                 "root_num", "root_den", "rounds")]
+
+
 PS_KNN_CORE, PS_KNN_ACC, PS_KNN_MAX_K = 0, 1, 128
 
 
@@ -285,6 +291,13 @@ SIGNATURES = {
     "ps_multi_linkage_tree": (_int, [_vp, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
     "ps_tree_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
     "ps_linkage_tree_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_upgma_tree": (_int, [_vp, _vp, C.POINTER(TreeParams), C.POINTER(Upgma), _vp, _vp, _vp, _vp, _vp]),
+    "ps_sim_upgma_tree": (_int, [_vp, C.POINTER(TreeParams), C.POINTER(Upgma), _vp, _vp, _vp, _vp, _vp]),
+    "ps_multi_upgma_tree": (_int, [_vp, C.POINTER(TreeParams), C.POINTER(Upgma), _vp, _vp, _vp, _vp, _vp]),
+    "ps_upgma_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(TreeParams), C.POINTER(Upgma), _vp, _vp, _vp, _vp,
+                                    _vp]),
+    "ps_upgma_newick": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    "ps_upgma_tree_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_nearest_neighbours": (_int, [_vp, _vp, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
     "ps_sim_nearest_neighbours": (_int, [_vp, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
     "ps_multi_nearest_neighbours": (_int, [_vp, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),

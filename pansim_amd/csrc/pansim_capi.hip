@@ -188,7 +188,7 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
 // ms of the last call's timer groups (`timed`: a call has completed)
-enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_COUNT };
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_COUNT };
 struct readout_slot {
     void *d = nullptr;
     uint64_t cap = 0;       // (bytes)
@@ -331,6 +331,8 @@ struct ps_population {
     //   PS_RO_LD_SEL    linkage disequilibrium (locus_ld.h), the selection scratch: column counts, flags, tile sums
     //   PS_RO_LD        ... the call's scratch: summary words, bins, list, bit rows, landing rows, one band of n11; ms: select, pack,
     //                   counts, stats
+    //   PS_RO_UPGMA     UPGMA tree (upgma_tree.h): the merge counter, the per-row arrays, the merge records, the N x N u64 sums (two
+    //                   matrices under the accessory metric); ms: counts, store, rounds
     readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
@@ -4956,6 +4958,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // single-linkage tree of all pairs (ps_linkage_tree, ps_tree_from_counts, ps_multi_*)
 #include "linkage_tree.h"
+
+// average-linkage (UPGMA) tree of all pairs (ps_upgma_tree, ps_upgma_from_counts, ps_upgma_newick, ps_multi_*)
+#include "upgma_tree.h"
 
 // nearest neighbours of all pairs and rank-k lineages (ps_nearest_neighbours, ps_neighbours_from_counts, ps_lineages_from_neighbours, ps_multi_*)
 #include "nearest_neighbours.h"

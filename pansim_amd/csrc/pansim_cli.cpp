@@ -60,6 +60,8 @@ static const Flag EXT_FLAGS[] = {
     { "cluster_acc_max", "Largest accessory distance of a pair that --print_clusters joins. Must be 0.0 <= X <= 1.0. Without it the accessory distance is not looked at.", "", true },
     { "print_tree", "Write the single-linkage tree of the final population -- the minimum spanning tree over ALL pairs under the distance chosen by --tree_metric, whose sorted edge weights are the heights at which strains merge -- to <outpref>_tree.tsv (lo, hi, num, den, distance per edge, ascending; the distance is num / den, NaN for an undefined one) and its summary to <outpref>_tree_summary.tsv (docs/LINKAGE_TREE.md), beside the usual outputs.", nullptr, false },
     { "tree_metric", "Distance of --print_tree: core or acc.", "core", true },
+    { "print_upgma", "Write the average-linkage (UPGMA) tree of the final population -- the dendrogram over ALL pairs under the distance chosen by --upgma_metric, in which the distance of two clusters is the average over their cross pairs -- to <outpref>_upgma.tsv (node, left, right, size, num, den, distance per merge, in the order the merges are performed; the distance is num / den), as Newick text to <outpref>_upgma.nwk and its summary to <outpref>_upgma_summary.tsv (docs/UPGMA_TREE.md), beside the usual outputs. Needs pop_size <= 16384.", nullptr, false },
+    { "upgma_metric", "Distance of --print_upgma: core or acc (acc needs core_genes >= 1).", "core", true },
     { "print_knn", "Write the <print_knn> nearest neighbours of every individual of the final population -- among ALL others, under the distance chosen by --knn_metric, ordered by (distance, row) -- to <outpref>_knn.tsv (row, rank from 1, neighbour, num, den, distance; the distance is num / den, NaN for an undefined one), the lineages at rank <print_knn> -- the connected components of the graph of those neighbours -- to <outpref>_lineages.tsv (row, label: the smallest row of its lineage) and the summary, with the number of lineages and the largest one at every rank up to <print_knn>, to <outpref>_knn_summary.tsv (docs/NEAREST_NEIGHBOURS.md), beside the usual outputs. Must be 1 <= X <= min(pop_size - 1, 128).", "", true },
     { "knn_metric", "Distance of --print_knn: core or acc.", "core", true },
     { "print_genealogy", "Record the parent draws of the last <print_genealogy> generations on the device and write the true genealogy of the final population: the comb to <outpref>_genealogy.tsv (rank, row, coal per individual in the order the engine stores them: coal is the number of generations back at which the individual and the next one share an ancestor, \"beyond\" when the record does not reach it, empty on the last line), its trees to <outpref>_genealogy.nwk (Newick, one line per root, branch lengths in generations), and ALL pairs binned by (divergence time, distance) to <outpref>_clock.tsv (time_bin, dist_bin, count per non-empty bin; time bin <Bt> holds the pairs beyond the record) with the summary and the mean distance per time bin in <outpref>_clock_summary.tsv (docs/GENEALOGY.md), beside the usual outputs. Must be a whole number >= 1. After --load_state the record starts at the loaded generation.", "", true },
@@ -355,6 +357,18 @@ int main(int argc, char **argv)
     ps_tree_params tree_prm = { PS_TREE_CORE };
     if (val["tree_metric"] == "acc") tree_prm.metric = PS_TREE_ACC;
     else if (val["tree_metric"] != "core") die(101, "pansim: --tree_metric must be core or acc, not \"" + val["tree_metric"] + "\"");
+    // --print_upgma: its metric is checked whether or not it is given
+    ps_tree_params upgma_prm = { PS_TREE_CORE };
+    if (val["upgma_metric"] == "acc") upgma_prm.metric = PS_TREE_ACC;
+    else if (val["upgma_metric"] != "core") die(101, "pansim: --upgma_metric must be core or acc, not \"" + val["upgma_metric"] + "\"");
+    // (the limits of ps_upgma_tree that the flags already decide, before any device work; exact after --load_state as well:
+    // pop_size and core_genes must be the state file's, ps_sim_load refuses a file that differs)
+    if (present["print_upgma"]) {
+        if (p.pop_size < 2 || p.pop_size > 16384)
+            die(101, "pansim: --print_upgma needs 2 <= pop_size <= 16384, not --pop_size " + std::to_string(p.pop_size));
+        if (upgma_prm.metric == PS_TREE_ACC && p.core_genes < 1)
+            die(101, "pansim: --upgma_metric acc needs core_genes >= 1, not --core_genes " + std::to_string(p.core_genes));
+    }
     // --print_knn: its metric is checked whether or not it is given
     ps_knn_params knn_prm = { PS_KNN_CORE, 0 };
     if (val["knn_metric"] == "acc") knn_prm.metric = PS_KNN_ACC;
@@ -572,6 +586,36 @@ int main(int argc, char **argv)
                 { "pop_size", t.pop_size }, { "pairs", t.pairs }, { "core_sites", t.core_sites }, { "core_genes", t.core_genes },
                 { "metric", t.metric }, { "edges", t.edges }, { "undefined_edges", t.undefined_edges },
                 { "distinct_heights", t.distinct_heights } };
+            for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+            fclose(f);
+        }
+        if (present["print_upgma"]) {                                  // (no counterpart in the reference: docs/UPGMA_TREE.md)
+            const size_t n = (size_t)p.pop_size;
+            std::vector<uint32_t> left(n), right(n), size(n);
+            std::vector<uint64_t> num(n), den(n);
+            ps_upgma_t t;
+            CK(multi ? ps_multi_upgma_tree(multi, &upgma_prm, &t, left.data(), right.data(), size.data(), num.data(), den.data())
+                     : ps_sim_upgma_tree(sim, &upgma_prm, &t, left.data(), right.data(), size.data(), num.data(), den.data()));
+            FILE *f = fopen((outpref + "_upgma.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_upgma.tsv");
+            for (uint64_t k = 0; k < t.merges; k++)
+                fprintf(f, "%llu\t%u\t%u\t%u\t%llu\t%llu\t%s\n", (unsigned long long)(t.pop_size + k), left[k], right[k], size[k],
+                        (unsigned long long)num[k], (unsigned long long)den[k], fmt((double)num[k] / (double)den[k]).c_str());
+            fclose(f);
+            uint64_t need = 0;
+            CK(ps_upgma_newick(left.data(), right.data(), num.data(), den.data(), t.pop_size, nullptr, 0, &need));
+            std::vector<char> text(need);
+            CK(ps_upgma_newick(left.data(), right.data(), num.data(), den.data(), t.pop_size, text.data(), need, &need));
+            f = fopen((outpref + "_upgma.nwk").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_upgma.nwk");
+            fprintf(f, "%s\n", text.data());
+            fclose(f);
+            f = fopen((outpref + "_upgma_summary.tsv").c_str(), "w");
+            if (!f) die(1, "Error: cannot create " + outpref + "_upgma_summary.tsv");
+            const std::pair<const char *, uint64_t> fields[] = {
+                { "pop_size", t.pop_size }, { "pairs", t.pairs }, { "core_sites", t.core_sites }, { "core_genes", t.core_genes },
+                { "metric", t.metric }, { "merges", t.merges }, { "distinct_heights", t.distinct_heights }, { "root_num", t.root_num },
+                { "root_den", t.root_den } };
             for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
             fclose(f);
         }

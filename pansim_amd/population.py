@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterParams, Clusters, Config, CoreDiversity, Knn, KnnParams, Lineages, PairHist, PairHistParams, Tree, TreeParams, check
+from ._lib import ClusterParams, Clusters, Config, CoreDiversity, Knn, KnnParams, Lineages, PairHist, PairHistParams, Tree, TreeParams, Upgma, check
 
 
 def _u32(a):
@@ -343,6 +343,117 @@ def tree_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_sites,
                       int(core_sites), int(core_genes))
 
 
+class UpgmaTree:
+    """The result of `upgma_tree` (ps_upgma_t + the merges; docs/UPGMA_TREE.md): the summary fields as integer attributes and the
+    pop_size - 1 merges in the order the sequential algorithm performs them, scipy's linkage matrix with exact fractions --
+    merge k creates node pop_size + k (the leaves are the rows), `left`, `right` (uint32) its children, `size` (uint32) its
+    members, `num`, `den` (uint64) its distance num[k] / den[k], non-decreasing in k -- and `distance` (float64)."""
+    FIELDS = tuple(name for name, _ in Upgma._fields_)
+
+    def __init__(self, t, left, right, size, num, den):
+        for name in self.FIELDS:
+            setattr(self, name, int(getattr(t, name)))
+        n = self.merges
+        self.left, self.right, self.size, self.num, self.den = left[:n], right[:n], size[:n], num[:n], den[:n]
+        self.distance = self.num.astype(np.float64) / self.den.astype(np.float64)
+
+    def _kept(self, num, den):
+        """how many merges (a prefix: the heights do not descend) lie at or below num / den under the integer rule
+        num[k] den <= num den[k]"""
+        num, den = int(num), int(den)
+        if num < 0 or den <= 0:
+            raise ValueError("a threshold is num / den with num >= 0 and den > 0")
+        k = 0
+        while k < self.merges and int(self.num[k]) * den <= num * int(self.den[k]):
+            k += 1
+        return k
+
+    def cut(self, num, den):
+        """labels (pop_size uint32, labels[r] the smallest row of r's cluster) after every merge at or below num / den"""
+        n = self.pop_size
+        label = list(range(n)) + [0] * self.merges           # per node: the smallest row below it
+        parent = list(range(n + self.merges))                # per node: the node it was merged into, among the merges kept
+        for k in range(self._kept(num, den)):
+            a, b = int(self.left[k]), int(self.right[k])
+            parent[a] = parent[b] = n + k
+            label[n + k] = min(label[a], label[b])
+        for x in range(n + self.merges - 1, -1, -1):         # (a parent's number is above its children's: the roots first)
+            if parent[x] != x:
+                label[x] = label[parent[x]]
+        return np.array(label[:n], np.uint32)
+
+    def clusters_at(self, num, den):
+        """the number of clusters of `cut(num, den)`: pop_size less the merges kept"""
+        return self.pop_size - self._kept(num, den)
+
+    def cophenetic(self, r1, r2):
+        """(num, den), two uint64 arrays: the distance of the merge that first joins rows r1[k] and r2[k] -- the tree's own
+        distance of the pair, the counterpart of `GenealogyResult.pairs`.  A node's number is above its children's, so the
+        lower of the two climbs until they meet."""
+        n = self.pop_size
+        parent = [0] * (n + self.merges)
+        for k in range(self.merges):
+            parent[int(self.left[k])] = parent[int(self.right[k])] = n + k
+        r1, r2 = _u32(r1).reshape(-1), _u32(r2).reshape(-1)
+        if r1.size != r2.size:
+            raise ValueError("two rows per pair")
+        num, den = np.zeros(r1.size, np.uint64), np.zeros(r1.size, np.uint64)
+        for k, (a, b) in enumerate(zip(r1.tolist(), r2.tolist())):
+            if a >= n or b >= n or a == b:
+                raise ValueError("pair %d: two different rows below pop_size" % k)
+            while a != b:
+                if a < b:
+                    a = parent[a]
+                else:
+                    b = parent[b]
+            num[k], den[k] = self.num[a - n], self.den[a - n]
+        return num, den
+
+    def newick(self):
+        """the tree as one line of Newick text (ps_upgma_newick): leaves are rows, branch lengths half the difference of the
+        two nodes' distances"""
+        return upgma_newick(self.left, self.right, self.num, self.den, self.pop_size)
+
+    def as_dict(self):
+        out = {name: getattr(self, name) for name in self.FIELDS}
+        out.update(left=self.left, right=self.right, size=self.size, num=self.num, den=self.den, distance=self.distance)
+        return out
+
+
+def upgma_newick(left, right, num, den, pop_size):
+    """the merges of a UPGMA tree as one line of Newick text (ps_upgma_newick; host only)"""
+    left, right = _u32(left).reshape(-1), _u32(right).reshape(-1)
+    num, den = np.ascontiguousarray(num, np.uint64).reshape(-1), np.ascontiguousarray(den, np.uint64).reshape(-1)
+    if not left.size == right.size == num.size == den.size == int(pop_size) - 1:
+        raise ValueError("pop_size - 1 merges")
+    lib, need = _lib.load(), C.c_uint64()
+    check(lib.ps_upgma_newick(_ptr(left), _ptr(right), _ptr(num), _ptr(den), int(pop_size), None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value)
+    check(lib.ps_upgma_newick(_ptr(left), _ptr(right), _ptr(num), _ptr(den), int(pop_size), buf, need.value, C.byref(need)))
+    return buf.value.decode()
+
+
+def _upgma_call(fn, prm, pop_size, *head):
+    """fn(*head, &params, &summary, left, right, size, num, den) -> UpgmaTree"""
+    t = Upgma()
+    n = max(1, int(pop_size))
+    left, right, size = (np.zeros(n, np.uint32) for _ in range(3))
+    num, den = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    check(fn(*head, C.byref(prm), C.byref(t), _ptr(left), _ptr(right), _ptr(size), _ptr(num), _ptr(den)))
+    return UpgmaTree(t, left, right, size, num, den)
+
+
+def upgma_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_sites, core_genes, metric="core"):
+    """`Population.upgma_tree` from the COMPLETE list of pairs (r1, r2), in any order and orientation, and their numerators
+    (`pairwise_counts` of both matrices), by the sequential algorithm on the host alone (ps_upgma_from_counts; no device;
+    O(pop_size^3) at worst).  The numerators of the other metric may be None."""
+    arrays = [None if a is None else _u32(a).reshape(-1) for a in (r1, r2, core_h, acc_inter, acc_union)]
+    if len({a.size for a in arrays if a is not None}) != 1 or arrays[0] is None or arrays[1] is None:
+        raise ValueError("two indices, and one value of every numerator given, per pair")
+    return _upgma_call(_lib.load().ps_upgma_from_counts, _tree_params(metric), pop_size, *map(_ptr, arrays), arrays[0].size, int(pop_size),
+                       int(core_sites), int(core_genes))
+
+
 class NearestNeighbours:
     """The result of `nearest_neighbours` (ps_knn_t + the lists; docs/NEAREST_NEIGHBOURS.md): the summary fields as integer
     attributes and, as (pop_size, k) arrays, `nbr` (uint32: entry [i, r] is the r-th nearest other individual of row i in
@@ -629,6 +740,18 @@ class Population:
         population `acc` of the same individuals under the core (`"core"`) or the accessory (`"acc"`) distance
         (ps_linkage_tree; docs/LINKAGE_TREE.md) -> a LinkageTree"""
         return _tree_call(self._lib.ps_linkage_tree, _tree_params(metric), self.size, self._h, acc._h)
+
+    def upgma_tree(self, acc, metric="core"):
+        """the average-linkage (UPGMA) tree over ALL pairs of this core population and the accessory population `acc` of the
+        same individuals under the core (`"core"`) or the accessory (`"acc"`) distance (ps_upgma_tree; docs/UPGMA_TREE.md) ->
+        an UpgmaTree"""
+        return _upgma_call(self._lib.ps_upgma_tree, _tree_params(metric), self.size, self._h, acc._h)
+
+    def upgma_tree_timing(self):
+        """device ms of (the count kernels, the store kernels, the rounds) of the last upgma_tree() on this core handle"""
+        t = [C.c_double() for _ in range(3)]
+        check(self._lib.ps_upgma_tree_timing(self._h, *map(C.byref, t)))
+        return tuple(x.value for x in t)
 
     def nearest_neighbours(self, acc, k, metric="core"):
         """the k nearest other individuals of every individual among ALL of this core population and the accessory population

@@ -252,6 +252,11 @@ class Simulation:
         from .population import _tree_call, _tree_params
         return _tree_call(self._lib.ps_sim_linkage_tree, _tree_params(metric), self.params.pop_size, self._h)
 
+    def upgma_tree(self, metric="core"):
+        """Population.upgma_tree() of the run's two matrices (ps_sim_upgma_tree), leaves in the reference's row order"""
+        from .population import _tree_params, _upgma_call
+        return _upgma_call(self._lib.ps_sim_upgma_tree, _tree_params(metric), self.params.pop_size, self._h)
+
     def nearest_neighbours(self, k, metric="core"):
         """Population.nearest_neighbours() of the run's two matrices (ps_sim_nearest_neighbours), rows and neighbours in the
         reference's row order"""
@@ -395,6 +400,12 @@ class MultiSimulation:
         against its accessory replica (ps_multi_linkage_tree)"""
         from .population import _tree_call, _tree_params
         return _tree_call(self._lib.ps_multi_linkage_tree, _tree_params(metric), self.params.pop_size, self._h)
+
+    def upgma_tree(self, metric="core"):
+        """Population.upgma_tree() over ALL core sites: the shards' band counts added and kept on shard 0, the rounds
+        against its accessory replica (ps_multi_upgma_tree)"""
+        from .population import _tree_params, _upgma_call
+        return _upgma_call(self._lib.ps_multi_upgma_tree, _tree_params(metric), self.params.pop_size, self._h)
 
     def nearest_neighbours(self, k, metric="core"):
         """Population.nearest_neighbours() over ALL core sites: the shards' band counts added on shard 0, the selection
