@@ -1,6 +1,7 @@
 // clock_histogram.h -- ps_sim_clock_histogram / ps_multi_clock_histogram, the host restatement ps_clock_from_counts and
 // ps_clock_histogram_timing (include/pansim_hip.h; the definitions: docs/GENEALOGY.md).  Included by pansim_capi.hip behind
-// genealogy.h; the band pipeline (pair_source_open, pair_pipeline) and the distance bins are the histogram's own.
+// genealogy.h; the pair-list reader, the metric checks and the band pipeline (pair_source_open, pair_pipeline) are those of
+// pair_readout.h, the distance bins the histogram's own.
 //
 // Everything on the device runs in INTERNAL row order, which is the comb's order: the divergence time of a pair of band row i
 // and column j is the maximum of coal[i .. j - 1], two reads of the sparse table.  Before the bands the comb and the table are
@@ -11,10 +12,11 @@
 #define PS_CLOCK_MAX_BINS 16384u        // 64 KB of u32 bins in LDS per workgroup
 #define PS_CLOCK_MAX_TIME_BINS 1024u    // ... beside 16 bytes of sums per time row
 
+static const metric_names CLOCK_NAMES = { "a clock histogram", "PS_KNN_CORE", "PS_KNN_ACC" };
+
 static int clock_check_params(const ps_clock_params *prm)
 {
-    if (prm->metric != PS_KNN_CORE && prm->metric != PS_KNN_ACC)
-        return ps_fail(PS_ERR_INVALID, "the metric of a clock histogram is PS_KNN_CORE (0) or PS_KNN_ACC (1), not %d", (int)prm->metric);
+    PSCHK(metric_check(prm->metric, CLOCK_NAMES));
     if (prm->time_bins < 1 || prm->dist_bins < 1) return ps_fail(PS_ERR_INVALID, "time_bins and dist_bins must be >= 1");
     if (prm->time_bins > PS_CLOCK_MAX_TIME_BINS)
         return ps_fail(PS_ERR_INVALID, "time_bins = %u exceeds the limit of %u time bins", prm->time_bins, PS_CLOCK_MAX_TIME_BINS);
@@ -23,14 +25,6 @@ static int clock_check_params(const ps_clock_params *prm)
                        ((unsigned long long)prm->time_bins + 1) * prm->dist_bins, PS_CLOCK_MAX_BINS);
     if (prm->time_span > 0xffffffffull)
         return ps_fail(PS_ERR_INVALID, "time_span = %llu exceeds the limit of 2^32 - 1 generations", (unsigned long long)prm->time_span);
-    return PS_OK;
-}
-
-static int clock_check_core_genes(const ps_clock_params *prm, uint64_t cg)
-{
-    if (prm->metric == PS_KNN_ACC && cg + 65535ull >= (1ull << 32))
-        return ps_fail(PS_ERR_INVALID, "the accessory metric of a clock histogram needs core_genes + 65535 < 2^32, not %llu core genes",
-                       (unsigned long long)cg);
     return PS_OK;
 }
 
@@ -65,11 +59,7 @@ static void clock_finish(ps_clock_t *o, const uint64_t *joint, uint64_t *per_tim
 static void clock_fill(ps_clock_t *o, uint64_t N, uint64_t pairs, uint64_t L, uint64_t cg, const ps_clock_params *prm, uint64_t St, uint64_t S,
                        uint64_t depth)
 {
-    memset(o, 0, sizeof *o);
-    o->pop_size = N;
-    o->pairs = pairs;
-    o->core_sites = L;
-    o->core_genes = cg;
+    readout_head(o, N, pairs, L, cg);
     o->metric = (uint64_t)prm->metric;
     o->time_bins = prm->time_bins;
     o->dist_bins = prm->dist_bins;
@@ -85,8 +75,9 @@ extern "C" int ps_clock_from_counts(const uint32_t *tmrca, const uint32_t *core_
     if (!tmrca || !prm || !out || !joint || !per_time) return ps_fail(PS_ERR_INVALID, "null argument");
     PSCHK(clock_check_params(prm));
     const bool acc = prm->metric == PS_KNN_ACC;
-    if (acc ? (!acc_inter || !acc_union) : !core_h) return ps_fail(PS_ERR_INVALID, "null argument: the metric needs its numerators");
-    PSCHK(clock_check_core_genes(prm, core_genes));
+    const pair_list pairs = { nullptr, nullptr, core_h, acc_inter, acc_union, n_pairs, 0 };
+    if (pairs.lacks(!acc, acc)) return ps_fail(PS_ERR_INVALID, "null argument: the metric needs its numerators");
+    PSCHK(metric_check_core_genes(prm->metric, core_genes, CLOCK_NAMES));
     if (n_pairs < 1) return ps_fail(PS_ERR_INVALID, "a clock histogram needs at least one pair (pop_size >= 2)");
     if (depth < 1 || depth > 0xfffffffeull) return ps_fail(PS_ERR_INVALID, "a clock histogram needs 1 <= depth < 2^32 - 1 recorded generations, not %llu", (unsigned long long)depth);
     uint64_t d_max = 0;
@@ -94,10 +85,7 @@ extern "C" int ps_clock_from_counts(const uint32_t *tmrca, const uint32_t *core_
         if (tmrca[p] != PS_GEN_BEYOND && (tmrca[p] < 1 || tmrca[p] > depth))
             return ps_fail(PS_ERR_INVALID, "pair %llu: a divergence time is 1 .. depth = %llu or PS_GEN_BEYOND, not %u", (unsigned long long)p,
                            (unsigned long long)depth, tmrca[p]);
-        if (acc && acc_inter[p] > acc_union[p])
-            return ps_fail(PS_ERR_INVALID, "pair %llu: intersection %u above union %u", (unsigned long long)p, acc_inter[p], acc_union[p]);
-        if (acc && acc_union[p] > 65535u)
-            return ps_fail(PS_ERR_INVALID, "pair %llu: union %u above the limit of 65535 accessory genes", (unsigned long long)p, acc_union[p]);
+        if (acc) PSCHK(pairs.check_acc(p, true));
         if (!acc) d_max = std::max<uint64_t>(d_max, core_h[p] / 2);
     }
     const uint64_t St = prm->time_span ? prm->time_span : depth, S = acc ? 1 : prm->core_span ? prm->core_span : d_max + 1;
@@ -157,7 +145,7 @@ static int clock_device(core_band_source &src, ps_sim *s, uint64_t L, const ps_c
     const bool acc_metric = prm->metric == PS_KNN_ACC;
     const uint64_t depth = std::min<uint64_t>(s->anc_written, s->anc_capacity);
     if (depth > 0xfffffffeull) return ps_fail(PS_ERR_INVALID, "a clock histogram needs depth < 2^32 - 1 recorded generations");
-    PSCHK(clock_check_core_genes(prm, cg));
+    PSCHK(metric_check_core_genes(prm->metric, cg, CLOCK_NAMES));
     PSCHK(use_device(c0));
     const uint32_t levels = gen_levels(N);
     const uint64_t n_words = PS_CK_WORDS + 2 * nt + nbins;

@@ -1,6 +1,6 @@
 // linkage_tree.h -- ps_linkage_tree / ps_sim_linkage_tree / ps_multi_linkage_tree and the host restatement
 // ps_tree_from_counts (include/pansim_hip.h; the definitions: docs/LINKAGE_TREE.md).  Included by pansim_capi.hip behind
-// strain_clusters.h, whose band source, count phases and stream ordering (pair_source_open, pair_pipeline) it reuses as they are.
+// pair_readout.h, whose pair-list reader, metric checks, band pipeline (pair_source_open, pair_pipeline) and entry bodies it reuses.
 //
 // As the clusters, everything on the device runs in INTERNAL row order: per band the numerators of the metric asked for (the
 // other metric's count kernels are not launched), then a store kernel on the core stream that keeps them as the band's rows of a
@@ -11,21 +11,7 @@
 
 #include "linkage_kernels.h"
 
-static int tree_check_params(const ps_tree_params *prm)
-{
-    if (prm->metric != PS_TREE_CORE && prm->metric != PS_TREE_ACC)
-        return ps_fail(PS_ERR_INVALID, "the metric of a linkage tree is PS_TREE_CORE (0) or PS_TREE_ACC (1), not %d", (int)prm->metric);
-    return PS_OK;
-}
-
-// the cross products of two accessory distances stay in 64 bits while a <= 65535 and b = U + core_genes < 2^32
-static int tree_check_core_genes(const ps_tree_params *prm, uint64_t cg)
-{
-    if (prm->metric == PS_TREE_ACC && cg + 65535ull >= (1ull << 32))
-        return ps_fail(PS_ERR_INVALID, "the accessory metric of a linkage tree needs core_genes + 65535 < 2^32, not %llu core genes",
-                       (unsigned long long)cg);
-    return PS_OK;
-}
+static const metric_names TREE_NAMES = { "a linkage tree", "PS_TREE_CORE", "PS_TREE_ACC" };
 
 // e[0 .. n): tree edges with lo < hi in output rows, in any order -> the four arrays in ascending order and the summary fields
 // that follow from them
@@ -48,31 +34,20 @@ extern "C" int ps_tree_from_counts(const uint32_t *r1, const uint32_t *r2, const
                                    const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi, uint64_t *num, uint64_t *den)
 {
     if (!prm || !out || !lo || !hi || !num || !den || (n_pairs && (!r1 || !r2))) return ps_fail(PS_ERR_INVALID, "null argument");
-    PSCHK(tree_check_params(prm));
+    PSCHK(metric_check(prm->metric, TREE_NAMES));
     const bool acc = prm->metric == PS_TREE_ACC;
-    if (n_pairs && (acc ? (!acc_inter || !acc_union) : !core_h))
+    const pair_list pairs = { r1, r2, core_h, acc_inter, acc_union, n_pairs, pop_size };
+    if (n_pairs && pairs.lacks(!acc, acc))
         return ps_fail(PS_ERR_INVALID, "null argument: the metric needs its numerators");
     if (pop_size < 2 || pop_size > 0xffffffffull) return ps_fail(PS_ERR_INVALID, "a linkage tree needs 2 <= pop_size < 2^32");
-    PSCHK(tree_check_core_genes(prm, core_genes));
+    PSCHK(metric_check_core_genes(prm->metric, core_genes, TREE_NAMES));
     std::vector<ps_tr_edge> all(n_pairs);
     for (uint64_t k = 0; k < n_pairs; k++) {
-        if (r1[k] >= pop_size || r2[k] >= pop_size)
-            return ps_fail(PS_ERR_INVALID, "pair %llu: index %u is not below pop_size %llu", (unsigned long long)k, std::max(r1[k], r2[k]),
-                           (unsigned long long)pop_size);
-        if (r1[k] == r2[k]) return ps_fail(PS_ERR_INVALID, "pair %llu: both indices are %u", (unsigned long long)k, r1[k]);
+        PSCHK(pairs.check(k, acc));
         ps_tr_edge &e = all[k];
         e.lo = std::min(r1[k], r2[k]);
         e.hi = std::max(r1[k], r2[k]);
-        if (acc) {
-            if (acc_inter[k] > acc_union[k])
-                return ps_fail(PS_ERR_INVALID, "pair %llu: intersection %u above union %u", (unsigned long long)k, acc_inter[k], acc_union[k]);
-            if (acc_union[k] > 65535u)
-                return ps_fail(PS_ERR_INVALID, "pair %llu: union %u above the limit of 65535 accessory genes", (unsigned long long)k, acc_union[k]);
-            ps_tr_acc_distance(acc_inter[k], acc_union[k], core_genes, &e.num, &e.den);
-        } else {
-            e.num = core_h[k] / 2;
-            e.den = core_sites;
-        }
+        pairs.distance(k, acc, core_sites, core_genes, &e.num, &e.den);
     }
     // Kruskal: the pairs in ascending order, a pair kept when it joins two sets (stable: of two copies of a pair at one distance
     // written as different fractions, the earlier one of the list is the one reported)
@@ -90,11 +65,7 @@ extern "C" int ps_tree_from_counts(const uint32_t *r1, const uint32_t *r2, const
         parent[std::max(x, y)] = std::min(x, y);
         kept.push_back(e);
     }
-    memset(out, 0, sizeof *out);
-    out->pop_size = pop_size;
-    out->pairs = n_pairs;
-    out->core_sites = core_sites;
-    out->core_genes = core_genes;
+    readout_head(out, pop_size, n_pairs, core_sites, core_genes);
     out->metric = (uint64_t)prm->metric;
     tree_finish(kept, out, lo, hi, num, den);
     return PS_OK;
@@ -146,13 +117,12 @@ static int tree_device(core_band_source &src, ps_population *acc, uint64_t L, co
     const uint32_t N = (uint32_t)c0->cfg.pop_size;
     const uint64_t cg = acc->cfg.core_genes;
     const bool acc_metric = prm->metric == PS_TREE_ACC;
-    PSCHK(tree_check_core_genes(prm, cg));
+    PSCHK(metric_check_core_genes(prm->metric, cg, TREE_NAMES));
     PSCHK(use_device(c0));
     tree_scratch s;
     PSCHK(tree_scratch_get(c0, N, acc_metric, &s));
     // out_row[i] = the output row of internal row i
-    std::vector<uint32_t> out_row(N);
-    for (uint32_t k = 0; k < N; k++) out_row[slot ? slot[k] : k] = k;
+    const std::vector<uint32_t> out_row = row_inverse(slot, N);
     readout_slot &ro = c0->ro[PS_RO_TREE];
     pair_pipeline pl(src, acc);
     hipStream_t sc = pl.sc;
@@ -219,43 +189,36 @@ static int tree_device(core_band_source &src, ps_population *acc, uint64_t L, co
         e[k].num = en[k];
         e[k].den = acc_metric ? (uint64_t)ed[k] : L;
     }
-    memset(out, 0, sizeof *out);
-    out->pop_size = N;
-    out->pairs = (uint64_t)N * (N - 1) / 2;
-    out->core_sites = L;
-    out->core_genes = cg;
+    readout_head(out, N, (uint64_t)N * (N - 1) / 2, L, cg);
     out->metric = (uint64_t)prm->metric;
     out->rounds = rounds;
     tree_finish(e, out, lo_out, hi_out, num_out, den_out);
     return PS_OK;
 }
 
-// ps_linkage_tree (m == nullptr) and ps_multi_linkage_tree (core, acc: shard 0's handles; the matrix and the rounds on shard 0
-// against its accessory replica, the row map from shard 0's simulation)
-static int tree_entry(ps_multi *m, ps_population *core, ps_population *acc, const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo,
-                      uint32_t *hi, uint64_t *num, uint64_t *den)
+// behind pair_entry: ps_linkage_tree (m == nullptr) and ps_multi_linkage_tree (core, acc: shard 0's handles; the matrix and the
+// rounds on shard 0 against its accessory replica, the row map from shard 0's simulation)
+static auto tree_entry(const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi, uint64_t *num, uint64_t *den)
 {
-    PSCHK(tree_check_params(prm));
-    core_band_source src;
-    const uint32_t *slot = nullptr;
-    PSCHK(pair_source_open(&src, "linkage_tree", "a linkage tree needs", "compares", m, core, acc, prm->metric == PS_TREE_CORE, &slot));
-    return tree_device(src, acc, m ? m->prm.core_size : core->cfg.global_cols, prm, slot, out, lo, hi, num, den);
+    return [=](ps_multi *m, ps_population *core, ps_population *acc) -> int {
+        PSCHK(metric_check(prm->metric, TREE_NAMES));
+        core_band_source src;
+        const uint32_t *slot = nullptr;
+        PSCHK(pair_source_open(&src, "linkage_tree", "a linkage tree needs", "compares", m, core, acc, prm->metric == PS_TREE_CORE, &slot));
+        return tree_device(src, acc, m ? m->prm.core_size : core->cfg.global_cols, prm, slot, out, lo, hi, num, den);
+    };
 }
 
 extern "C" int ps_linkage_tree(ps_population *core, ps_population *acc, const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi,
                                uint64_t *num, uint64_t *den)
 {
-    PSCHK(ps_needs_device());
-    if (!core || !acc || !prm || !out || !lo || !hi || !num || !den) return ps_fail(PS_ERR_INVALID, "null argument");
-    return tree_entry(nullptr, core, acc, prm, out, lo, hi, num, den);
+    return pair_entry(core, acc, prm && out && lo && hi && num && den, tree_entry(prm, out, lo, hi, num, den));
 }
 
 extern "C" int ps_sim_linkage_tree(ps_sim *s, const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi, uint64_t *num,
                                    uint64_t *den)
 {
-    PSCHK(ps_needs_device());
-    if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
-    return ps_linkage_tree(s->core, s->acc, prm, out, lo, hi, num, den);
+    return pair_entry(s, prm && out && lo && hi && num && den, tree_entry(prm, out, lo, hi, num, den));
 }
 
 extern "C" int ps_linkage_tree_timing(ps_population *core, double *counts_ms, double *store_ms, double *rounds_ms)
@@ -267,8 +230,5 @@ extern "C" int ps_linkage_tree_timing(ps_population *core, double *counts_ms, do
 extern "C" int ps_multi_linkage_tree(ps_multi *m, const ps_tree_params *prm, ps_tree_t *out, uint32_t *lo, uint32_t *hi, uint64_t *num,
                                      uint64_t *den)
 {
-    PSCHK(ps_needs_device());
-    if (!m || !prm || !out || !lo || !hi || !num || !den) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (m->shard.size() == 1) return ps_sim_linkage_tree(m->shard[0], prm, out, lo, hi, num, den);
-    return tree_entry(m, m->shard[0]->core, m->shard[0]->acc, prm, out, lo, hi, num, den);
+    return pair_entry(m, prm && out && lo && hi && num && den, tree_entry(prm, out, lo, hi, num, den));
 }

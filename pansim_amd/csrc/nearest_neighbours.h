@@ -1,7 +1,7 @@
 // nearest_neighbours.h -- ps_nearest_neighbours / ps_sim_nearest_neighbours / ps_multi_nearest_neighbours, the host restatement
 // ps_neighbours_from_counts and the lineages ps_lineages_from_neighbours (include/pansim_hip.h; the definitions:
-// docs/NEAREST_NEIGHBOURS.md).  Included by pansim_capi.hip behind linkage_tree.h, whose metric, comparator and band pipeline
-// (pair_source_open, pair_pipeline) it reuses as they are.
+// docs/NEAREST_NEIGHBOURS.md).  Included by pansim_capi.hip behind pair_readout.h, whose pair-list reader, metric checks, band
+// pipeline (pair_source_open, pair_pipeline) and entry bodies it reuses, and behind strain_clusters.h (cluster_finish).
 //
 // As the tree, everything on the device runs in INTERNAL row order: per band the numerators of the metric asked for (the other
 // metric's count kernels are not launched), then knn_select_kernel on the core stream, which lists the k nearest columns of
@@ -12,23 +12,15 @@
 
 #include "knn_kernels.h"
 
+static const metric_names KNN_NAMES = { "nearest neighbours", "PS_KNN_CORE", "PS_KNN_ACC" };
+
 static int knn_check_params(const ps_knn_params *prm, uint64_t N)
 {
-    if (prm->metric != PS_KNN_CORE && prm->metric != PS_KNN_ACC)
-        return ps_fail(PS_ERR_INVALID, "the metric of nearest neighbours is PS_KNN_CORE (0) or PS_KNN_ACC (1), not %d", (int)prm->metric);
+    PSCHK(metric_check(prm->metric, KNN_NAMES));
     if (N < 2 || N > 0xffffffffull) return ps_fail(PS_ERR_INVALID, "nearest neighbours need 2 <= pop_size < 2^32");
     if (prm->k < 1 || prm->k > PS_KNN_MAX_K || prm->k > N - 1)
         return ps_fail(PS_ERR_INVALID, "nearest neighbours need 1 <= k <= min(pop_size - 1, %u), not k = %u of %llu individuals", PS_KNN_MAX_K,
                        prm->k, (unsigned long long)N);
-    return PS_OK;
-}
-
-// the cross products of two accessory distances stay in 64 bits while a <= 65535 and b = U + core_genes < 2^32
-static int knn_check_core_genes(const ps_knn_params *prm, uint64_t cg)
-{
-    if (prm->metric == PS_KNN_ACC && cg + 65535ull >= (1ull << 32))
-        return ps_fail(PS_ERR_INVALID, "the accessory metric of nearest neighbours needs core_genes + 65535 < 2^32, not %llu core genes",
-                       (unsigned long long)cg);
     return PS_OK;
 }
 
@@ -122,23 +114,15 @@ extern "C" int ps_neighbours_from_counts(const uint32_t *r1, const uint32_t *r2,
     if (!prm || !out || !nbr || !num || !den || (n_pairs && (!r1 || !r2))) return ps_fail(PS_ERR_INVALID, "null argument");
     PSCHK(knn_check_params(prm, pop_size));
     const bool acc = prm->metric == PS_KNN_ACC;
-    if (n_pairs && (acc ? (!acc_inter || !acc_union) : !core_h))
+    const pair_list pairs = { r1, r2, core_h, acc_inter, acc_union, n_pairs, pop_size };
+    if (n_pairs && pairs.lacks(!acc, acc))
         return ps_fail(PS_ERR_INVALID, "null argument: the metric needs its numerators");
-    PSCHK(knn_check_core_genes(prm, core_genes));
+    PSCHK(metric_check_core_genes(prm->metric, core_genes, KNN_NAMES));
     const uint32_t k = prm->k;
     // the partners of every individual in the order of the list (both ends of a pair): first[i] .. first[i + 1]
     std::vector<uint64_t> first(pop_size + 1, 0);
     for (uint64_t p = 0; p < n_pairs; p++) {
-        if (r1[p] >= pop_size || r2[p] >= pop_size)
-            return ps_fail(PS_ERR_INVALID, "pair %llu: index %u is not below pop_size %llu", (unsigned long long)p, std::max(r1[p], r2[p]),
-                           (unsigned long long)pop_size);
-        if (r1[p] == r2[p]) return ps_fail(PS_ERR_INVALID, "pair %llu: both indices are %u", (unsigned long long)p, r1[p]);
-        if (acc) {
-            if (acc_inter[p] > acc_union[p])
-                return ps_fail(PS_ERR_INVALID, "pair %llu: intersection %u above union %u", (unsigned long long)p, acc_inter[p], acc_union[p]);
-            if (acc_union[p] > 65535u)
-                return ps_fail(PS_ERR_INVALID, "pair %llu: union %u above the limit of 65535 accessory genes", (unsigned long long)p, acc_union[p]);
-        }
+        PSCHK(pairs.check(p, acc));
         first[r1[p] + 1]++;
         first[r2[p] + 1]++;
     }
@@ -148,11 +132,7 @@ extern "C" int ps_neighbours_from_counts(const uint32_t *r1, const uint32_t *r2,
     std::vector<uint64_t> fill(first.begin(), first.end() - 1);
     for (uint64_t p = 0; p < n_pairs; p++) {
         cand c;
-        if (acc) ps_tr_acc_distance(acc_inter[p], acc_union[p], core_genes, &c.num, &c.den);
-        else {
-            c.num = core_h[p] / 2;
-            c.den = core_sites;
-        }
+        pairs.distance(p, acc, core_sites, core_genes, &c.num, &c.den);
         c.j = r2[p];
         all[fill[r1[p]]++] = c;
         c.j = r1[p];
@@ -177,11 +157,7 @@ extern "C" int ps_neighbours_from_counts(const uint32_t *r1, const uint32_t *r2,
             num[i * k + n] = den[i * k + n] = 0;
         }
     }
-    memset(out, 0, sizeof *out);
-    out->pop_size = pop_size;
-    out->pairs = n_pairs;
-    out->core_sites = core_sites;
-    out->core_genes = core_genes;
+    readout_head(out, pop_size, n_pairs, core_sites, core_genes);
     out->metric = (uint64_t)prm->metric;
     out->k = k;
     knn_finish(out, nbr, den);
@@ -232,13 +208,12 @@ static int knn_device(core_band_source &src, ps_population *acc, uint64_t L, con
     const uint32_t N = (uint32_t)c0->cfg.pop_size, k = prm->k;
     const uint64_t cg = acc->cfg.core_genes, nk = (uint64_t)N * k;
     const bool acc_metric = prm->metric == PS_KNN_ACC;
-    PSCHK(knn_check_core_genes(prm, cg));
+    PSCHK(metric_check_core_genes(prm->metric, cg, KNN_NAMES));
     PSCHK(use_device(c0));
     knn_scratch s;
     PSCHK(knn_scratch_get(c0, N, k, acc_metric, &s));
     // out_row[i] = the output row of internal row i
-    std::vector<uint32_t> out_row(N);
-    for (uint32_t r = 0; r < N; r++) out_row[slot ? slot[r] : r] = r;
+    const std::vector<uint32_t> out_row = row_inverse(slot, N);
     readout_slot &ro = c0->ro[PS_RO_KNN];
     pair_pipeline pl(src, acc);
     hipStream_t sc = pl.sc;
@@ -269,42 +244,35 @@ static int knn_device(core_band_source &src, ps_population *acc, uint64_t L, con
             den_out[to + q] = acc_metric ? (uint64_t)hd[from + q] : L;
         }
     }
-    memset(out, 0, sizeof *out);
-    out->pop_size = N;
-    out->pairs = (uint64_t)N * (N - 1) / 2;
-    out->core_sites = L;
-    out->core_genes = cg;
+    readout_head(out, N, (uint64_t)N * (N - 1) / 2, L, cg);
     out->metric = (uint64_t)prm->metric;
     out->k = k;
     knn_finish(out, nbr_out, den_out);
     return PS_OK;
 }
 
-// ps_nearest_neighbours (m == nullptr) and ps_multi_nearest_neighbours (core, acc: shard 0's handles; the selection on shard 0
-// against its accessory replica, the row map from shard 0's simulation)
-static int knn_entry(ps_multi *m, ps_population *core, ps_population *acc, const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr, uint64_t *num,
-                     uint64_t *den)
+// behind pair_entry: ps_nearest_neighbours (m == nullptr) and ps_multi_nearest_neighbours (core, acc: shard 0's handles; the
+// selection on shard 0 against its accessory replica, the row map from shard 0's simulation)
+static auto knn_entry(const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr, uint64_t *num, uint64_t *den)
 {
-    PSCHK(knn_check_params(prm, core->cfg.pop_size));
-    core_band_source src;
-    const uint32_t *slot = nullptr;
-    PSCHK(pair_source_open(&src, "nearest_neighbours", "nearest neighbours need", "compares", m, core, acc, prm->metric == PS_KNN_CORE, &slot));
-    return knn_device(src, acc, m ? m->prm.core_size : core->cfg.global_cols, prm, slot, out, nbr, num, den);
+    return [=](ps_multi *m, ps_population *core, ps_population *acc) -> int {
+        PSCHK(knn_check_params(prm, core->cfg.pop_size));
+        core_band_source src;
+        const uint32_t *slot = nullptr;
+        PSCHK(pair_source_open(&src, "nearest_neighbours", "nearest neighbours need", "compares", m, core, acc, prm->metric == PS_KNN_CORE, &slot));
+        return knn_device(src, acc, m ? m->prm.core_size : core->cfg.global_cols, prm, slot, out, nbr, num, den);
+    };
 }
 
 extern "C" int ps_nearest_neighbours(ps_population *core, ps_population *acc, const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr,
                                      uint64_t *num, uint64_t *den)
 {
-    PSCHK(ps_needs_device());
-    if (!core || !acc || !prm || !out || !nbr || !num || !den) return ps_fail(PS_ERR_INVALID, "null argument");
-    return knn_entry(nullptr, core, acc, prm, out, nbr, num, den);
+    return pair_entry(core, acc, prm && out && nbr && num && den, knn_entry(prm, out, nbr, num, den));
 }
 
 extern "C" int ps_sim_nearest_neighbours(ps_sim *s, const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr, uint64_t *num, uint64_t *den)
 {
-    PSCHK(ps_needs_device());
-    if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
-    return ps_nearest_neighbours(s->core, s->acc, prm, out, nbr, num, den);
+    return pair_entry(s, prm && out && nbr && num && den, knn_entry(prm, out, nbr, num, den));
 }
 
 extern "C" int ps_nearest_neighbours_timing(ps_population *core, double *counts_ms, double *select_ms)
@@ -315,8 +283,5 @@ extern "C" int ps_nearest_neighbours_timing(ps_population *core, double *counts_
 
 extern "C" int ps_multi_nearest_neighbours(ps_multi *m, const ps_knn_params *prm, ps_knn_t *out, uint32_t *nbr, uint64_t *num, uint64_t *den)
 {
-    PSCHK(ps_needs_device());
-    if (!m || !prm || !out || !nbr || !num || !den) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (m->shard.size() == 1) return ps_sim_nearest_neighbours(m->shard[0], prm, out, nbr, num, den);
-    return knn_entry(m, m->shard[0]->core, m->shard[0]->acc, prm, out, nbr, num, den);
+    return pair_entry(m, prm && out && nbr && num && den, knn_entry(prm, out, nbr, num, den));
 }

@@ -1,6 +1,7 @@
 // pair_histogram.h -- ps_distance_histogram / ps_sim_distance_histogram / ps_multi_distance_histogram and the host
 // restatement ps_histogram_from_counts (include/pansim_hip.h; the definitions: docs/DISTANCE_HISTOGRAM.md).  Included by
-// pansim_capi.hip behind core_band_source.
+// pansim_capi.hip behind pair_readout.h, whose pair-list reader, band pipeline (pair_source_open, pair_pipeline) and entry
+// bodies it reuses.
 //
 // Both count phases run in INTERNAL row order (no row slot): the set of unordered pairs does not change under one
 // permutation applied to both matrices, and inside a simulation the two matrices hold the same individuals in the same
@@ -57,9 +58,8 @@ extern "C" int ps_histogram_from_counts(const uint32_t *core_h, const uint32_t *
     if (!core_h || !acc_inter || !acc_union || !prm || !out || !joint) return ps_fail(PS_ERR_INVALID, "null argument");
     PSCHK(pair_hist_check_params(prm));
     if (n_pairs < 1) return ps_fail(PS_ERR_INVALID, "a distance histogram needs at least one pair (pop_size >= 2)");
-    for (uint64_t k = 0; k < n_pairs; k++)
-        if (acc_inter[k] > acc_union[k])
-            return ps_fail(PS_ERR_INVALID, "pair %llu: intersection %u above union %u", (unsigned long long)k, acc_inter[k], acc_union[k]);
+    const pair_list pairs = { nullptr, nullptr, core_h, acc_inter, acc_union, n_pairs, 0 };
+    for (uint64_t k = 0; k < n_pairs; k++) PSCHK(pairs.check_acc(k, false));
     unsigned long long w[PS_PH_WORDS] = {};
     w[PS_PH_MIN] = ~0ull;
     unsigned __int128 sq = 0;
@@ -91,90 +91,13 @@ extern "C" int ps_histogram_from_counts(const uint32_t *core_h, const uint32_t *
         if (undefined) w[PS_PH_UNDEF]++;
         else joint[(size_t)bc * a.Ba + ba]++;
     }
-    memset(out, 0, sizeof *out);
-    out->pairs = n_pairs;
-    out->core_sites = core_sites;
-    out->core_genes = core_genes;
+    readout_head(out, 0, n_pairs, core_sites, core_genes);
     out->core_bins = prm->core_bins;
     out->acc_bins = prm->acc_bins;
     out->core_span = S;
     pair_hist_finish(out, w);
     return PS_OK;
 }
-
-static int pair_hist_handles(const ps_population *core, const ps_population *acc, const char *call, const char *what = "a distance histogram needs")
-{
-    if (!core->cfg.core || acc->cfg.core)
-        return ps_fail(PS_ERR_INVALID, "%s takes a core handle first and an accessory handle second", call);
-    if (core->cfg.pop_size != acc->cfg.pop_size)
-        return ps_fail(PS_ERR_INVALID, "%s: the core handle holds %llu individuals, the accessory handle %llu", call,
-                       (unsigned long long)core->cfg.pop_size, (unsigned long long)acc->cfg.pop_size);
-    if (core->device != acc->device) return ps_fail(PS_ERR_INVALID, "%s: the two handles live on different devices", call);
-    if (core->cfg.pop_size < 2) return ps_fail(PS_ERR_INVALID, "%s pop_size >= 2", what);
-    if (acc->d.G > 65535) return ps_fail(PS_ERR_INVALID, "%s at most 65535 accessory genes (u16 intersection counts)", what);
-    return PS_OK;
-}
-
-// The per-band pipeline of the all-pairs read-outs (histogram, clusters) over the core stream of src.c0 and the stream of the
-// accessory handle on the same device; both idle on entry.  Per band: core_counts() on the core stream, acc_counts() on the
-// accessory stream behind the last consumer that read the scratch, consume() on the core stream behind both.  Every piece of
-// work is timed into a group (event_timer); finish() synchronises both streams and leaves the groups' totals in the read-out's slot.
-struct pair_pipeline : event_timer {
-    core_band_source &src;
-    ps_population *c0, *acc;
-    hipStream_t sc, sa;
-    acc_padded A;                   // (all null without accessory counts: the kernels take I = U = 0)
-    bool acc_on = false, consumed = false;
-    hipEvent_t ev_acc = nullptr, ev_used = nullptr;
-
-    pair_pipeline(core_band_source &s, ps_population *a) : src(s), c0(s.c0), acc(a), sc(s.c0->stream), sa(a->stream) {}
-    // want_acc: the accessory counts are read at all; the padded rows and row counts on the accessory stream (G == 0: nothing)
-    int open(bool want_acc)
-    {
-        acc_on = want_acc && acc->d.G > 0;
-        if (acc_on) PSCHK(acc_rows_padded(acc, sa, &A));
-        PSCHK(make(&ev_acc));
-        return make(&ev_used);
-    }
-    const uint16_t *In() const { return acc_on ? (const uint16_t *)acc->d_davg_in : nullptr; }
-    // body(lo, nrows) for every band of the source
-    template <class B>
-    int for_bands(B &&body)
-    {
-        const core_davg_bands &b = src.b;
-        for (uint32_t lo = b.c0; lo < b.c_end; lo += b.band) PSCHK(body(lo, std::min(b.band, b.c_end - lo)));
-        return PS_OK;
-    }
-    int core_counts(int group, uint32_t lo, uint32_t nrows)
-    {
-        return timed(group, sc, [&]() { return src.counts(lo, nrows); });
-    }
-    int acc_counts(int group, uint32_t lo, uint32_t nrows)
-    {
-        if (!acc_on) return PS_OK;
-        if (consumed) HIPCHK(hipStreamWaitEvent(sa, ev_used, 0));
-        // (a wave of the contraction stores 64 whole rows: the scratch's band is a multiple of 256)
-        PSCHK(timed(group, sa, [&]() { return acc_intersections_band(acc, A, 2u, ((uint64_t)src.b.band + 255) & ~255ull, lo, nrows, sa); }));
-        HIPCHK(hipEventRecord(ev_acc, sa));
-        HIPCHK(hipStreamWaitEvent(sc, ev_acc, 0));
-        return PS_OK;
-    }
-    template <class W>
-    int consume(int group, W &&work)
-    {
-        PSCHK(timed(group, sc, work));
-        HIPCHK(hipEventRecord(ev_used, sc));
-        consumed = true;
-        return PS_OK;
-    }
-    // the end of a read-out: everything queued on both streams complete, the first `groups` totals in its slot
-    int finish(readout_slot &ro, int groups)
-    {
-        HIPCHK(hipStreamSynchronize(sa));
-        HIPCHK(hipStreamSynchronize(sc));
-        return collect(ro, groups);
-    }
-};
 
 template <bool BIN, bool MOM>
 static int pair_hist_launch(const pair_pipeline &pl, uint32_t lo, uint32_t nrows, const ps_ph_args &a, unsigned long long *d_ph)
@@ -260,11 +183,7 @@ static int pair_hist_device(core_band_source &src, ps_population *acc, uint64_t 
     HIPCHK(hipMemcpyAsync(w, d_ph, sizeof w, hipMemcpyDeviceToHost, sc));
     HIPCHK(hipMemcpyAsync(joint, d_ph + PS_PH_WORDS, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, sc));
     PSCHK(pl.finish(ro, 2));
-    memset(out, 0, sizeof *out);
-    out->pop_size = N;
-    out->pairs = N * (N - 1) / 2;
-    out->core_sites = L;
-    out->core_genes = cg;
+    readout_head(out, N, N * (N - 1) / 2, L, cg);
     out->core_bins = prm->core_bins;
     out->acc_bins = prm->acc_bins;
     out->core_span = S;
@@ -272,55 +191,27 @@ static int pair_hist_device(core_band_source &src, ps_population *acc, uint64_t 
     return PS_OK;
 }
 
-// What the entries of the histogram and of the clusters share behind their own parameter checks, under the name ps_<name> (m ==
-// nullptr: `core` must hold all sites, over which the read-out `verb`s) or ps_multi_<name> (core, acc: shard 0's handles).  The
-// handles checked, `slot` (if asked for) the current row map of `core`, everything queued before the call complete, the band
-// source open in internal order.
-static int pair_source_open(core_band_source *src, const char *name, const char *what, const char *verb, ps_multi *m, ps_population *core,
-                            ps_population *acc, bool core_counts, const uint32_t **slot)
+// behind pair_entry: ps_distance_histogram (m == nullptr) and ps_multi_distance_histogram (core, acc: shard 0's handles; the
+// binning -- with the halving h / 2 behind the sum over the shards -- runs on shard 0 against its accessory replica)
+static auto pair_hist_entry(const ps_pair_hist_params *prm, ps_pair_hist_t *out, uint64_t *joint)
 {
-    const std::string call = std::string(m ? "ps_multi_" : "ps_") + name;
-    PSCHK(pair_hist_handles(core, acc, call.c_str(), what));
-    if (!m && core->cfg.ncols != core->cfg.global_cols)
-        return ps_fail(PS_ERR_INVALID, "%s %s over all %llu core sites; this handle is one site shard ([%llu, %llu)): use ps_multi_%s",
-                       call.c_str(), verb, (unsigned long long)core->cfg.global_cols, (unsigned long long)core->cfg.col_offset,
-                       (unsigned long long)(core->cfg.col_offset + core->cfg.ncols), name);
-    PSCHK(use_device(core));
-    if (slot) PSCHK(rows_current(core, slot));
-    if (m) {
-        PSCHK(ps_multi_sync(m));
-    } else {
-        // everything queued on either handle precedes the count kernels of both (as sim_pair_counts orders them)
-        HIPCHK(hipStreamSynchronize(acc->stream));
-        HIPCHK(hipStreamSynchronize(core->stream));
-    }
-    return src->open(core, m, 0, core->cfg.pop_size, false, core_counts);
-}
-
-// ps_distance_histogram (m == nullptr) and ps_multi_distance_histogram (core, acc: shard 0's handles; the binning -- with the
-// halving h / 2 behind the sum over the shards -- runs on shard 0 against its accessory replica)
-static int pair_hist_entry(ps_multi *m, ps_population *core, ps_population *acc, const ps_pair_hist_params *prm, ps_pair_hist_t *out,
-                           uint64_t *joint)
-{
-    PSCHK(pair_hist_check_params(prm));
-    core_band_source src;
-    PSCHK(pair_source_open(&src, "distance_histogram", "a distance histogram needs", "sums", m, core, acc, true, nullptr));
-    return pair_hist_device(src, acc, m ? m->prm.core_size : core->cfg.global_cols, prm, out, joint);
+    return [=](ps_multi *m, ps_population *core, ps_population *acc) -> int {
+        PSCHK(pair_hist_check_params(prm));
+        core_band_source src;
+        PSCHK(pair_source_open(&src, "distance_histogram", "a distance histogram needs", "sums", m, core, acc, true, nullptr));
+        return pair_hist_device(src, acc, m ? m->prm.core_size : core->cfg.global_cols, prm, out, joint);
+    };
 }
 
 extern "C" int ps_distance_histogram(ps_population *core, ps_population *acc, const ps_pair_hist_params *prm, ps_pair_hist_t *out,
                                      uint64_t *joint)
 {
-    PSCHK(ps_needs_device());
-    if (!core || !acc || !prm || !out || !joint) return ps_fail(PS_ERR_INVALID, "null argument");
-    return pair_hist_entry(nullptr, core, acc, prm, out, joint);
+    return pair_entry(core, acc, prm && out && joint, pair_hist_entry(prm, out, joint));
 }
 
 extern "C" int ps_sim_distance_histogram(ps_sim *s, const ps_pair_hist_params *prm, ps_pair_hist_t *out, uint64_t *joint)
 {
-    PSCHK(ps_needs_device());
-    if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
-    return ps_distance_histogram(s->core, s->acc, prm, out, joint);
+    return pair_entry(s, prm && out && joint, pair_hist_entry(prm, out, joint));
 }
 
 extern "C" int ps_distance_histogram_timing(ps_population *core, double *counts_ms, double *binning_ms)
@@ -331,8 +222,5 @@ extern "C" int ps_distance_histogram_timing(ps_population *core, double *counts_
 
 extern "C" int ps_multi_distance_histogram(ps_multi *m, const ps_pair_hist_params *prm, ps_pair_hist_t *out, uint64_t *joint)
 {
-    PSCHK(ps_needs_device());
-    if (!m || !prm || !out || !joint) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (m->shard.size() == 1) return ps_sim_distance_histogram(m->shard[0], prm, out, joint);
-    return pair_hist_entry(m, m->shard[0]->core, m->shard[0]->acc, prm, out, joint);
+    return pair_entry(m, prm && out && joint, pair_hist_entry(prm, out, joint));
 }

@@ -4950,6 +4950,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 // core allele counts and diversity (ps_site_allele_counts, ps_core_diversity, ps_diversity_from_counts, ps_multi_*)
 #include "core_diversity.h"
 
+// the host frame of the all-pairs read-outs below: pair-list reader, metric checks, band pipeline, entry bodies
+#include "pair_readout.h"
+
 // joint core x accessory distance histogram over all pairs (ps_distance_histogram, ps_histogram_from_counts, ps_multi_*)
 #include "pair_histogram.h"
 

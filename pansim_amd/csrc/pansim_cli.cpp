@@ -214,6 +214,23 @@ static void write_pairs_tsv(FILE *f, const std::vector<double> &cd, const std::v
     }
 }
 
+// the output file <outpref><suffix>, created or cut to nothing
+static FILE *open_out(const std::string &outpref, const char *suffix)
+{
+    FILE *f = fopen((outpref + suffix).c_str(), "w");
+    if (!f) die(1, "Error: cannot create " + outpref + suffix);
+    return f;
+}
+
+// the value of a --<name>_metric flag: core (0) or acc (1), the constants of every metric of include/pansim_hip.h
+static int32_t metric_flag(std::map<std::string, std::string> &val, const char *name)
+{
+    const std::string &v = val[name];
+    if (v != "core" && v != "acc") die(101, std::string("pansim: --") + name + " must be core or acc, not \"" + v + "\"");
+    return v == "acc" ? 1 : 0;
+}
+static_assert(PS_TREE_CORE == 0 && PS_TREE_ACC == 1 && PS_KNN_CORE == 0 && PS_KNN_ACC == 1 && PS_LD_CORE == 0 && PS_LD_ACC == 1, "metric_flag");
+
 #define CK(call)                                                        \
     do {                                                                \
         if ((call) != PS_OK) die(101, std::string("pansim: ") + ps_last_error()); \
@@ -354,13 +371,9 @@ int main(int argc, char **argv)
     if (present["print_clusters"] && cluster_prm.core_max_d == UINT64_MAX && cluster_prm.acc_den == 0)
         die(101, "pansim: --print_clusters needs --cluster_core_max, --cluster_acc_max or both");
     // --print_tree: its metric is checked whether or not it is given
-    ps_tree_params tree_prm = { PS_TREE_CORE };
-    if (val["tree_metric"] == "acc") tree_prm.metric = PS_TREE_ACC;
-    else if (val["tree_metric"] != "core") die(101, "pansim: --tree_metric must be core or acc, not \"" + val["tree_metric"] + "\"");
+    const ps_tree_params tree_prm = { metric_flag(val, "tree_metric") };
     // --print_upgma: its metric is checked whether or not it is given
-    ps_tree_params upgma_prm = { PS_TREE_CORE };
-    if (val["upgma_metric"] == "acc") upgma_prm.metric = PS_TREE_ACC;
-    else if (val["upgma_metric"] != "core") die(101, "pansim: --upgma_metric must be core or acc, not \"" + val["upgma_metric"] + "\"");
+    const ps_tree_params upgma_prm = { metric_flag(val, "upgma_metric") };
     // (the limits of ps_upgma_tree that the flags already decide, before any device work; exact after --load_state as well:
     // pop_size and core_genes must be the state file's, ps_sim_load refuses a file that differs)
     if (present["print_upgma"]) {
@@ -370,9 +383,7 @@ int main(int argc, char **argv)
             die(101, "pansim: --upgma_metric acc needs core_genes >= 1, not --core_genes " + std::to_string(p.core_genes));
     }
     // --print_knn: its metric is checked whether or not it is given
-    ps_knn_params knn_prm = { PS_KNN_CORE, 0 };
-    if (val["knn_metric"] == "acc") knn_prm.metric = PS_KNN_ACC;
-    else if (val["knn_metric"] != "core") die(101, "pansim: --knn_metric must be core or acc, not \"" + val["knn_metric"] + "\"");
+    ps_knn_params knn_prm = { metric_flag(val, "knn_metric"), 0 };
     const bool print_knn = !val["print_knn"].empty();
     if (print_knn) {
         const std::string &t = val["print_knn"];
@@ -385,9 +396,7 @@ int main(int argc, char **argv)
         knn_prm.k = (uint32_t)k;
     }
     // --print_genealogy: the bins and the metric of its clock histogram are checked whether or not it is given
-    ps_clock_params clock_prm = { PS_KNN_CORE, 32, 64, 0, 0 };
-    if (val["clock_metric"] == "acc") clock_prm.metric = PS_KNN_ACC;
-    else if (val["clock_metric"] != "core") die(101, "pansim: --clock_metric must be core or acc, not \"" + val["clock_metric"] + "\"");
+    ps_clock_params clock_prm = { metric_flag(val, "clock_metric"), 32, 64, 0, 0 };
     {
         const std::string &b = val["clock_bins"];
         unsigned long long bt = 0, bx = 0;
@@ -402,9 +411,7 @@ int main(int argc, char **argv)
     }
     // --print_ld: its metric, bins and selection are checked whether or not it is given
     ps_ld_params ld_prm = { 64, 1, 1, 4096 };
-    int32_t ld_metric = PS_LD_CORE;
-    if (val["ld_metric"] == "acc") ld_metric = PS_LD_ACC;
-    else if (val["ld_metric"] != "core") die(101, "pansim: --ld_metric must be core or acc, not \"" + val["ld_metric"] + "\"");
+    const int32_t ld_metric = metric_flag(val, "ld_metric");
     {
         const std::string &b = val["ld_bins"];
         unsigned long long br = 0, bl = 0;
@@ -473,8 +480,7 @@ int main(int argc, char **argv)
     auto distances = [&](double *c, double *a) { return multi ? ps_multi_pairwise_distances(multi, c, a) : ps_sim_pairwise_distances(sim, c, a); };
 
     if (p.print_selection) {                                           // main.rs:321-331
-        FILE *f = fopen((outpref + "_selection.tsv").c_str(), "w");
-        if (!f) die(1, "Error: cannot create " + outpref + "_selection.tsv");
+        FILE *f = open_out(outpref, "_selection.tsv");
         const double *sel = ps_sim_selection(sim);
         for (uint64_t g = 0; g < G; g++) fprintf(f, "%s%s", g ? "\n" : "", fmt(sel[g]).c_str());
         fputc('\n', f);
@@ -488,14 +494,12 @@ int main(int argc, char **argv)
         {
             CK(sync());
             CK(distances(cd.data(), ad.data()));
-            FILE *f = fopen((outpref + ".tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + ".tsv");
+            FILE *f = open_out(outpref, ".tsv");
             write_pairs_tsv(f, cd, ad);
             fclose(f);
             std::vector<double> freqs(G + p.core_genes);
             CK(ps_gene_frequencies(acc, freqs.data()));
-            f = fopen((outpref + "_freqs.txt").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_freqs.txt");
+            f = open_out(outpref, "_freqs.txt");
             for (double x : freqs) fprintf(f, "%s\n", fmt(x).c_str());
             fclose(f);
         }
@@ -505,12 +509,10 @@ int main(int argc, char **argv)
             ps_core_diversity_t dv;
             CK(multi ? ps_multi_site_allele_counts(multi, cnt.data()) : ps_site_allele_counts(ps_sim_core(sim), cnt.data()));
             CK(multi ? ps_multi_core_diversity(multi, &dv, spec.data()) : ps_core_diversity(ps_sim_core(sim), &dv, spec.data()));
-            FILE *f = fopen((outpref + "_core_freqs.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_core_freqs.tsv");
+            FILE *f = open_out(outpref, "_core_freqs.tsv");
             for (uint64_t s = 0; s < p.core_size; s++) fprintf(f, "%u\t%u\t%u\t%u\n", cnt[4 * s], cnt[4 * s + 1], cnt[4 * s + 2], cnt[4 * s + 3]);
             fclose(f);
-            f = fopen((outpref + "_core_diversity.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_core_diversity.tsv");
+            f = open_out(outpref, "_core_diversity.tsv");
             const std::pair<const char *, uint64_t> fields[] = {
                 { "pop_size", dv.pop_size }, { "sites", dv.sites }, { "other_cells", dv.other_cells },
                 { "segregating_sites", dv.segregating_sites }, { "pair_differences", dv.pair_differences },
@@ -526,15 +528,13 @@ int main(int argc, char **argv)
             std::vector<uint64_t> joint((size_t)hist_prm.core_bins * hist_prm.acc_bins);
             ps_pair_hist_t h;
             CK(multi ? ps_multi_distance_histogram(multi, &hist_prm, &h, joint.data()) : ps_sim_distance_histogram(sim, &hist_prm, &h, joint.data()));
-            FILE *f = fopen((outpref + "_dist_hist.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_dist_hist.tsv");
+            FILE *f = open_out(outpref, "_dist_hist.tsv");
             for (uint32_t bc = 0; bc < h.core_bins; bc++)
                 for (uint32_t ba = 0; ba < h.acc_bins; ba++)
                     if (joint[(size_t)bc * h.acc_bins + ba])
                         fprintf(f, "%u\t%u\t%llu\n", bc, ba, (unsigned long long)joint[(size_t)bc * h.acc_bins + ba]);
             fclose(f);
-            f = fopen((outpref + "_dist_hist_summary.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_dist_hist_summary.tsv");
+            f = open_out(outpref, "_dist_hist_summary.tsv");
             const std::pair<const char *, uint64_t> fields[] = {
                 { "pop_size", h.pop_size }, { "pairs", h.pairs }, { "core_sites", h.core_sites }, { "core_genes", h.core_genes },
                 { "core_bins", h.core_bins }, { "acc_bins", h.acc_bins }, { "core_span", h.core_span },
@@ -553,12 +553,10 @@ int main(int argc, char **argv)
             std::vector<uint32_t> labels((size_t)p.pop_size);
             ps_cluster_t c;
             CK(multi ? ps_multi_strain_clusters(multi, &cluster_prm, &c, labels.data()) : ps_sim_strain_clusters(sim, &cluster_prm, &c, labels.data()));
-            FILE *f = fopen((outpref + "_clusters.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_clusters.tsv");
+            FILE *f = open_out(outpref, "_clusters.tsv");
             for (uint64_t k = 0; k < p.pop_size; k++) fprintf(f, "%llu\t%u\n", (unsigned long long)k, labels[k]);
             fclose(f);
-            f = fopen((outpref + "_clusters_summary.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_clusters_summary.tsv");
+            f = open_out(outpref, "_clusters_summary.tsv");
             const std::pair<const char *, uint64_t> fields[] = {
                 { "pop_size", c.pop_size }, { "pairs", c.pairs }, { "core_sites", c.core_sites }, { "core_genes", c.core_genes },
                 { "edges", c.edges }, { "clusters", c.clusters }, { "singletons", c.singletons }, { "largest_cluster", c.largest_cluster },
@@ -574,14 +572,12 @@ int main(int argc, char **argv)
             ps_tree_t t;
             CK(multi ? ps_multi_linkage_tree(multi, &tree_prm, &t, lo.data(), hi.data(), num.data(), den.data())
                      : ps_sim_linkage_tree(sim, &tree_prm, &t, lo.data(), hi.data(), num.data(), den.data()));
-            FILE *f = fopen((outpref + "_tree.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_tree.tsv");
+            FILE *f = open_out(outpref, "_tree.tsv");
             for (uint64_t k = 0; k < t.edges; k++)
                 fprintf(f, "%u\t%u\t%llu\t%llu\t%s\n", lo[k], hi[k], (unsigned long long)num[k], (unsigned long long)den[k],
                         den[k] ? fmt((double)num[k] / (double)den[k]).c_str() : "NaN");
             fclose(f);
-            f = fopen((outpref + "_tree_summary.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_tree_summary.tsv");
+            f = open_out(outpref, "_tree_summary.tsv");
             const std::pair<const char *, uint64_t> fields[] = {
                 { "pop_size", t.pop_size }, { "pairs", t.pairs }, { "core_sites", t.core_sites }, { "core_genes", t.core_genes },
                 { "metric", t.metric }, { "edges", t.edges }, { "undefined_edges", t.undefined_edges },
@@ -596,8 +592,7 @@ int main(int argc, char **argv)
             ps_upgma_t t;
             CK(multi ? ps_multi_upgma_tree(multi, &upgma_prm, &t, left.data(), right.data(), size.data(), num.data(), den.data())
                      : ps_sim_upgma_tree(sim, &upgma_prm, &t, left.data(), right.data(), size.data(), num.data(), den.data()));
-            FILE *f = fopen((outpref + "_upgma.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_upgma.tsv");
+            FILE *f = open_out(outpref, "_upgma.tsv");
             for (uint64_t k = 0; k < t.merges; k++)
                 fprintf(f, "%llu\t%u\t%u\t%u\t%llu\t%llu\t%s\n", (unsigned long long)(t.pop_size + k), left[k], right[k], size[k],
                         (unsigned long long)num[k], (unsigned long long)den[k], fmt((double)num[k] / (double)den[k]).c_str());
@@ -606,12 +601,10 @@ int main(int argc, char **argv)
             CK(ps_upgma_newick(left.data(), right.data(), num.data(), den.data(), t.pop_size, nullptr, 0, &need));
             std::vector<char> text(need);
             CK(ps_upgma_newick(left.data(), right.data(), num.data(), den.data(), t.pop_size, text.data(), need, &need));
-            f = fopen((outpref + "_upgma.nwk").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_upgma.nwk");
+            f = open_out(outpref, "_upgma.nwk");
             fprintf(f, "%s\n", text.data());
             fclose(f);
-            f = fopen((outpref + "_upgma_summary.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_upgma_summary.tsv");
+            f = open_out(outpref, "_upgma_summary.tsv");
             const std::pair<const char *, uint64_t> fields[] = {
                 { "pop_size", t.pop_size }, { "pairs", t.pairs }, { "core_sites", t.core_sites }, { "core_genes", t.core_genes },
                 { "metric", t.metric }, { "merges", t.merges }, { "distinct_heights", t.distinct_heights }, { "root_num", t.root_num },
@@ -626,14 +619,12 @@ int main(int argc, char **argv)
             ps_knn_t t;
             CK(multi ? ps_multi_nearest_neighbours(multi, &knn_prm, &t, nbr.data(), num.data(), den.data())
                      : ps_sim_nearest_neighbours(sim, &knn_prm, &t, nbr.data(), num.data(), den.data()));
-            FILE *f = fopen((outpref + "_knn.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_knn.tsv");
+            FILE *f = open_out(outpref, "_knn.tsv");
             for (size_t e = 0; e < n * k; e++)
                 fprintf(f, "%llu\t%llu\t%u\t%llu\t%llu\t%s\n", (unsigned long long)(e / k), (unsigned long long)(e % k + 1), nbr[e],
                         (unsigned long long)num[e], (unsigned long long)den[e], den[e] ? fmt((double)num[e] / (double)den[e]).c_str() : "NaN");
             fclose(f);
-            f = fopen((outpref + "_knn_summary.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_knn_summary.tsv");
+            f = open_out(outpref, "_knn_summary.tsv");
             const std::pair<const char *, uint64_t> fields[] = {
                 { "pop_size", t.pop_size }, { "pairs", t.pairs }, { "core_sites", t.core_sites }, { "core_genes", t.core_genes },
                 { "metric", t.metric }, { "k", t.k }, { "undefined_neighbours", t.undefined_neighbours }, { "graph_edges", t.graph_edges },
@@ -646,8 +637,7 @@ int main(int argc, char **argv)
                 fprintf(f, "lineages\t%u\t%llu\t%llu\n", r, (unsigned long long)l.lineages, (unsigned long long)l.largest_lineage);
             }
             fclose(f);
-            f = fopen((outpref + "_lineages.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_lineages.tsv");
+            f = open_out(outpref, "_lineages.tsv");
             for (size_t i = 0; i < n; i++) fprintf(f, "%llu\t%u\n", (unsigned long long)i, labels[i]);
             fclose(f);
         }
@@ -658,14 +648,12 @@ int main(int argc, char **argv)
             ps_ld_t t;
             CK(multi ? ps_multi_locus_ld(multi, ld_metric, &ld_prm, nullptr, 0, &t, index.data(), count.data(), hist.data(), lag_sum.data())
                      : ps_sim_locus_ld(sim, ld_metric, &ld_prm, nullptr, 0, &t, index.data(), count.data(), hist.data(), lag_sum.data()));
-            FILE *f = fopen((outpref + "_ld.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_ld.tsv");
+            FILE *f = open_out(outpref, "_ld.tsv");
             for (size_t l = 0; l < nl; l++)
                 for (size_t r = 0; r < nr; r++)
                     if (hist[l * nr + r]) fprintf(f, "%llu\t%llu\t%llu\n", (unsigned long long)l, (unsigned long long)r, (unsigned long long)hist[l * nr + r]);
             fclose(f);
-            f = fopen((outpref + "_ld_summary.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_ld_summary.tsv");
+            f = open_out(outpref, "_ld_summary.tsv");
             const std::pair<const char *, uint64_t> fields[] = {
                 { "pop_size", t.pop_size }, { "metric", (uint64_t)ld_metric }, { "columns", t.columns }, { "candidates", t.candidates }, { "loci", t.loci },
                 { "pairs", t.pairs }, { "defined_pairs", t.defined_pairs }, { "undefined_pairs", t.undefined_pairs },
@@ -680,8 +668,7 @@ int main(int argc, char **argv)
                 if (n) fprintf(f, "lag\t%llu\t%llu\t%llu\n", (unsigned long long)l, (unsigned long long)n, (unsigned long long)lag_sum[l]);
             }
             fclose(f);
-            f = fopen((outpref + "_ld_loci.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_ld_loci.tsv");
+            f = open_out(outpref, "_ld_loci.tsv");
             for (uint64_t k = 0; k < t.loci; k++) fprintf(f, "%u\t%u\n", index[k], count[k]);
             fclose(f);
         }
@@ -690,8 +677,7 @@ int main(int argc, char **argv)
             std::vector<uint32_t> order(n), coal(n);
             ps_genealogy_t g;
             CK(multi ? ps_multi_genealogy(multi, &g, order.data(), coal.data()) : ps_sim_genealogy(sim, &g, order.data(), coal.data()));
-            FILE *f = fopen((outpref + "_genealogy.tsv").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_genealogy.tsv");
+            FILE *f = open_out(outpref, "_genealogy.tsv");
             for (size_t r = 0; r < n; r++) {
                 if (r + 1 == n) fprintf(f, "%llu\t%u\t\n", (unsigned long long)r, order[r]);
                 else if (coal[r] == PS_GEN_BEYOND) fprintf(f, "%llu\t%u\tbeyond\n", (unsigned long long)r, order[r]);
@@ -702,8 +688,7 @@ int main(int argc, char **argv)
             CK(ps_genealogy_newick(order.data(), coal.data(), n, nullptr, 0, &need));
             std::vector<char> text(need);
             CK(ps_genealogy_newick(order.data(), coal.data(), n, text.data(), need, &need));
-            f = fopen((outpref + "_genealogy.nwk").c_str(), "w");
-            if (!f) die(1, "Error: cannot create " + outpref + "_genealogy.nwk");
+            f = open_out(outpref, "_genealogy.nwk");
             fputs(text.data(), f);
             fclose(f);
             // (a run that recorded no generation -- a loaded state already at --n_gen -- has no divergence times to bin)
@@ -714,14 +699,12 @@ int main(int argc, char **argv)
                 ps_clock_t c;
                 CK(multi ? ps_multi_clock_histogram(multi, &clock_prm, &c, joint.data(), per_time.data())
                          : ps_sim_clock_histogram(sim, &clock_prm, &c, joint.data(), per_time.data()));
-                f = fopen((outpref + "_clock.tsv").c_str(), "w");
-                if (!f) die(1, "Error: cannot create " + outpref + "_clock.tsv");
+                f = open_out(outpref, "_clock.tsv");
                 for (size_t t = 0; t < nt; t++)
                     for (size_t x = 0; x < bx; x++)
                         if (joint[t * bx + x]) fprintf(f, "%llu\t%llu\t%llu\n", (unsigned long long)t, (unsigned long long)x, (unsigned long long)joint[t * bx + x]);
                 fclose(f);
-                f = fopen((outpref + "_clock_summary.tsv").c_str(), "w");
-                if (!f) die(1, "Error: cannot create " + outpref + "_clock_summary.tsv");
+                f = open_out(outpref, "_clock_summary.tsv");
                 const std::pair<const char *, uint64_t> fields[] = {
                     { "pop_size", c.pop_size }, { "pairs", c.pairs }, { "core_sites", c.core_sites }, { "core_genes", c.core_genes },
                     { "metric", c.metric }, { "time_bins", c.time_bins }, { "dist_bins", c.dist_bins }, { "time_span", c.time_span },
@@ -757,8 +740,7 @@ int main(int argc, char **argv)
         }
     }
     if (p.print_dist) {                                                // main.rs:531-548
-        FILE *f = fopen((outpref + "_per_gen.tsv").c_str(), "w");
-        if (!f) die(1, "Error: cannot create " + outpref + "_per_gen.tsv");
+        FILE *f = open_out(outpref, "_per_gen.tsv");
         for (int32_t j = 0; j < p.n_gen; j++)
             fprintf(f, "%s\t%s\t%s\t%s\n", fmt(avg_core[j]).c_str(), fmt(std_core[j]).c_str(),
                     fmt(avg_acc[j]).c_str(), fmt(std_acc[j]).c_str());

@@ -1,6 +1,6 @@
 // strain_clusters.h -- ps_strain_clusters / ps_sim_strain_clusters / ps_multi_strain_clusters and the host restatement
 // ps_clusters_from_counts (include/pansim_hip.h; the definitions: docs/STRAIN_CLUSTERS.md).  Included by pansim_capi.hip
-// behind pair_histogram.h, whose band source, count phases and stream ordering (pair_pipeline) it reuses as they are.
+// behind pair_readout.h, whose pair-list reader, band pipeline (pair_source_open, pair_pipeline) and entry bodies it reuses.
 //
 // As the histogram, everything on the device runs in INTERNAL row order: per band the core numerators on the core stream,
 // the accessory intersections on the accessory stream, pair_edge_kernel on the core stream behind both; after the last band
@@ -58,16 +58,13 @@ extern "C" int ps_clusters_from_counts(const uint32_t *r1, const uint32_t *r2, c
     if (!prm || !out || !labels || (n_pairs && (!r1 || !r2))) return ps_fail(PS_ERR_INVALID, "null argument");
     bool core_on, acc_on;
     PSCHK(cluster_check_params(prm, &core_on, &acc_on));
-    if (n_pairs && ((core_on && !core_h) || (acc_on && (!acc_inter || !acc_union))))
+    const pair_list pairs = { r1, r2, core_h, acc_inter, acc_union, n_pairs, pop_size };
+    if (n_pairs && pairs.lacks(core_on, acc_on))
         return ps_fail(PS_ERR_INVALID, "null argument: an active criterion needs its numerators");
     if (pop_size < 2 || pop_size > 0xffffffffull) return ps_fail(PS_ERR_INVALID, "strain clusters need 2 <= pop_size < 2^32");
     for (uint64_t k = 0; k < n_pairs; k++) {
-        if (r1[k] >= pop_size || r2[k] >= pop_size)
-            return ps_fail(PS_ERR_INVALID, "pair %llu: index %u is not below pop_size %llu", (unsigned long long)k, std::max(r1[k], r2[k]),
-                           (unsigned long long)pop_size);
-        if (r1[k] == r2[k]) return ps_fail(PS_ERR_INVALID, "pair %llu: both indices are %u", (unsigned long long)k, r1[k]);
-        if (acc_on && acc_inter[k] > acc_union[k])
-            return ps_fail(PS_ERR_INVALID, "pair %llu: intersection %u above union %u", (unsigned long long)k, acc_inter[k], acc_union[k]);
+        PSCHK(pairs.check_indices(k));
+        if (acc_on) PSCHK(pairs.check_acc(k, false));       // (no u16 limit: the edges are decided pair by pair)
     }
     const ps_cl_args a = cluster_args(prm, core_genes);
     // union-find, the smaller root kept: root(k) is the smallest member of k's set
@@ -77,7 +74,7 @@ extern "C" int ps_clusters_from_counts(const uint32_t *r1, const uint32_t *r2, c
         while (parent[x] != x) x = parent[x] = parent[parent[x]];
         return x;
     };
-    memset(out, 0, sizeof *out);
+    readout_head(out, pop_size, n_pairs, core_sites, core_genes);
     for (uint64_t k = 0; k < n_pairs; k++) {
         const uint32_t h = core_on ? core_h[k] : 0u, in = acc_on ? acc_inter[k] : 0u, un = acc_on ? acc_union[k] : 0u;
         bool undefined, edge;
@@ -91,10 +88,6 @@ extern "C" int ps_clusters_from_counts(const uint32_t *r1, const uint32_t *r2, c
         parent[std::max(x, y)] = std::min(x, y);
     }
     for (uint64_t k = 0; k < pop_size; k++) parent[k] = root((uint32_t)k);
-    out->pop_size = pop_size;
-    out->pairs = n_pairs;
-    out->core_sites = core_sites;
-    out->core_genes = core_genes;
     cluster_finish(parent.data(), pop_size, labels, out);
     return PS_OK;
 }
@@ -188,11 +181,7 @@ static int cluster_device(core_band_source &src, ps_population *acc, uint64_t L,
     HIPCHK(hipMemcpyAsync(rep.data(), d_L, (uint64_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost, sc));
     PSCHK(pl.finish(ro, 3));
     rows_permute(rep.data(), slot, N);
-    memset(out, 0, sizeof *out);
-    out->pop_size = N;
-    out->pairs = (uint64_t)N * (N - 1) / 2;
-    out->core_sites = L;
-    out->core_genes = cg;
+    readout_head(out, N, (uint64_t)N * (N - 1) / 2, L, cg);
     out->edges = w[PS_CL_EDGES];
     out->undefined_pairs = w[PS_CL_UNDEF];
     out->rounds = rounds;
@@ -200,32 +189,29 @@ static int cluster_device(core_band_source &src, ps_population *acc, uint64_t L,
     return PS_OK;
 }
 
-// ps_strain_clusters (m == nullptr) and ps_multi_strain_clusters (core, acc: shard 0's handles; the edges and the labels on
-// shard 0 against its accessory replica, the row map from shard 0's simulation)
-static int cluster_entry(ps_multi *m, ps_population *core, ps_population *acc, const ps_cluster_params *prm, ps_cluster_t *out,
-                         uint32_t *labels)
+// behind pair_entry: ps_strain_clusters (m == nullptr) and ps_multi_strain_clusters (core, acc: shard 0's handles; the edges and
+// the labels on shard 0 against its accessory replica, the row map from shard 0's simulation)
+static auto cluster_entry(const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels)
 {
-    bool core_on, acc_on;
-    PSCHK(cluster_check_params(prm, &core_on, &acc_on));
-    core_band_source src;
-    const uint32_t *slot = nullptr;
-    PSCHK(pair_source_open(&src, "strain_clusters", "strain clusters need", "compares", m, core, acc, core_on, &slot));
-    return cluster_device(src, acc, m ? m->prm.core_size : core->cfg.global_cols, prm, slot, out, labels);
+    return [=](ps_multi *m, ps_population *core, ps_population *acc) -> int {
+        bool core_on, acc_on;
+        PSCHK(cluster_check_params(prm, &core_on, &acc_on));
+        core_band_source src;
+        const uint32_t *slot = nullptr;
+        PSCHK(pair_source_open(&src, "strain_clusters", "strain clusters need", "compares", m, core, acc, core_on, &slot));
+        return cluster_device(src, acc, m ? m->prm.core_size : core->cfg.global_cols, prm, slot, out, labels);
+    };
 }
 
 extern "C" int ps_strain_clusters(ps_population *core, ps_population *acc, const ps_cluster_params *prm, ps_cluster_t *out,
                                   uint32_t *labels)
 {
-    PSCHK(ps_needs_device());
-    if (!core || !acc || !prm || !out || !labels) return ps_fail(PS_ERR_INVALID, "null argument");
-    return cluster_entry(nullptr, core, acc, prm, out, labels);
+    return pair_entry(core, acc, prm && out && labels, cluster_entry(prm, out, labels));
 }
 
 extern "C" int ps_sim_strain_clusters(ps_sim *s, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels)
 {
-    PSCHK(ps_needs_device());
-    if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
-    return ps_strain_clusters(s->core, s->acc, prm, out, labels);
+    return pair_entry(s, prm && out && labels, cluster_entry(prm, out, labels));
 }
 
 extern "C" int ps_strain_clusters_timing(ps_population *core, double *counts_ms, double *edges_ms, double *labels_ms)
@@ -236,8 +222,5 @@ extern "C" int ps_strain_clusters_timing(ps_population *core, double *counts_ms,
 
 extern "C" int ps_multi_strain_clusters(ps_multi *m, const ps_cluster_params *prm, ps_cluster_t *out, uint32_t *labels)
 {
-    PSCHK(ps_needs_device());
-    if (!m || !prm || !out || !labels) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (m->shard.size() == 1) return ps_sim_strain_clusters(m->shard[0], prm, out, labels);
-    return cluster_entry(m, m->shard[0]->core, m->shard[0]->acc, prm, out, labels);
+    return pair_entry(m, prm && out && labels, cluster_entry(prm, out, labels));
 }

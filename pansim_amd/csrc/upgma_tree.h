@@ -1,6 +1,6 @@
 // upgma_tree.h -- ps_upgma_tree / ps_sim_upgma_tree / ps_multi_upgma_tree, the host restatement ps_upgma_from_counts and
-// ps_upgma_newick (include/pansim_hip.h; the definitions: docs/UPGMA_TREE.md).  Included by pansim_capi.hip behind linkage_tree.h,
-// whose parameters (ps_tree_params) and band source (pair_source_open, pair_pipeline) it reuses as they are.
+// ps_upgma_newick (include/pansim_hip.h; the definitions: docs/UPGMA_TREE.md).  Included by pansim_capi.hip behind pair_readout.h,
+// whose pair-list reader, metric checks, band pipeline (pair_source_open, pair_pipeline) and entry bodies it reuses.
 //
 // As the single-linkage tree, everything on the device runs in INTERNAL row order: per band the numerators of the metric asked
 // for (the other metric's count kernels are not launched), then a store kernel on the core stream that widens them into the
@@ -23,12 +23,7 @@ struct upgma_merge {
     uint32_t a, b, size_a, size_b;
 };
 
-static int upgma_check_params(const ps_tree_params *prm)
-{
-    if (prm->metric != PS_TREE_CORE && prm->metric != PS_TREE_ACC)
-        return ps_fail(PS_ERR_INVALID, "the metric of a UPGMA tree is PS_TREE_CORE (0) or PS_TREE_ACC (1), not %d", (int)prm->metric);
-    return PS_OK;
-}
+static const metric_names UPGMA_NAMES = { "a UPGMA tree", "PS_TREE_CORE", "PS_TREE_ACC" };
 
 // the limits that keep every sum in u64 and every cross product in 128 bits
 static int upgma_check_limits(const ps_tree_params *prm, uint64_t N, uint64_t L, uint64_t cg)
@@ -40,10 +35,7 @@ static int upgma_check_limits(const ps_tree_params *prm, uint64_t N, uint64_t L,
     if (prm->metric != PS_TREE_ACC) return PS_OK;
     if (cg < 1)
         return ps_fail(PS_ERR_INVALID, "the accessory metric of a UPGMA tree needs core_genes >= 1 (a pair without genes would be 0 / 0)");
-    if (cg + 65535ull >= (1ull << 32))
-        return ps_fail(PS_ERR_INVALID, "the accessory metric of a UPGMA tree needs core_genes + 65535 < 2^32, not %llu core genes",
-                       (unsigned long long)cg);
-    return PS_OK;
+    return metric_check_core_genes(prm->metric, cg, UPGMA_NAMES);
 }
 
 // m[0 .. N - 1): the merges of a tree over the ids 0 .. N - 1, each set of pairs that merged at the same time in one piece (the
@@ -104,9 +96,10 @@ extern "C" int ps_upgma_from_counts(const uint32_t *r1, const uint32_t *r2, cons
                                     uint64_t *den)
 {
     if (!prm || !out || !left || !right || !size || !num || !den || !r1 || !r2) return ps_fail(PS_ERR_INVALID, "null argument");
-    PSCHK(upgma_check_params(prm));
+    PSCHK(metric_check(prm->metric, UPGMA_NAMES));
     const bool acc = prm->metric == PS_TREE_ACC;
-    if (acc ? (!acc_inter || !acc_union) : !core_h) return ps_fail(PS_ERR_INVALID, "null argument: the metric needs its numerators");
+    const pair_list pairs = { r1, r2, core_h, acc_inter, acc_union, n_pairs, pop_size };
+    if (pairs.lacks(!acc, acc)) return ps_fail(PS_ERR_INVALID, "null argument: the metric needs its numerators");
     PSCHK(upgma_check_limits(prm, pop_size, core_sites, core_genes));
     const uint64_t N = pop_size;
     if (n_pairs != N * (N - 1) / 2)
@@ -115,25 +108,18 @@ extern "C" int ps_upgma_from_counts(const uint32_t *r1, const uint32_t *r2, cons
     std::vector<uint64_t> S(N * N, 0), B(acc ? N * N : 0, 0);
     std::vector<uint8_t> seen(N * N, 0);
     for (uint64_t k = 0; k < n_pairs; k++) {
-        if (r1[k] >= N || r2[k] >= N)
-            return ps_fail(PS_ERR_INVALID, "pair %llu: index %u is not below pop_size %llu", (unsigned long long)k, std::max(r1[k], r2[k]),
-                           (unsigned long long)N);
-        if (r1[k] == r2[k]) return ps_fail(PS_ERR_INVALID, "pair %llu: both indices are %u", (unsigned long long)k, r1[k]);
+        PSCHK(pairs.check_indices(k));
         const uint64_t x = (uint64_t)r1[k] * N + r2[k], y = (uint64_t)r2[k] * N + r1[k];
         if (seen[x])
             return ps_fail(PS_ERR_INVALID, "pair %llu: the pair (%u, %u) is listed twice", (unsigned long long)k, std::min(r1[k], r2[k]),
                            std::max(r1[k], r2[k]));
         seen[x] = seen[y] = 1;
-        if (acc) {
-            if (acc_inter[k] > acc_union[k])
-                return ps_fail(PS_ERR_INVALID, "pair %llu: intersection %u above union %u", (unsigned long long)k, acc_inter[k], acc_union[k]);
-            if (acc_union[k] > 65535u)
-                return ps_fail(PS_ERR_INVALID, "pair %llu: union %u above the limit of 65535 accessory genes", (unsigned long long)k, acc_union[k]);
-            S[x] = S[y] = (uint64_t)(acc_union[k] - acc_inter[k]);
-            B[x] = B[y] = (uint64_t)acc_union[k] + core_genes;
-        } else {
-            S[x] = S[y] = core_h[k] / 2;
-        }
+        if (acc) PSCHK(pairs.check_acc(k, true));
+        // (the sums of a cluster pair start as the pair's own distance; the core den, L for every pair, is not summed)
+        uint64_t num, den;
+        pairs.distance(k, acc, core_sites, core_genes, &num, &den);
+        S[x] = S[y] = num;
+        if (acc) B[x] = B[y] = den;
     }
     // (n_pairs distinct pairs of N (N - 1) / 2 possible ones: the list is complete)
     // The sequential algorithm: N - 1 times the smallest pair of the current clusters under (distance, lo id, hi id).  A cluster
@@ -174,11 +160,7 @@ extern "C" int ps_upgma_from_counts(const uint32_t *r1, const uint32_t *r2, cons
             else if (ps_up_less(key(c, a), key(c, nn[c]))) nn[c] = a;
         }
     }
-    memset(out, 0, sizeof *out);
-    out->pop_size = N;
-    out->pairs = n_pairs;
-    out->core_sites = core_sites;
-    out->core_genes = core_genes;
+    readout_head(out, N, n_pairs, core_sites, core_genes);
     out->metric = (uint64_t)prm->metric;
     return upgma_finish(m, N, acc ? 1 : core_sites, out, left, right, size, num, den);
 }
@@ -291,8 +273,7 @@ static int upgma_device(core_band_source &src, ps_population *acc, uint64_t L, c
     upgma_scratch s;
     PSCHK(upgma_scratch_get(c0, N, acc_metric, &s));
     // out_row[i] = the output row of internal row i: the id of the cluster that starts there
-    std::vector<uint32_t> out_row(N);
-    for (uint32_t k = 0; k < N; k++) out_row[slot ? slot[k] : k] = k;
+    const std::vector<uint32_t> out_row = row_inverse(slot, N);
     readout_slot &ro = c0->ro[PS_RO_UPGMA];
     pair_pipeline pl(src, acc);
     hipStream_t sc = pl.sc;
@@ -358,47 +339,41 @@ static int upgma_device(core_band_source &src, ps_population *acc, uint64_t L, c
             return ps_fail(PS_ERR_STATE, "merge %u of the UPGMA tree joins rows %u and %u of %u in round %u", k, rec[k].a, rec[k].b, N, rec[k].round);
         m[k] = { rec[k].num, rec[k].den, out_row[rec[k].a], out_row[rec[k].b], rec[k].size_a, rec[k].size_b };
     }
-    memset(out, 0, sizeof *out);
-    out->pop_size = N;
-    out->pairs = (uint64_t)N * (N - 1) / 2;
-    out->core_sites = L;
-    out->core_genes = cg;
+    readout_head(out, N, (uint64_t)N * (N - 1) / 2, L, cg);
     out->metric = (uint64_t)prm->metric;
     out->rounds = rounds;
     return upgma_finish(m, N, acc_metric ? 1 : L, out, left, right, size, num, den);
 }
 
-// ps_upgma_tree (m == nullptr) and ps_multi_upgma_tree (core, acc: shard 0's handles; the matrix and the rounds on shard 0
-// against its accessory replica, the row map from shard 0's simulation)
-static int upgma_entry(ps_multi *m, ps_population *core, ps_population *acc, const ps_tree_params *prm, ps_upgma_t *out, uint32_t *left,
-                       uint32_t *right, uint32_t *size, uint64_t *num, uint64_t *den)
+// behind pair_entry: ps_upgma_tree (m == nullptr) and ps_multi_upgma_tree (core, acc: shard 0's handles; the matrix and the
+// rounds on shard 0 against its accessory replica, the row map from shard 0's simulation)
+static auto upgma_entry(const ps_tree_params *prm, ps_upgma_t *out, uint32_t *left, uint32_t *right, uint32_t *size, uint64_t *num,
+                        uint64_t *den)
 {
-    PSCHK(upgma_check_params(prm));
-    core_band_source src;
-    const uint32_t *slot = nullptr;
-    // (the handles first -- their order, the 65535 genes -- then this read-out's own limits, all before anything is queued;
-    // pair_source_open checks the handles once more, which costs nothing)
-    PSCHK(pair_hist_handles(core, acc, m ? "ps_multi_upgma_tree" : "ps_upgma_tree", "a UPGMA tree needs"));
-    const uint64_t L = m ? m->prm.core_size : core->cfg.global_cols;
-    PSCHK(upgma_check_limits(prm, core->cfg.pop_size, L, acc->cfg.core_genes));
-    PSCHK(pair_source_open(&src, "upgma_tree", "a UPGMA tree needs", "averages", m, core, acc, prm->metric == PS_TREE_CORE, &slot));
-    return upgma_device(src, acc, L, prm, slot, out, left, right, size, num, den);
+    return [=](ps_multi *m, ps_population *core, ps_population *acc) -> int {
+        PSCHK(metric_check(prm->metric, UPGMA_NAMES));
+        core_band_source src;
+        const uint32_t *slot = nullptr;
+        // (the handles first -- their order, the 65535 genes -- then this read-out's own limits, all before anything is queued;
+        // pair_source_open checks the handles once more, which costs nothing)
+        PSCHK(pair_handles(core, acc, m ? "ps_multi_upgma_tree" : "ps_upgma_tree", "a UPGMA tree needs"));
+        const uint64_t L = m ? m->prm.core_size : core->cfg.global_cols;
+        PSCHK(upgma_check_limits(prm, core->cfg.pop_size, L, acc->cfg.core_genes));
+        PSCHK(pair_source_open(&src, "upgma_tree", "a UPGMA tree needs", "averages", m, core, acc, prm->metric == PS_TREE_CORE, &slot));
+        return upgma_device(src, acc, L, prm, slot, out, left, right, size, num, den);
+    };
 }
 
 extern "C" int ps_upgma_tree(ps_population *core, ps_population *acc, const ps_tree_params *prm, ps_upgma_t *out, uint32_t *left, uint32_t *right,
                              uint32_t *size, uint64_t *num, uint64_t *den)
 {
-    PSCHK(ps_needs_device());
-    if (!core || !acc || !prm || !out || !left || !right || !size || !num || !den) return ps_fail(PS_ERR_INVALID, "null argument");
-    return upgma_entry(nullptr, core, acc, prm, out, left, right, size, num, den);
+    return pair_entry(core, acc, prm && out && left && right && size && num && den, upgma_entry(prm, out, left, right, size, num, den));
 }
 
 extern "C" int ps_sim_upgma_tree(ps_sim *s, const ps_tree_params *prm, ps_upgma_t *out, uint32_t *left, uint32_t *right, uint32_t *size,
                                  uint64_t *num, uint64_t *den)
 {
-    PSCHK(ps_needs_device());
-    if (!s) return ps_fail(PS_ERR_INVALID, "null argument");
-    return ps_upgma_tree(s->core, s->acc, prm, out, left, right, size, num, den);
+    return pair_entry(s, prm && out && left && right && size && num && den, upgma_entry(prm, out, left, right, size, num, den));
 }
 
 extern "C" int ps_upgma_tree_timing(ps_population *core, double *counts_ms, double *store_ms, double *rounds_ms)
@@ -410,8 +385,5 @@ extern "C" int ps_upgma_tree_timing(ps_population *core, double *counts_ms, doub
 extern "C" int ps_multi_upgma_tree(ps_multi *m, const ps_tree_params *prm, ps_upgma_t *out, uint32_t *left, uint32_t *right, uint32_t *size,
                                    uint64_t *num, uint64_t *den)
 {
-    PSCHK(ps_needs_device());
-    if (!m || !prm || !out || !left || !right || !size || !num || !den) return ps_fail(PS_ERR_INVALID, "null argument");
-    if (m->shard.size() == 1) return ps_sim_upgma_tree(m->shard[0], prm, out, left, right, size, num, den);
-    return upgma_entry(m, m->shard[0]->core, m->shard[0]->acc, prm, out, left, right, size, num, den);
+    return pair_entry(m, prm && out && left && right && size && num && den, upgma_entry(prm, out, left, right, size, num, den));
 }

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Ld, LdParams, check
-from .population import _ptr, _u32
+from .population import _metric as _core_or_acc, _ptr, _u32
 
 
 class LocusLd:
@@ -47,9 +47,7 @@ def _ld_call(fn, prm, loci, *head):
 
 
 def _metric(metric):
-    if metric not in ("core", "acc"):
-        raise ValueError("metric must be \"core\" or \"acc\"")
-    return _lib.PS_LD_CORE if metric == "core" else _lib.PS_LD_ACC
+    return _core_or_acc(metric, _lib.PS_LD_CORE, _lib.PS_LD_ACC)
 
 
 def ld_select_loci(ones, pop_size, min_minor=1, max_loci=4096):

@@ -98,6 +98,40 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _pair_arrays(r1, r2, core_h, acc_inter, acc_union):
+    """the five per-pair arrays of a `*_from_counts` call, flat uint32; a numerator that is not given stays None"""
+    arrays = [None if a is None else _u32(a).reshape(-1) for a in (r1, r2, core_h, acc_inter, acc_union)]
+    if len({a.size for a in arrays if a is not None}) != 1 or arrays[0] is None or arrays[1] is None:
+        raise ValueError("two indices, and one value of every numerator given, per pair")
+    return arrays
+
+
+def _metric(metric, core_const, acc_const):
+    if metric not in ("core", "acc"):
+        raise ValueError('metric must be "core" or "acc"')
+    return core_const if metric == "core" else acc_const
+
+
+def _timing(fn, n, handle):
+    """the n device times in ms of a ps_*_timing entry"""
+    t = [C.c_double() for _ in range(n)]
+    check(fn(handle, *map(C.byref, t)))
+    return tuple(x.value for x in t)
+
+
+class _Summary:
+    """What the result classes share: the fields of the C summary that FIELDS names as integer attributes, and as the head of
+    `as_dict`."""
+    FIELDS = ()
+
+    def _take(self, summary):
+        for name in self.FIELDS:
+            setattr(self, name, int(getattr(summary, name)))
+
+    def _head(self, *more):
+        return {name: getattr(self, name) for name in self.FIELDS + more}
+
+
 def site_tables(core, global_cols, mutations_vec, recombinations_vec, mutation_weights, recombination_weights=None):
     """The host tables of `Population.set_site_rates` (ps_site_tables; no device): a dict with the core plan fields
     `k`, `R`, `cshift`, `has_events`, `ranges` (True: the vectors are contiguous 0/1 masks, the set_rates path), `thresholds`
@@ -146,7 +180,7 @@ def diversity_from_counts(counts, pop_size, spectrum=False):
     return _diversity_call(_lib.load().ps_diversity_from_counts, pop_size, spectrum, _ptr(c), c.shape[0], int(pop_size))
 
 
-class DistanceHistogram:
+class DistanceHistogram(_Summary):
     """The result of `distance_histogram` (ps_pair_hist_t + the bins; docs/DISTANCE_HISTOGRAM.md): the summary fields as
     integer attributes (`core_d_sqsum` one Python integer), `mean_core_distance`, `joint` -- (core_bins, acc_bins) uint64 --
     and the two marginals `core_marginal` / `acc_marginal` (its row and column sums)."""
@@ -154,8 +188,7 @@ class DistanceHistogram:
               "core_clamped", "core_d_min", "core_d_max", "core_d_sum")
 
     def __init__(self, h, joint):
-        for name in self.FIELDS:
-            setattr(self, name, int(getattr(h, name)))
+        self._take(h)
         self.core_d_sqsum = (int(h.core_d_sqsum_hi) << 64) | int(h.core_d_sqsum_lo)
         self.mean_core_distance = float(h.mean_core_distance)
         self.joint = joint.reshape(self.core_bins, self.acc_bins)
@@ -168,7 +201,7 @@ class DistanceHistogram:
         return [-((-k * self.core_span) // self.core_bins) for k in range(self.core_bins + 1)]
 
     def as_dict(self):
-        out = {name: getattr(self, name) for name in self.FIELDS + ("core_d_sqsum", "mean_core_distance")}
+        out = self._head("core_d_sqsum", "mean_core_distance")
         out.update(joint=self.joint, core_marginal=self.core_marginal, acc_marginal=self.acc_marginal)
         return out
 
@@ -205,14 +238,13 @@ def histogram_from_counts(core_h, acc_inter, acc_union, core_sites, core_genes, 
     return _hist_call(_lib.load().ps_histogram_from_counts, prm, _ptr(h), _ptr(i), _ptr(u), h.size, int(core_sites), int(core_genes))
 
 
-class StrainClusters:
+class StrainClusters(_Summary):
     """The result of `strain_clusters` (ps_cluster_t + the labels; docs/STRAIN_CLUSTERS.md): the summary fields as integer
     attributes and `labels` -- pop_size uint32, labels[k] the smallest row of k's cluster."""
     FIELDS = tuple(name for name, _ in Clusters._fields_)
 
     def __init__(self, c, labels):
-        for name in self.FIELDS:
-            setattr(self, name, int(getattr(c, name)))
+        self._take(c)
         self.labels = labels
 
     def sizes(self):
@@ -220,7 +252,7 @@ class StrainClusters:
         return np.sort(np.bincount(self.labels)[np.unique(self.labels)])[::-1]
 
     def as_dict(self):
-        out = {name: getattr(self, name) for name in self.FIELDS}
+        out = self._head()
         out["labels"] = self.labels
         return out
 
@@ -258,23 +290,20 @@ def clusters_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_si
     """`Population.strain_clusters` from any list of pairs (r1, r2) and their numerators (`pairwise_counts` of both
     matrices), on the host alone (ps_clusters_from_counts; no device).  The numerators of a criterion that is not applied
     may be None."""
-    arrays = [None if a is None else _u32(a).reshape(-1) for a in (r1, r2, core_h, acc_inter, acc_union)]
-    if len({a.size for a in arrays if a is not None}) != 1 or arrays[0] is None or arrays[1] is None:
-        raise ValueError("two indices, and one value of every numerator given, per pair")
+    arrays = _pair_arrays(r1, r2, core_h, acc_inter, acc_union)
     prm = _cluster_params(core_sites, core_max, acc_max, core_max_d, acc_ratio)
     return _cluster_call(_lib.load().ps_clusters_from_counts, prm, pop_size, *map(_ptr, arrays), arrays[0].size, int(pop_size),
                          int(core_sites), int(core_genes))
 
 
-class LinkageTree:
+class LinkageTree(_Summary):
     """The result of `linkage_tree` (ps_tree_t + the edges; docs/LINKAGE_TREE.md): the summary fields as integer attributes,
     the tree's edges in ascending order of (distance, lo, hi) -- `lo`, `hi` (uint32 rows, lo < hi), `num`, `den` (uint64; the
     distance of edge k is num[k] / den[k], den 0 = undefined) -- and `distance` (float64, NaN where den is 0)."""
     FIELDS = tuple(name for name, _ in Tree._fields_)
 
     def __init__(self, t, lo, hi, num, den):
-        for name in self.FIELDS:
-            setattr(self, name, int(getattr(t, name)))
+        self._take(t)
         n = self.edges
         self.lo, self.hi, self.num, self.den = lo[:n], hi[:n], num[:n], den[:n]
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -312,15 +341,13 @@ class LinkageTree:
         return self.pop_size - self._kept(num, den)
 
     def as_dict(self):
-        out = {name: getattr(self, name) for name in self.FIELDS}
+        out = self._head()
         out.update(lo=self.lo, hi=self.hi, num=self.num, den=self.den, distance=self.distance)
         return out
 
 
 def _tree_params(metric):
-    if metric not in ("core", "acc"):
-        raise ValueError('metric must be "core" or "acc"')
-    return TreeParams(_lib.PS_TREE_CORE if metric == "core" else _lib.PS_TREE_ACC)
+    return TreeParams(_metric(metric, _lib.PS_TREE_CORE, _lib.PS_TREE_ACC))
 
 
 def _tree_call(fn, prm, pop_size, *head):
@@ -336,14 +363,12 @@ def tree_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_sites,
     """`Population.linkage_tree` from any list of pairs (r1, r2) and their numerators (`pairwise_counts` of both matrices),
     on the host alone (ps_tree_from_counts; no device).  The numerators of the other metric may be None.  A list that does
     not connect everything gives the minimum spanning forest (`edges` < pop_size - 1)."""
-    arrays = [None if a is None else _u32(a).reshape(-1) for a in (r1, r2, core_h, acc_inter, acc_union)]
-    if len({a.size for a in arrays if a is not None}) != 1 or arrays[0] is None or arrays[1] is None:
-        raise ValueError("two indices, and one value of every numerator given, per pair")
+    arrays = _pair_arrays(r1, r2, core_h, acc_inter, acc_union)
     return _tree_call(_lib.load().ps_tree_from_counts, _tree_params(metric), pop_size, *map(_ptr, arrays), arrays[0].size, int(pop_size),
                       int(core_sites), int(core_genes))
 
 
-class UpgmaTree:
+class UpgmaTree(_Summary):
     """The result of `upgma_tree` (ps_upgma_t + the merges; docs/UPGMA_TREE.md): the summary fields as integer attributes and the
     pop_size - 1 merges in the order the sequential algorithm performs them, scipy's linkage matrix with exact fractions --
     merge k creates node pop_size + k (the leaves are the rows), `left`, `right` (uint32) its children, `size` (uint32) its
@@ -351,8 +376,7 @@ class UpgmaTree:
     FIELDS = tuple(name for name, _ in Upgma._fields_)
 
     def __init__(self, t, left, right, size, num, den):
-        for name in self.FIELDS:
-            setattr(self, name, int(getattr(t, name)))
+        self._take(t)
         n = self.merges
         self.left, self.right, self.size, self.num, self.den = left[:n], right[:n], size[:n], num[:n], den[:n]
         self.distance = self.num.astype(np.float64) / self.den.astype(np.float64)
@@ -415,7 +439,7 @@ class UpgmaTree:
         return upgma_newick(self.left, self.right, self.num, self.den, self.pop_size)
 
     def as_dict(self):
-        out = {name: getattr(self, name) for name in self.FIELDS}
+        out = self._head()
         out.update(left=self.left, right=self.right, size=self.size, num=self.num, den=self.den, distance=self.distance)
         return out
 
@@ -447,14 +471,12 @@ def upgma_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_sites
     """`Population.upgma_tree` from the COMPLETE list of pairs (r1, r2), in any order and orientation, and their numerators
     (`pairwise_counts` of both matrices), by the sequential algorithm on the host alone (ps_upgma_from_counts; no device;
     O(pop_size^3) at worst).  The numerators of the other metric may be None."""
-    arrays = [None if a is None else _u32(a).reshape(-1) for a in (r1, r2, core_h, acc_inter, acc_union)]
-    if len({a.size for a in arrays if a is not None}) != 1 or arrays[0] is None or arrays[1] is None:
-        raise ValueError("two indices, and one value of every numerator given, per pair")
+    arrays = _pair_arrays(r1, r2, core_h, acc_inter, acc_union)
     return _upgma_call(_lib.load().ps_upgma_from_counts, _tree_params(metric), pop_size, *map(_ptr, arrays), arrays[0].size, int(pop_size),
                        int(core_sites), int(core_genes))
 
 
-class NearestNeighbours:
+class NearestNeighbours(_Summary):
     """The result of `nearest_neighbours` (ps_knn_t + the lists; docs/NEAREST_NEIGHBOURS.md): the summary fields as integer
     attributes and, as (pop_size, k) arrays, `nbr` (uint32: entry [i, r] is the r-th nearest other individual of row i in
     ascending order of (distance, row); 2^32 - 1 in a slot that a pair list left unfilled), `num`, `den` (uint64; the
@@ -462,8 +484,7 @@ class NearestNeighbours:
     FIELDS = tuple(name for name, _ in Knn._fields_)
 
     def __init__(self, t, nbr, num, den):
-        for name in self.FIELDS:
-            setattr(self, name, int(getattr(t, name)))
+        self._take(t)
         shape = (self.pop_size, self.k)
         self.nbr, self.num, self.den = nbr.reshape(shape), num.reshape(shape), den.reshape(shape)
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -481,17 +502,16 @@ class NearestNeighbours:
         return labels, {name: int(getattr(out, name)) for name, _ in Lineages._fields_}
 
     def as_dict(self):
-        out = {name: getattr(self, name) for name in self.FIELDS}
+        out = self._head()
         out.update(nbr=self.nbr, num=self.num, den=self.den, distance=self.distance)
         return out
 
 
 def _knn_params(k, metric):
-    if metric not in ("core", "acc"):
-        raise ValueError('metric must be "core" or "acc"')
+    m = _metric(metric, _lib.PS_KNN_CORE, _lib.PS_KNN_ACC)
     if not 0 <= int(k) < 2**32:
         raise ValueError("k must fit 32 bits")
-    return KnnParams(_lib.PS_KNN_CORE if metric == "core" else _lib.PS_KNN_ACC, int(k))
+    return KnnParams(m, int(k))
 
 
 def _knn_call(fn, prm, pop_size, *head):
@@ -508,9 +528,7 @@ def neighbours_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_
     """`Population.nearest_neighbours` from any list of pairs (r1, r2) and their numerators (`pairwise_counts` of both
     matrices), on the host alone (ps_neighbours_from_counts; no device).  The numerators of the other metric may be None.
     An individual with fewer than k listed partners has 2^32 - 1, 0, 0 in its unfilled slots."""
-    arrays = [None if a is None else _u32(a).reshape(-1) for a in (r1, r2, core_h, acc_inter, acc_union)]
-    if len({a.size for a in arrays if a is not None}) != 1 or arrays[0] is None or arrays[1] is None:
-        raise ValueError("two indices, and one value of every numerator given, per pair")
+    arrays = _pair_arrays(r1, r2, core_h, acc_inter, acc_union)
     return _knn_call(_lib.load().ps_neighbours_from_counts, _knn_params(k, metric), pop_size, *map(_ptr, arrays), arrays[0].size,
                      int(pop_size), int(core_sites), int(core_genes))
 
@@ -724,9 +742,7 @@ class Population:
 
     def distance_histogram_timing(self):
         """device ms of (the count kernels, the binning kernel) of the last distance_histogram() on this core handle"""
-        a, b = C.c_double(), C.c_double()
-        check(self._lib.ps_distance_histogram_timing(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return _timing(self._lib.ps_distance_histogram_timing, 2, self._h)
 
     def strain_clusters(self, acc, core_max=None, acc_max=None, core_max_d=None, acc_ratio=None):
         """the single-linkage clusters of ALL individuals of this core population and the accessory population `acc` of
@@ -749,9 +765,7 @@ class Population:
 
     def upgma_tree_timing(self):
         """device ms of (the count kernels, the store kernels, the rounds) of the last upgma_tree() on this core handle"""
-        t = [C.c_double() for _ in range(3)]
-        check(self._lib.ps_upgma_tree_timing(self._h, *map(C.byref, t)))
-        return tuple(x.value for x in t)
+        return _timing(self._lib.ps_upgma_tree_timing, 3, self._h)
 
     def nearest_neighbours(self, acc, k, metric="core"):
         """the k nearest other individuals of every individual among ALL of this core population and the accessory population
@@ -761,21 +775,15 @@ class Population:
 
     def nearest_neighbours_timing(self):
         """device ms of (the count kernels, the select kernels) of the last nearest_neighbours() on this core handle"""
-        t = [C.c_double() for _ in range(2)]
-        check(self._lib.ps_nearest_neighbours_timing(self._h, *map(C.byref, t)))
-        return tuple(x.value for x in t)
+        return _timing(self._lib.ps_nearest_neighbours_timing, 2, self._h)
 
     def linkage_tree_timing(self):
         """device ms of (the count kernels, the store kernels, the rounds) of the last linkage_tree() on this core handle"""
-        t = [C.c_double() for _ in range(3)]
-        check(self._lib.ps_linkage_tree_timing(self._h, *map(C.byref, t)))
-        return tuple(x.value for x in t)
+        return _timing(self._lib.ps_linkage_tree_timing, 3, self._h)
 
     def strain_clusters_timing(self):
         """device ms of (the count kernels, the edge kernel, the label rounds) of the last strain_clusters() on this core handle"""
-        t = [C.c_double() for _ in range(3)]
-        check(self._lib.ps_strain_clusters_timing(self._h, *map(C.byref, t)))
-        return tuple(x.value for x in t)
+        return _timing(self._lib.ps_strain_clusters_timing, 3, self._h)
 
     def locus_ld(self, r2_bins=64, lag_bins=1, min_minor=1, max_loci=4096, loci=None):
         """linkage disequilibrium between the columns of this handle -- core sites or accessory genes by its kind
@@ -787,9 +795,7 @@ class Population:
 
     def locus_ld_timing(self):
         """device ms of (counts and selection, packing, the contraction, the pair statistics) of the last locus_ld()"""
-        t = [C.c_double() for _ in range(4)]
-        check(self._lib.ps_locus_ld_timing(self._h, *map(C.byref, t)))
-        return tuple(x.value for x in t)
+        return _timing(self._lib.ps_locus_ld_timing, 4, self._h)
 
     def core_diversity_timing(self):
         """device ms of the counts kernel of the last site_allele_counts() / core_diversity() call"""
