@@ -911,6 +911,79 @@ int ps_ld_from_counts(const uint32_t *locus_index, const uint32_t *locus_count, 
  * before any call. */
 int ps_locus_ld_timing(ps_population *p, double *select_ms, double *pack_ms, double *counts_ms, double *stats_ms);
 
+/* Group differentiation (docs/GROUP_DIFFERENTIATION.md): what the labels of strain_clusters, the trees' clusters_at, the
+ * lineages and the genealogy's clusters say about the matrices.  The reference has no such function (the counts are the grouped
+ * form of population.rs:840-863).  Groups: a distinct label value with at least min_size members is a candidate, candidates are
+ * ranked by (size descending, label ascending), the first max_groups (1 .. PS_GROUPS_MAX) are groups 0 .. K - 1; everyone else
+ * is unassigned (group_of = UINT32_MAX) and takes part in nothing.  K = 0 is PS_ERR_INVALID.  With n_g the group sizes, N_a
+ * their sum and c_{s,g,c} the cells of site s in group g of class c (A, C, G, T, other: the five classes of
+ * docs/CORE_DIVERSITY.md):
+ *   counts[(s K + g) 4 + a]  cells of site s in group g whose byte is 1 << a
+ *   between[g K + h]         sum_s (n_g n_h - sum_c c_{s,g,c} c_{s,h,c}), the (pair, site) differences; g == h: sum_s (n_g^2 -
+ *                            sum_c c^2) / 2; symmetric
+ *   fixed[g K + h]           sites where g and h share no class; g == h: sites where g is monomorphic
+ *   site_within[s]           sum_g (n_g^2 - sum_c c_{s,g,c}^2) / 2
+ *   site_total[s]            (N_a^2 - sum_c (sum_g c_{s,g,c})^2) / 2
+ *   gene_counts[y K + g]     members of g that carry accessory gene y
+ *   acc_between[g K + h]     sum_y (c_g (n_h - c_h) + (n_g - c_g) c_h), presence / absence differences over pairs; g == h: sum_y
+ *                            c_g (n_g - c_g)
+ *   gene_fixed[g K + h]      genes present in every member of g and absent from every member of h
+ *   gene_private[g]          genes with c_g > 0 and c_h = 0 for every other group h
+ * Every integer is exact over ALL pairs and independent of the launch geometry, the sharding and the order of the individuals;
+ * the doubles are formed once from the integers. */
+#define PS_GROUPS_MAX 16
+typedef struct {
+    uint32_t max_groups;               /* 1 .. PS_GROUPS_MAX */
+    uint32_t min_size;                 /* >= 1 */
+} ps_diff_params;
+typedef struct {
+    uint64_t pop_size, sites, genes;   /* N; core sites this result covers; accessory genes (0 without the accessory handle) */
+    uint64_t groups, assigned, unassigned;                 /* K, N_a, N - N_a */
+    uint64_t other_cells;              /* cells of the assigned that are not 1/2/4/8 */
+    uint64_t within_pairs, between_pairs;                  /* sum_g n_g (n_g - 1) / 2; sum_{g<h} n_g n_h */
+    uint64_t within_differences, between_differences;      /* sum_g between[g][g]; sum_{g<h} between[g][h] */
+    double pi_within, pi_between;      /* differences / pairs / sites, 0.0 when a denominator is 0 */
+    double fst;                        /* Hudson: 1 - pi_within / pi_between, 0.0 when pi_between is 0 */
+} ps_diff_t;
+/* The group rules on the host alone (no device is touched; the reference has no such function; population.rs:840-863 grouped):
+ * labels and group_of hold pop_size values, group_label and group_size max_groups (the first *groups written). */
+int ps_groups_from_labels(const uint32_t *labels, uint64_t pop_size, uint32_t max_groups, uint32_t min_size, uint32_t *group_of,
+                          uint32_t *group_label, uint32_t *group_size, uint32_t *groups);
+/* One core handle and, or NULL, the accessory handle of the same individuals on the same device (the reference has no such
+ * function; population.rs:840-863 grouped).  labels: pop_size values in the reference's row order.  group_of: pop_size;
+ * group_label, group_size: max_groups; between, fixed, acc_between, gene_fixed: max_groups^2 (K x K values are written,
+ * densely); gene_private: max_groups; site_within, site_total: ncols; counts: ncols x max_groups x 4 (ncols x K x 4 written);
+ * gene_counts: genes x max_groups.  site_within .. gene_private may each be NULL, and what is not asked for launches no work of
+ * its own; the gene outputs need `acc`.  pop_size <= 65536.  A site-shard core handle answers for its own sites, without an
+ * accessory handle (with one: ps_multi_group_differentiation).  Ordered behind all queued work of both handles; changes no
+ * state.  PS_ERR_NO_DEVICE before anything else when no GPU is visible. */
+int ps_group_differentiation(ps_population *core, ps_population *acc, const uint32_t *labels, const ps_diff_params *prm, ps_diff_t *out,
+                             uint32_t *group_of, uint32_t *group_label, uint32_t *group_size, uint64_t *between, uint64_t *fixed,
+                             uint32_t *site_within, uint32_t *site_total, uint32_t *counts, uint32_t *gene_counts, uint64_t *acc_between,
+                             uint64_t *gene_fixed, uint64_t *gene_private);
+/* The same for the two matrices of a simulation (the reference has no such function; population.rs:840-863 grouped) */
+int ps_sim_group_differentiation(ps_sim *s, const uint32_t *labels, const ps_diff_params *prm, ps_diff_t *out, uint32_t *group_of,
+                                 uint32_t *group_label, uint32_t *group_size, uint64_t *between, uint64_t *fixed, uint32_t *site_within,
+                                 uint32_t *site_total, uint32_t *counts, uint32_t *gene_counts, uint64_t *acc_between,
+                                 uint64_t *gene_fixed, uint64_t *gene_private);
+/* The same for a sharded run (the reference has no such function; population.rs:840-863 grouped): every shard answers for its
+ * own sites, the u64 matrices and the summary integers add, the per-site arrays and the counts concatenate in site order
+ * (core_size sites), the doubles are formed once; the genes from shard 0's accessory replica. */
+int ps_multi_group_differentiation(ps_multi *m, const uint32_t *labels, const ps_diff_params *prm, ps_diff_t *out, uint32_t *group_of,
+                                   uint32_t *group_label, uint32_t *group_size, uint64_t *between, uint64_t *fixed, uint32_t *site_within,
+                                   uint32_t *site_total, uint32_t *counts, uint32_t *gene_counts, uint64_t *acc_between,
+                                   uint64_t *gene_fixed, uint64_t *gene_private);
+/* The core results from a counts table, on the host alone (no device is touched, as ps_diversity_from_counts; the reference has
+ * no such function; population.rs:840-863 grouped).  counts: sites x groups x 4; group_size: groups values that add up to at
+ * most 65536; between, fixed: groups^2; site_within, site_total: sites, or NULL.  out->pop_size = out->assigned = the sum of the
+ * sizes, out->genes = 0.  Counts of a (site, group) that add up to more than the group's size are PS_ERR_INVALID. */
+int ps_differentiation_from_counts(const uint32_t *counts, uint64_t sites, uint32_t groups, const uint32_t *group_size, ps_diff_t *out,
+                                   uint64_t *between, uint64_t *fixed, uint32_t *site_within, uint32_t *site_total);
+/* device ms of the last ps_group_differentiation on this core handle (each shard's own after the ps_multi form; HIP events; the
+ * reference has no such function; population.rs:840-863 grouped): the membership tables, the core pass, the gene pass (0.0
+ * without one).  PS_ERR_STATE before any call. */
+int ps_group_differentiation_timing(ps_population *core, double *members_ms, double *core_ms, double *genes_ms);
+
 #ifdef __cplusplus
 }
 #endif

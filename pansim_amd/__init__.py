@@ -5,7 +5,7 @@ over the C ABI of libpansim_hip.so (include/pansim_hip.h).  All compute runs in 
 HIP kernels; there is no CPU fallback and importing the API without the built library fails.
 """
 from ._lib import LIB_PATH, PansimError, load  # noqa: F401
-from .population import (DistanceHistogram, LinkageTree, NearestNeighbours, Population, StrainClusters, UpgmaTree, clusters_from_counts, diversity_from_counts, draw_parents,  # noqa: F401
+from .population import (DistanceHistogram, GroupDifferentiation, LinkageTree, NearestNeighbours, Population, StrainClusters, UpgmaTree, clusters_from_counts, differentiation_from_counts, diversity_from_counts, draw_parents, groups_from_labels,  # noqa: F401
                          fmt_f64, hamming_bitwise_fast, histogram_from_counts, init_vector, int_to_base, jaccard_distance_fast, neighbours_from_counts,
                          sample_weights, site_tables, standard_deviation, tree_from_counts, upgma_from_counts, upgma_newick)
 from .linkage import LocusLd, ld_from_counts, ld_select_loci  # noqa: F401

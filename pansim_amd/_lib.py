@@ -176,6 +176,21 @@ class Clock(C.Structure):
                                                  "binned_pairs", "num_sum", "den_sum")]
 
 
+PS_GROUPS_MAX = 16
+
+
+class DiffParams(C.Structure):
+    """ps_diff_params: the group rules of ps_group_differentiation (docs/GROUP_DIFFERENTIATION.md)"""
+    _fields_ = [("max_groups", C.c_uint32), ("min_size", C.c_uint32)]
+
+
+class Diff(C.Structure):
+    """ps_diff_t: the summary of ps_group_differentiation / ps_differentiation_from_counts"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "sites", "genes", "groups", "assigned", "unassigned", "other_cells",
+                                                 "within_pairs", "between_pairs", "within_differences", "between_differences")] + \
+               [(name, C.c_double) for name in ("pi_within", "pi_between", "fst")]
+
+
 # every symbol include/pansim_hip.h declares (tests/test_host_logic.py::test_library_exports_every_declared_symbol checks the header against this)
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -322,6 +337,12 @@ SIGNATURES = {
     "ps_ld_select_loci": (_int, [_vp, _u64, _u64, _u32, _u32, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "ps_ld_from_counts": (_int, [_vp, _vp, _vp, _u64, _u64, C.POINTER(LdParams), C.POINTER(Ld), _vp, _vp]),
     "ps_locus_ld_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_groups_from_labels": (_int, [_vp, _u64, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "ps_group_differentiation": (_int, [_vp, _vp, _vp, C.POINTER(DiffParams), C.POINTER(Diff)] + [_vp] * 12),
+    "ps_sim_group_differentiation": (_int, [_vp, _vp, C.POINTER(DiffParams), C.POINTER(Diff)] + [_vp] * 12),
+    "ps_multi_group_differentiation": (_int, [_vp, _vp, C.POINTER(DiffParams), C.POINTER(Diff)] + [_vp] * 12),
+    "ps_differentiation_from_counts": (_int, [_vp, _u64, _u32, _vp, C.POINTER(Diff), _vp, _vp, _vp, _vp]),
+    "ps_group_differentiation_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

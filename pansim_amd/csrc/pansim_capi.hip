@@ -188,7 +188,7 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
 // ms of the last call's timer groups (`timed`: a call has completed)
-enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_COUNT };
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_COUNT };
 struct readout_slot {
     void *d = nullptr;
     uint64_t cap = 0;       // (bytes)
@@ -333,6 +333,9 @@ struct ps_population {
     //                   counts, stats
     //   PS_RO_UPGMA     UPGMA tree (upgma_tree.h): the merge counter, the per-row arrays, the merge records, the N x N u64 sums (two
     //                   matrices under the accessory metric); ms: counts, store, rounds
+    //   PS_RO_DIFF      group differentiation (group_differentiation.h): the words, the group sizes, the groups of the internal rows, the
+    //                   membership fragments, the per-site words, the counts (accessory handle: groups, masks, gene counts); ms: members,
+    //                   core, genes
     readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
@@ -4974,6 +4977,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // linkage disequilibrium of loci (ps_locus_ld, ps_ld_select_loci, ps_ld_from_counts, ps_sim_* and ps_multi_*)
 #include "locus_ld.h"
+
+// group differentiation from labels (ps_group_differentiation, ps_groups_from_labels, ps_differentiation_from_counts, ps_sim_* and ps_multi_*)
+#include "group_differentiation.h"
 
 // the native RCCL provider of ps_exchange_fn (ps_rccl_*, ps_exchange_rccl)
 #include "exchange_rccl.h"

@@ -58,6 +58,9 @@ static const Flag EXT_FLAGS[] = {
     { "print_clusters", "Write the strain clusters of the final population -- the connected components over ALL pairs of the graph that joins two individuals when their core distance is at most --cluster_core_max and their accessory distance at most --cluster_acc_max -- to <outpref>_clusters.tsv (row, label per individual: the label is the smallest row of its cluster) and their summary to <outpref>_clusters_summary.tsv (docs/STRAIN_CLUSTERS.md), beside the usual outputs. Needs at least one of the two thresholds.", nullptr, false },
     { "cluster_core_max", "Largest core distance of a pair that --print_clusters joins. Must be >= 0.0. Without it the core distance is not looked at.", "", true },
     { "cluster_acc_max", "Largest accessory distance of a pair that --print_clusters joins. Must be 0.0 <= X <= 1.0. Without it the accessory distance is not looked at.", "", true },
+    { "print_differentiation", "Write how the strain clusters of the final population -- those of --cluster_core_max / --cluster_acc_max, as --print_clusters finds them -- differ: per group its size, pairwise differences, monomorphic sites and private genes to <outpref>_diff_groups.tsv, per pair of groups the core differences over all cross pairs, the fixed sites, the gene differences and the genes fixed either way to <outpref>_diff_between.tsv, per core site the within-group and total differences to <outpref>_diff_sites.tsv, per accessory gene its carriers in every group to <outpref>_diff_genes.tsv and the summary with pi within, pi between and F_ST to <outpref>_diff_summary.tsv (docs/GROUP_DIFFERENTIATION.md), beside the usual outputs. Needs at least one of the two thresholds and pop_size <= 65536.", nullptr, false },
+    { "diff_max_groups", "Largest number of groups of --print_differentiation: the largest clusters are taken. Must be 1 <= X <= 16.", "16", true },
+    { "diff_min_size", "Smallest cluster that --print_differentiation takes as a group. Must be a whole number >= 1.", "2", true },
     { "print_tree", "Write the single-linkage tree of the final population -- the minimum spanning tree over ALL pairs under the distance chosen by --tree_metric, whose sorted edge weights are the heights at which strains merge -- to <outpref>_tree.tsv (lo, hi, num, den, distance per edge, ascending; the distance is num / den, NaN for an undefined one) and its summary to <outpref>_tree_summary.tsv (docs/LINKAGE_TREE.md), beside the usual outputs.", nullptr, false },
     { "tree_metric", "Distance of --print_tree: core or acc.", "core", true },
     { "print_upgma", "Write the average-linkage (UPGMA) tree of the final population -- the dendrogram over ALL pairs under the distance chosen by --upgma_metric, in which the distance of two clusters is the average over their cross pairs -- to <outpref>_upgma.tsv (node, left, right, size, num, den, distance per merge, in the order the merges are performed; the distance is num / den), as Newick text to <outpref>_upgma.nwk and its summary to <outpref>_upgma_summary.tsv (docs/UPGMA_TREE.md), beside the usual outputs. Needs pop_size <= 16384.", nullptr, false },
@@ -370,6 +373,25 @@ int main(int argc, char **argv)
     }
     if (present["print_clusters"] && cluster_prm.core_max_d == UINT64_MAX && cluster_prm.acc_den == 0)
         die(101, "pansim: --print_clusters needs --cluster_core_max, --cluster_acc_max or both");
+    // --print_differentiation: its two parameters are checked whether or not it is given
+    ps_diff_params diff_prm = { 16, 2 };
+    {
+        auto whole = [&](const char *name, unsigned long long lo, unsigned long long hi, const char *range) {
+            const std::string &t = val[name];
+            unsigned long long v = 0;
+            int used = 0;
+            if (sscanf(t.c_str(), "%llu%n", &v, &used) != 1 || (size_t)used != t.size() || t.find_first_of("+- ") != std::string::npos || v < lo || v > hi)
+                die(101, std::string("pansim: --") + name + " must be " + range + ", not \"" + t + "\"");
+            return (uint32_t)v;
+        };
+        diff_prm.max_groups = whole("diff_max_groups", 1, PS_GROUPS_MAX, "1 <= X <= 16");
+        diff_prm.min_size = whole("diff_min_size", 1, 0xffffffffull, "a whole number >= 1");
+    }
+    if (present["print_differentiation"]) {
+        if (cluster_prm.core_max_d == UINT64_MAX && cluster_prm.acc_den == 0)
+            die(101, "pansim: --print_differentiation needs --cluster_core_max, --cluster_acc_max or both");
+        if (p.pop_size > 65536) die(101, "pansim: --print_differentiation needs pop_size <= 65536, not --pop_size " + std::to_string(p.pop_size));
+    }
     // --print_tree: its metric is checked whether or not it is given
     const ps_tree_params tree_prm = { metric_flag(val, "tree_metric") };
     // --print_upgma: its metric is checked whether or not it is given
@@ -563,6 +585,52 @@ int main(int argc, char **argv)
                 { "within_pairs", c.within_pairs }, { "undefined_pairs", c.undefined_pairs }, { "core_max_d", cluster_prm.core_max_d },
                 { "acc_num", cluster_prm.acc_num }, { "acc_den", cluster_prm.acc_den } };
             for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+            fclose(f);
+        }
+        if (present["print_differentiation"]) {                        // (no counterpart in the reference: docs/GROUP_DIFFERENTIATION.md)
+            const size_t n = (size_t)p.pop_size, M = diff_prm.max_groups, L = (size_t)p.core_size;
+            std::vector<uint32_t> labels(n), group_of(n), glabel(M), gsize(M), within(std::max<size_t>(L, 1)), total(std::max<size_t>(L, 1));
+            ps_cluster_t c;
+            CK(multi ? ps_multi_strain_clusters(multi, &cluster_prm, &c, labels.data()) : ps_sim_strain_clusters(sim, &cluster_prm, &c, labels.data()));
+            const size_t G = (size_t)(p.pan_genes - p.core_genes);
+            std::vector<uint32_t> gc(std::max<size_t>(G * M, 1));
+            std::vector<uint64_t> between(M * M), fixed(M * M), acc_between(M * M), gene_fixed(M * M), gene_private(M);
+            ps_diff_t d;
+            CK(multi ? ps_multi_group_differentiation(multi, labels.data(), &diff_prm, &d, group_of.data(), glabel.data(), gsize.data(), between.data(),
+                                                      fixed.data(), within.data(), total.data(), nullptr, gc.data(), acc_between.data(),
+                                                      gene_fixed.data(), gene_private.data())
+                     : ps_sim_group_differentiation(sim, labels.data(), &diff_prm, &d, group_of.data(), glabel.data(), gsize.data(), between.data(),
+                                                    fixed.data(), within.data(), total.data(), nullptr, gc.data(), acc_between.data(),
+                                                    gene_fixed.data(), gene_private.data()));
+            const size_t K = (size_t)d.groups;
+            FILE *f = open_out(outpref, "_diff_groups.tsv");
+            for (size_t g = 0; g < K; g++)
+                fprintf(f, "%zu\t%u\t%u\t%llu\t%llu\t%llu\n", g, glabel[g], gsize[g], (unsigned long long)between[g * K + g],
+                        (unsigned long long)fixed[g * K + g], (unsigned long long)gene_private[g]);
+            fclose(f);
+            f = open_out(outpref, "_diff_between.tsv");
+            for (size_t g = 0; g < K; g++)
+                for (size_t h = g + 1; h < K; h++)
+                    fprintf(f, "%zu\t%zu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", g, h, (unsigned long long)gsize[g] * gsize[h],
+                            (unsigned long long)between[g * K + h], (unsigned long long)fixed[g * K + h], (unsigned long long)acc_between[g * K + h],
+                            (unsigned long long)gene_fixed[g * K + h], (unsigned long long)gene_fixed[h * K + g]);
+            fclose(f);
+            f = open_out(outpref, "_diff_sites.tsv");
+            for (uint64_t s = 0; s < d.sites; s++) fprintf(f, "%u\t%u\n", within[s], total[s]);
+            fclose(f);
+            f = open_out(outpref, "_diff_genes.tsv");
+            for (uint64_t y = 0; y < d.genes; y++)
+                for (size_t g = 0; g < K; g++) fprintf(f, "%u%c", gc[y * K + g], g + 1 == K ? '\n' : '\t');
+            fclose(f);
+            f = open_out(outpref, "_diff_summary.tsv");
+            const std::pair<const char *, uint64_t> fields[] = {
+                { "pop_size", d.pop_size }, { "sites", d.sites }, { "genes", d.genes }, { "groups", d.groups }, { "assigned", d.assigned },
+                { "unassigned", d.unassigned }, { "other_cells", d.other_cells }, { "within_pairs", d.within_pairs },
+                { "between_pairs", d.between_pairs }, { "within_differences", d.within_differences },
+                { "between_differences", d.between_differences } };
+            for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+            fprintf(f, "pi_within\t%s\npi_between\t%s\nfst\t%s\n", fmt(d.pi_within).c_str(), fmt(d.pi_between).c_str(), fmt(d.fst).c_str());
+            fprintf(f, "diff_max_groups\t%u\ndiff_min_size\t%u\n", diff_prm.max_groups, diff_prm.min_size);
             fclose(f);
         }
         if (present["print_tree"]) {                                   // (no counterpart in the reference: docs/LINKAGE_TREE.md)

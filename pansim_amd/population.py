@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import ClusterParams, Clusters, Config, CoreDiversity, Knn, KnnParams, Lineages, PairHist, PairHistParams, Tree, TreeParams, Upgma, check
+from ._lib import PS_GROUPS_MAX, ClusterParams, Clusters, Config, CoreDiversity, Diff, DiffParams, Knn, KnnParams, Lineages, PairHist, PairHistParams, Tree, TreeParams, Upgma, check
 
 
 def _u32(a):
@@ -533,6 +533,134 @@ def neighbours_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_
                      int(pop_size), int(core_sites), int(core_genes))
 
 
+class GroupDifferentiation(_Summary):
+    """The result of `group_differentiation` (ps_diff_t + the arrays; docs/GROUP_DIFFERENTIATION.md): the integer summary
+    fields as attributes, `pi_within`, `pi_between`, `fst`, and with K = `groups`: `group_of` (pop_size uint32, 2^32 - 1 =
+    unassigned), `group_label`, `group_size` (K), `between`, `fixed` ((K, K) uint64); when asked for `site_within`,
+    `site_total` (sites), `counts` ((sites, K, 4)) and, with an accessory matrix, `gene_counts` ((genes, K)), `acc_between`,
+    `gene_fixed` ((K, K)) and `gene_private` (K).  What was not asked for is None."""
+    FIELDS = tuple(name for name, kind in Diff._fields_ if kind is C.c_uint64)
+
+    def __init__(self, d, **arrays):
+        self._take(d)
+        self.pi_within, self.pi_between, self.fst = float(d.pi_within), float(d.pi_between), float(d.fst)
+        K = self.groups
+        for name, a in arrays.items():
+            if a is not None:
+                if name in ("group_label", "group_size", "gene_private"):
+                    a = a[:K].copy()
+                elif name in ("between", "fixed", "acc_between", "gene_fixed"):
+                    a = a[:K * K].reshape(K, K).copy()
+                elif name == "counts":
+                    a = a[:self.sites * K * 4].reshape(self.sites, K, 4).copy()
+                elif name == "gene_counts":
+                    a = a[:self.genes * K].reshape(self.genes, K).copy()
+            setattr(self, name, a)
+
+    ARRAYS = ("group_of", "group_label", "group_size", "between", "fixed", "site_within", "site_total", "counts", "gene_counts",
+              "acc_between", "gene_fixed", "gene_private")
+
+    def dxy(self):
+        """(K, K) float64: between[g][h] / (n_g n_h sites) off the diagonal, pi() on it"""
+        n = self.group_size.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out = self.between.astype(np.float64) / (np.outer(n, n) * float(self.sites))
+        out[np.diag_indices(self.groups)] = self.pi()
+        return np.nan_to_num(out, nan=0.0, posinf=0.0)
+
+    def pi(self):
+        """K float64: the diversity of each group, between[g][g] / (n_g (n_g - 1) / 2) / sites (0.0 for a group of one)"""
+        n = self.group_size.astype(np.float64)
+        den = n * (n - 1.0) / 2.0 * float(self.sites)
+        return np.divide(np.diag(self.between).astype(np.float64), den, out=np.zeros(self.groups), where=den > 0)
+
+    def site_fst(self):
+        """sites float64 (needs per_site): Hudson's F_ST of every site, 1 - (within / within_pairs) / (between /
+        between_pairs) with between = site_total - site_within; 0.0 where a denominator is 0"""
+        if self.site_within is None or self.site_total is None:
+            raise ValueError("site_fst needs per_site=True")
+        w = self.site_within.astype(np.float64)
+        b = self.site_total.astype(np.float64) - w
+        out = np.zeros(w.size)
+        if self.within_pairs and self.between_pairs:
+            ok = b > 0
+            out[ok] = 1.0 - (w[ok] / self.within_pairs) / (b[ok] / self.between_pairs)
+        return out
+
+    def as_dict(self):
+        out = self._head("pi_within", "pi_between", "fst")
+        out.update({name: getattr(self, name) for name in self.ARRAYS})
+        return out
+
+
+def _diff_params(max_groups, min_size):
+    if not 1 <= int(max_groups) <= PS_GROUPS_MAX:
+        raise ValueError("max_groups must be 1 .. %d" % PS_GROUPS_MAX)
+    if int(min_size) < 1:
+        raise ValueError("min_size must be >= 1")
+    return DiffParams(int(max_groups), int(min_size))
+
+
+def _diff_call(fn, labels, pop_size, sites, genes, max_groups, min_size, per_site, counts, with_genes, *head):
+    """fn(*head, labels, &params, &summary, the twelve arrays) -> GroupDifferentiation"""
+    lab = _u32(labels).reshape(-1)
+    if lab.size != int(pop_size):
+        raise ValueError("one label per individual: %d, not %d" % (int(pop_size), lab.size))
+    prm = _diff_params(max_groups, min_size)
+    M, N, L, G = prm.max_groups, int(pop_size), int(sites), int(genes)
+    a = dict(group_of=np.zeros(max(1, N), np.uint32), group_label=np.zeros(M, np.uint32), group_size=np.zeros(M, np.uint32),
+             between=np.zeros(M * M, np.uint64), fixed=np.zeros(M * M, np.uint64),
+             site_within=np.zeros(max(1, L), np.uint32) if per_site else None,
+             site_total=np.zeros(max(1, L), np.uint32) if per_site else None,
+             counts=np.zeros(max(1, L * M * 4), np.uint32) if counts else None,
+             gene_counts=np.zeros(max(1, G * M), np.uint32) if with_genes else None,
+             acc_between=np.zeros(M * M, np.uint64) if with_genes else None,
+             gene_fixed=np.zeros(M * M, np.uint64) if with_genes else None,
+             gene_private=np.zeros(M, np.uint64) if with_genes else None)
+    d = Diff()
+    check(fn(*head, _ptr(lab), C.byref(prm), C.byref(d), *[_ptr(a[name]) for name in GroupDifferentiation.ARRAYS]))
+    a["group_of"] = a["group_of"][:N]
+    for name in ("site_within", "site_total"):
+        if a[name] is not None:
+            a[name] = a[name][:L]
+    return GroupDifferentiation(d, **a)
+
+
+def groups_from_labels(labels, max_groups=16, min_size=1):
+    """The group rules of `group_differentiation` on the host alone (ps_groups_from_labels; no device): -> (group_of,
+    group_label, group_size).  A label with at least `min_size` members is a candidate; candidates are ranked by (size
+    descending, label ascending) and the first `max_groups` are the groups; group_of is 2^32 - 1 for everyone else."""
+    lab = _u32(labels).reshape(-1)
+    prm = _diff_params(max_groups, min_size)
+    group_of = np.zeros(max(1, lab.size), np.uint32)
+    label, size = np.zeros(prm.max_groups, np.uint32), np.zeros(prm.max_groups, np.uint32)
+    K = C.c_uint32()
+    check(_lib.load().ps_groups_from_labels(_ptr(lab), lab.size, prm.max_groups, prm.min_size, _ptr(group_of), _ptr(label), _ptr(size),
+                                            C.byref(K)))
+    return group_of[:lab.size], label[:K.value].copy(), size[:K.value].copy()
+
+
+def differentiation_from_counts(counts, group_size):
+    """The core results of `group_differentiation` from a (sites, K, 4) table of per-group A, C, G, T counts and the K group
+    sizes, on the host alone (ps_differentiation_from_counts; no device) -> a GroupDifferentiation with `between`, `fixed`,
+    `site_within`, `site_total` and the summary.  Cells a group's counts do not cover are its `other` class."""
+    n = _u32(group_size).reshape(-1)
+    c = np.ascontiguousarray(counts, np.uint32)
+    if c.ndim != 3 or c.shape[1] != n.size or c.shape[2] != 4:
+        raise ValueError("counts must be (sites, groups, 4): A, C, G, T per site and group")
+    K, L = n.size, c.shape[0]
+    if not 1 <= K <= PS_GROUPS_MAX:
+        raise ValueError("1 .. %d groups" % PS_GROUPS_MAX)
+    between, fixed = np.zeros(K * K, np.uint64), np.zeros(K * K, np.uint64)
+    within, total = np.zeros(max(1, L), np.uint32), np.zeros(max(1, L), np.uint32)
+    d = Diff()
+    check(_lib.load().ps_differentiation_from_counts(_ptr(c), L, K, _ptr(n), C.byref(d), _ptr(between), _ptr(fixed), _ptr(within),
+                                                     _ptr(total)))
+    return GroupDifferentiation(d, group_of=None, group_label=None, group_size=n.copy(), between=between, fixed=fixed,
+                                site_within=within[:L], site_total=total[:L], counts=c, gene_counts=None, acc_between=None,
+                                gene_fixed=None, gene_private=None)
+
+
 def draw_parents(weights, seed, generation):
     """population.rs:440-443"""
     w = _f64(weights)
@@ -784,6 +912,18 @@ class Population:
     def strain_clusters_timing(self):
         """device ms of (the count kernels, the edge kernel, the label rounds) of the last strain_clusters() on this core handle"""
         return _timing(self._lib.ps_strain_clusters_timing, 3, self._h)
+
+    def group_differentiation(self, labels, acc=None, max_groups=16, min_size=1, per_site=False, counts=False):
+        """how the groups that `labels` name (one value per individual, the reference's row order: the labels of
+        strain_clusters, clusters_at, lineages ...) differ on this core population and, if given, the accessory population
+        `acc` of the same individuals (ps_group_differentiation; docs/GROUP_DIFFERENTIATION.md) -> a GroupDifferentiation.
+        `per_site`: site_within / site_total as well; `counts`: the (sites, K, 4) per-group allele counts as well."""
+        return _diff_call(self._lib.ps_group_differentiation, labels, self.size, self.ncols, acc.ncols if acc is not None else 0,
+                          max_groups, min_size, per_site, counts, acc is not None, self._h, acc._h if acc is not None else None)
+
+    def group_differentiation_timing(self):
+        """device ms of (the membership tables, the core pass, the gene pass) of the last group_differentiation() on this core handle"""
+        return _timing(self._lib.ps_group_differentiation_timing, 3, self._h)
 
     def locus_ld(self, r2_bins=64, lag_bins=1, min_minor=1, max_loci=4096, loci=None):
         """linkage disequilibrium between the columns of this handle -- core sites or accessory genes by its kind

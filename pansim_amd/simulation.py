@@ -247,6 +247,13 @@ class Simulation:
         prm = _cluster_params(self.params.core_size, core_max, acc_max, core_max_d, acc_ratio)
         return _cluster_call(self._lib.ps_sim_strain_clusters, prm, self.params.pop_size, self._h)
 
+    def group_differentiation(self, labels, max_groups=16, min_size=1, per_site=False, counts=False):
+        """Population.group_differentiation() of the run's two matrices (ps_sim_group_differentiation), labels in the
+        reference's row order: behind every queued generation, and without a change of state"""
+        from .population import _diff_call
+        return _diff_call(self._lib.ps_sim_group_differentiation, labels, self.params.pop_size, self.core_genome.ncols,
+                          self.pan_genome.ncols, max_groups, min_size, per_site, counts, True, self._h)
+
     def linkage_tree(self, metric="core"):
         """Population.linkage_tree() of the run's two matrices (ps_sim_linkage_tree), edges in the reference's row order"""
         from .population import _tree_call, _tree_params
@@ -394,6 +401,13 @@ class MultiSimulation:
         from .population import _cluster_call, _cluster_params
         prm = _cluster_params(self.params.core_size, core_max, acc_max, core_max_d, acc_ratio)
         return _cluster_call(self._lib.ps_multi_strain_clusters, prm, self.params.pop_size, self._h)
+
+    def group_differentiation(self, labels, max_groups=16, min_size=1, per_site=False, counts=False):
+        """Population.group_differentiation() over ALL core sites: the shards' matrices and integers added, their per-site
+        arrays and counts concatenated, the genes from shard 0's accessory replica (ps_multi_group_differentiation)"""
+        from .population import _diff_call
+        return _diff_call(self._lib.ps_multi_group_differentiation, labels, self.params.pop_size, self.params.core_size,
+                          self.pan_genome.ncols, max_groups, min_size, per_site, counts, True, self._h)
 
     def linkage_tree(self, metric="core"):
         """Population.linkage_tree() over ALL core sites: the shards' band counts added and kept on shard 0, the rounds
