@@ -984,6 +984,92 @@ int ps_differentiation_from_counts(const uint32_t *counts, uint64_t sites, uint3
  * without one).  PS_ERR_STATE before any call. */
 int ps_group_differentiation_timing(ps_population *core, double *members_ms, double *core_ms, double *genes_ms);
 
+/* Parsimony of the two matrices on a tree (docs/TREE_PARSIMONY.md): Fitch parsimony of every core site and accessory gene on a
+ * given binary tree -- how often each column changed, which sites changed more often than their alleles require (homoplasy),
+ * and how many sites changed and genes were gained or lost on every branch.  The reference has no such function (its trees are
+ * implicit in the parent draws of population.rs:443; the columns are those of population.rs:840-863).
+ * Tree: merges `left[k]`, `right[k]`, k < merges, of node ids in scipy's numbering as ps_upgma_tree returns them: nodes 0 ..
+ * pop_size - 1 are the leaves (rows of the reference's row order), merge k creates node pop_size + k.  2 <= pop_size <=
+ * PS_PARS_MAX_POP, 1 <= merges <= pop_size - 1, every child id < pop_size + k, left[k] != right[k], no node a child twice; else
+ * PS_ERR_INVALID, found on the host before any device work.  merges < pop_size - 1 is a forest; a node that is nobody's child is
+ * a root, a leaf that is one is uncovered.
+ * States: the class bit of a core cell is its byte if that is 1, 2, 4 or 8, else 16 (`other`, a fifth state); of a gene 1
+ * (absent) or 2 (present).  Up pass: S(leaf) = its class bit, S(node) = S(l) & S(r) if not empty, else S(l) | S(r);
+ * changes[s] = the merges with an empty intersection at column s, the minimum number of changes of the column on the tree.
+ * Down pass (only when a branch, gain or loss output is asked for): X(root) = the lowest bit of S(root); X(c) = X(v) if
+ * X(v) & S(c) is not empty, else the lowest bit of S(c); the branch above c changes at s iff X(c) != X(v), for a gene 1 -> 2 is
+ * a gain and 2 -> 1 a loss.  Over all branches the changing branches of a column are changes[s].
+ *   site_changes[s]                    changes of core site s
+ *   site_hist[PS_PARS_BINS]            sites by their changes, the last bin >= PS_PARS_BINS - 1
+ *   branch_changes[node]               core sites that change on the branch above the node (pop_size + merges values; roots 0)
+ *   gene_changes / _gains / _losses[y] per accessory gene; gains + losses = changes
+ *   branch_gains / branch_losses[node] genes gained / lost on the branch above the node
+ * Every integer is exact and independent of the launch geometry, the sharding and the order of the individuals; ci is formed
+ * once from the integers. */
+#define PS_PARS_BINS 64
+#define PS_PARS_MAX_POP 16384u
+typedef struct {
+    uint64_t pop_size, sites, genes;   /* N; core sites this result covers; accessory genes (0 without a gene output) */
+    uint64_t merges, trees;            /* M; internal roots */
+    uint64_t covered_leaves;           /* leaves that are somebody's child */
+    uint64_t spanning;                 /* 1 iff merges == pop_size - 1 */
+    uint64_t total_changes, changed_sites, max_changes;    /* sum, number of non-zero entries and maximum of site_changes */
+    uint64_t gene_total_changes, gene_total_gains, gene_total_losses;  /* gains and losses 0 when no down pass ran on the genes */
+    /* only when spanning, else 0: min_changes = sum_s (classes_s - 1) with classes_s the distinct class bits among all leaves;
+     * excess_changes = total_changes - min_changes; homoplasic_sites = the sites with changes[s] > classes_s - 1 */
+    uint64_t min_changes, excess_changes, homoplasic_sites;
+    double ci;                         /* consistency index min_changes / total_changes; 0.0 when not spanning or no changes */
+} ps_parsimony_t;
+/* One core handle and, or NULL, the accessory handle of the same individuals on the same device (the reference has no such
+ * function; population.rs:443, :840-863).  site_changes: ncols; site_hist: PS_PARS_BINS; branch_*: pop_size + merges;
+ * gene_*: the accessory handle's genes.  Every output but `out` may be NULL, and what is not asked for launches no work of its
+ * own; the gene outputs and the branch gains / losses need `acc`.  Leaves are mapped through each handle's own row order.  A
+ * site-shard core handle answers for its own sites, without an accessory handle (with one: ps_multi_tree_parsimony).  Ordered
+ * behind all queued work of both handles; changes no state.  PS_ERR_NO_DEVICE before anything else when no GPU is visible. */
+int ps_tree_parsimony(ps_population *core, ps_population *acc, const uint32_t *left, const uint32_t *right, uint64_t merges,
+                      ps_parsimony_t *out, uint32_t *site_changes, uint64_t *site_hist, uint64_t *branch_changes, uint32_t *gene_changes,
+                      uint32_t *gene_gains, uint32_t *gene_losses, uint64_t *branch_gains, uint64_t *branch_losses);
+/* The same for the two matrices of a simulation (the reference has no such function; population.rs:443, :840-863) */
+int ps_sim_tree_parsimony(ps_sim *s, const uint32_t *left, const uint32_t *right, uint64_t merges, ps_parsimony_t *out,
+                          uint32_t *site_changes, uint64_t *site_hist, uint64_t *branch_changes, uint32_t *gene_changes,
+                          uint32_t *gene_gains, uint32_t *gene_losses, uint64_t *branch_gains, uint64_t *branch_losses);
+/* The same for a sharded run (the reference has no such function; population.rs:443, :840-863): every shard answers for its own
+ * sites, the u64 arrays and the summary integers add (max_changes: the largest), site_changes concatenates in site order
+ * (core_size sites), ci is formed once; the genes from shard 0's accessory replica. */
+int ps_multi_tree_parsimony(ps_multi *m, const uint32_t *left, const uint32_t *right, uint64_t merges, ps_parsimony_t *out,
+                            uint32_t *site_changes, uint64_t *site_hist, uint64_t *branch_changes, uint32_t *gene_changes,
+                            uint32_t *gene_gains, uint32_t *gene_losses, uint64_t *branch_gains, uint64_t *branch_losses);
+/* device ms of the last ps_tree_parsimony on this core handle (each shard's own after the ps_multi form; HIP events; the
+ * reference has no such function; population.rs:443): the upload of the schedule, the core pass, the gene pass (0.0 without
+ * one).  PS_ERR_STATE before any call. */
+int ps_tree_parsimony_timing(ps_population *core, double *schedule_ms, double *core_ms, double *gene_ms);
+/* The merge list of a linkage tree (host only, no device is touched; the reference has no such function; population.rs:787-837):
+ * Kruskal over the edges (lo[k], hi[k]) of ps_linkage_tree in their given order; merge k joins the clusters of edge k, left the
+ * one with the smaller smallest row (ps_upgma_tree's convention).  left, right: room for `edges` values.  An edge inside one
+ * cluster, a row >= pop_size or more than pop_size - 1 edges is PS_ERR_INVALID. */
+int ps_merges_from_tree(const uint32_t *lo, const uint32_t *hi, uint64_t edges, uint64_t pop_size, uint32_t *left, uint32_t *right,
+                        uint64_t *merges);
+/* The merge list of a comb (host only; the reference has no such function; population.rs:443): the positions r with coal[r] !=
+ * PS_GEN_BEYOND in (coal ascending, r ascending) order; merge k joins the two contiguous intervals of internal rows that meet
+ * between r and r + 1, left the left interval; leaves are order[r]; height[k] (may be NULL) = coal[r].  Equal times, which
+ * ps_genealogy_newick prints as one multifurcation, are resolved left to right in comb order.  left, right, height: room for
+ * pop_size - 1 values.  order must be a permutation of 0 .. pop_size - 1. */
+int ps_merges_from_genealogy(const uint32_t *order, const uint32_t *coal, uint64_t pop_size, uint32_t *left, uint32_t *right,
+                             uint32_t *height, uint64_t *merges);
+/* The schedule the kernel runs by (host only; the reference has no such function; population.rs:443): level_of[k] of merge k =
+ * 1 + the larger of its children's levels, leaves at 0; *levels = the largest.  The tree rules above apply. */
+int ps_parsimony_schedule(const uint32_t *left, const uint32_t *right, uint64_t merges, uint64_t pop_size, uint32_t *level_of,
+                          uint32_t *levels);
+/* The plain sequential restatement on the host (no device is touched, as ps_diversity_from_counts; the reference has no such
+ * function; population.rs:443, :840-863), through the same per-node functions as the kernel.  rows: individual-major pop_size x
+ * cols bytes, row k = leaf k.  genes == 0: the bytes are core cells and site_changes, site_hist, branch_changes are filled (the
+ * gene outputs must be NULL); genes == 1: a byte is the presence (non-zero) of a gene and gene_changes .. branch_losses are
+ * filled (the core outputs must be NULL).  Any output may be NULL. */
+int ps_parsimony_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, int genes, const uint32_t *left, const uint32_t *right,
+                           uint64_t merges, ps_parsimony_t *out, uint32_t *site_changes, uint64_t *site_hist, uint64_t *branch_changes,
+                           uint32_t *gene_changes, uint32_t *gene_gains, uint32_t *gene_losses, uint64_t *branch_gains,
+                           uint64_t *branch_losses);
+
 #ifdef __cplusplus
 }
 #endif

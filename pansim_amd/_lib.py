@@ -191,6 +191,17 @@ class Diff(C.Structure):
                [(name, C.c_double) for name in ("pi_within", "pi_between", "fst")]
 
 
+PS_PARS_BINS, PS_PARS_MAX_POP = 64, 16384
+
+
+class Parsimony(C.Structure):
+    """ps_parsimony_t: the summary of ps_tree_parsimony / ps_parsimony_from_rows (docs/TREE_PARSIMONY.md)"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "sites", "genes", "merges", "trees", "covered_leaves", "spanning",
+                                                 "total_changes", "changed_sites", "max_changes", "gene_total_changes",
+                                                 "gene_total_gains", "gene_total_losses", "min_changes", "excess_changes",
+                                                 "homoplasic_sites")] + [("ci", C.c_double)]
+
+
 # every symbol include/pansim_hip.h declares (tests/test_host_logic.py::test_library_exports_every_declared_symbol checks the header against this)
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -343,6 +354,14 @@ SIGNATURES = {
     "ps_multi_group_differentiation": (_int, [_vp, _vp, C.POINTER(DiffParams), C.POINTER(Diff)] + [_vp] * 12),
     "ps_differentiation_from_counts": (_int, [_vp, _u64, _u32, _vp, C.POINTER(Diff), _vp, _vp, _vp, _vp]),
     "ps_group_differentiation_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_tree_parsimony": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(Parsimony)] + [_vp] * 8),
+    "ps_sim_tree_parsimony": (_int, [_vp, _vp, _vp, _u64, C.POINTER(Parsimony)] + [_vp] * 8),
+    "ps_multi_tree_parsimony": (_int, [_vp, _vp, _vp, _u64, C.POINTER(Parsimony)] + [_vp] * 8),
+    "ps_tree_parsimony_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_merges_from_tree": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, C.POINTER(_u64)]),
+    "ps_merges_from_genealogy": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)]),
+    "ps_parsimony_schedule": (_int, [_vp, _vp, _u64, _u64, _vp, C.POINTER(_u32)]),
+    "ps_parsimony_from_rows": (_int, [_vp, _u64, _u64, _int, _vp, _vp, _u64, C.POINTER(Parsimony)] + [_vp] * 8),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

@@ -75,6 +75,7 @@ static const Flag EXT_FLAGS[] = {
     { "ld_max_loci", "Largest number of loci of --print_ld; more candidates are thinned evenly. Must be 1 <= X <= 65536.", "4096", true },
     { "ld_min_minor", "Smallest minor count of a locus of --print_ld. Must be a whole number >= 1.", "1", true },
     { "ld_bins", "Bins of --print_ld as <r2>,<lag>: both at least 1, lag at most 32, their product at most 16384.", "64,1", true },
+    { "print_parsimony", "Put the two matrices of the final population on a tree by Fitch parsimony -- <print_parsimony> is upgma (the tree of --upgma_metric), tree (the single-linkage tree of --tree_metric) or genealogy (the recorded one: needs --print_genealogy; equal times are resolved left to right) -- and write the changes of every core site to <outpref>_parsimony_sites.tsv, per accessory gene its changes, gains and losses to <outpref>_parsimony_genes.tsv, per node its parent (-1 for a root), the core sites that change and the genes gained and lost on the branch above it to <outpref>_parsimony_branches.tsv (node, parent, site_changes, gene_gains, gene_losses), the tree with branch lengths in changes per site to <outpref>_parsimony.nwk (Newick, one line per root) and the summary with the homoplasic sites and the consistency index to <outpref>_parsimony_summary.tsv (docs/TREE_PARSIMONY.md), beside the usual outputs. Needs 2 <= pop_size <= 16384.", "", true },
     { "load_state", "Start from a state file instead of a clonal population: --n_gen stays the TOTAL, generations [saved, n_gen) are run. pop_size, core_size, pan_genes and core_genes must be the file's; every other flag is this command line's (the same flags continue the saved run bit for bit, other flags branch off it). With --print_dist the earlier rows of _per_gen.tsv come from the file, which must have been saved with --print_dist. One shard only (--gpus 1).", "", true },
 };
 
@@ -456,6 +457,18 @@ int main(int argc, char **argv)
         }
         if (ld_prm.max_loci > PS_LD_MAX_LOCI) die(101, "pansim: --ld_max_loci must be 1 <= X <= 65536, not " + val["ld_max_loci"]);
     }
+    // --print_parsimony: the tree it names, before any device work
+    const std::string pars_source = val["print_parsimony"];
+    if (!pars_source.empty()) {
+        if (pars_source != "upgma" && pars_source != "tree" && pars_source != "genealogy")
+            die(101, "pansim: --print_parsimony must be upgma, tree or genealogy, not \"" + pars_source + "\"");
+        if (pars_source == "genealogy" && val["print_genealogy"].empty())
+            die(101, "pansim: --print_parsimony genealogy needs --print_genealogy: nothing is recorded without it");
+        if (p.pop_size < 2 || p.pop_size > PS_PARS_MAX_POP)
+            die(101, "pansim: --print_parsimony needs 2 <= pop_size <= 16384, not --pop_size " + std::to_string(p.pop_size));
+        if (pars_source == "upgma" && upgma_prm.metric == PS_TREE_ACC && p.core_genes < 1)
+            die(101, "pansim: --upgma_metric acc needs core_genes >= 1, not --core_genes " + std::to_string(p.core_genes));
+    }
     uint32_t record_capacity = 0;
     if (!val["print_genealogy"].empty()) {
         const std::string &t = val["print_genealogy"];
@@ -784,6 +797,84 @@ int main(int argc, char **argv)
                     if (per_time[3 * t])
                         fprintf(f, "time\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)t, (unsigned long long)per_time[3 * t],
                                 (unsigned long long)per_time[3 * t + 1], (unsigned long long)per_time[3 * t + 2]);
+                fclose(f);
+            }
+        }
+        if (!pars_source.empty()) {                                    // (no counterpart in the reference: docs/TREE_PARSIMONY.md)
+            const size_t n = (size_t)p.pop_size, L = (size_t)p.core_size, G = (size_t)(p.pan_genes - p.core_genes);
+            std::vector<uint32_t> left(n), right(n);
+            uint64_t M = 0;
+            if (pars_source == "upgma") {
+                std::vector<uint32_t> size(n);
+                std::vector<uint64_t> num(n), den(n);
+                ps_upgma_t t;
+                CK(multi ? ps_multi_upgma_tree(multi, &upgma_prm, &t, left.data(), right.data(), size.data(), num.data(), den.data())
+                         : ps_sim_upgma_tree(sim, &upgma_prm, &t, left.data(), right.data(), size.data(), num.data(), den.data()));
+                M = t.merges;
+            } else if (pars_source == "tree") {
+                std::vector<uint32_t> lo(n), hi(n);
+                std::vector<uint64_t> num(n), den(n);
+                ps_tree_t t;
+                CK(multi ? ps_multi_linkage_tree(multi, &tree_prm, &t, lo.data(), hi.data(), num.data(), den.data())
+                         : ps_sim_linkage_tree(sim, &tree_prm, &t, lo.data(), hi.data(), num.data(), den.data()));
+                CK(ps_merges_from_tree(lo.data(), hi.data(), t.edges, n, left.data(), right.data(), &M));
+            } else {
+                std::vector<uint32_t> order(n), coal(n);
+                ps_genealogy_t g;
+                CK(multi ? ps_multi_genealogy(multi, &g, order.data(), coal.data()) : ps_sim_genealogy(sim, &g, order.data(), coal.data()));
+                CK(ps_merges_from_genealogy(order.data(), coal.data(), n, left.data(), right.data(), nullptr, &M));
+            }
+            if (M == 0) fprintf(stderr, "pansim: the %s of --print_parsimony has no merge: the _parsimony files are not written\n", pars_source.c_str());
+            else {
+                const size_t nodes = n + (size_t)M;
+                std::vector<uint32_t> sites(std::max<size_t>(L, 1)), gch(std::max<size_t>(G, 1)), ggn(std::max<size_t>(G, 1)), gls(std::max<size_t>(G, 1));
+                std::vector<uint64_t> hist(PS_PARS_BINS), bch(nodes), bgn(nodes), bls(nodes);
+                ps_parsimony_t t;
+                CK(multi ? ps_multi_tree_parsimony(multi, left.data(), right.data(), M, &t, sites.data(), hist.data(), bch.data(), gch.data(), ggn.data(),
+                                                   gls.data(), bgn.data(), bls.data())
+                         : ps_sim_tree_parsimony(sim, left.data(), right.data(), M, &t, sites.data(), hist.data(), bch.data(), gch.data(), ggn.data(),
+                                                 gls.data(), bgn.data(), bls.data()));
+                FILE *f = open_out(outpref, "_parsimony_sites.tsv");
+                for (uint64_t s = 0; s < t.sites; s++) fprintf(f, "%u\n", sites[s]);
+                fclose(f);
+                f = open_out(outpref, "_parsimony_genes.tsv");
+                for (uint64_t y = 0; y < t.genes; y++) fprintf(f, "%u\t%u\t%u\n", gch[y], ggn[y], gls[y]);
+                fclose(f);
+                std::vector<long long> parent(nodes, -1);
+                for (uint64_t k = 0; k < M; k++) parent[left[k]] = parent[right[k]] = (long long)(n + k);
+                f = open_out(outpref, "_parsimony_branches.tsv");
+                for (size_t x = 0; x < nodes; x++)
+                    fprintf(f, "%zu\t%lld\t%llu\t%llu\t%llu\n", x, parent[x], (unsigned long long)bch[x], (unsigned long long)bgn[x], (unsigned long long)bls[x]);
+                fclose(f);
+                // Newick, one line per root: an explicit stack (a caterpillar is pop_size deep); text entries are negative
+                f = open_out(outpref, "_parsimony.nwk");
+                auto tail = [&](size_t x) { return parent[x] >= 0 ? ":" + fmt(t.sites ? (double)bch[x] / (double)t.sites : 0.0) : std::string(); };
+                for (size_t root = n; root < nodes; root++) {
+                    if (parent[root] >= 0) continue;
+                    std::vector<long long> stack{ (long long)root };
+                    while (!stack.empty()) {
+                        const long long e = stack.back();
+                        stack.pop_back();
+                        if (e == -1) fputs(",", f);
+                        else if (e < -1) fprintf(f, ")%s", tail((size_t)(-e - 2)).c_str());
+                        else if ((size_t)e < n) fprintf(f, "%lld%s", e, tail((size_t)e).c_str());
+                        else {
+                            fputs("(", f);
+                            stack.insert(stack.end(), { -e - 2, (long long)right[(size_t)e - n], -1, (long long)left[(size_t)e - n] });
+                        }
+                    }
+                    fputs(";\n", f);
+                }
+                fclose(f);
+                f = open_out(outpref, "_parsimony_summary.tsv");
+                const std::pair<const char *, uint64_t> fields[] = {
+                    { "pop_size", t.pop_size }, { "sites", t.sites }, { "genes", t.genes }, { "merges", t.merges }, { "trees", t.trees },
+                    { "covered_leaves", t.covered_leaves }, { "spanning", t.spanning }, { "total_changes", t.total_changes },
+                    { "changed_sites", t.changed_sites }, { "max_changes", t.max_changes }, { "gene_total_changes", t.gene_total_changes },
+                    { "gene_total_gains", t.gene_total_gains }, { "gene_total_losses", t.gene_total_losses }, { "min_changes", t.min_changes },
+                    { "excess_changes", t.excess_changes }, { "homoplasic_sites", t.homoplasic_sites } };
+                for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+                fprintf(f, "ci\t%s\ntree\t%s\n", fmt(t.ci).c_str(), pars_source.c_str());
                 fclose(f);
             }
         }

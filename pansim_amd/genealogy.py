@@ -73,6 +73,12 @@ class GenealogyResult:
     def newick(self):
         return genealogy_newick(self.order, self.coal)
 
+    def merges(self):
+        """(left, right, height): the comb as a merge list in scipy's numbering, equal times resolved left to right
+        (ps_merges_from_genealogy); `tree_parsimony(*merges()[:2])`"""
+        from .parsimony import merges_from_genealogy
+        return merges_from_genealogy(self.order, self.coal)
+
 
 def _genealogy_call(fn, pop_size, handle):
     g = Genealogy()

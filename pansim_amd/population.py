@@ -340,6 +340,12 @@ class LinkageTree(_Summary):
         """the number of clusters of `cut(num, den)`: pop_size less the edges kept"""
         return self.pop_size - self._kept(num, den)
 
+    def merges(self):
+        """(left, right): the tree as a merge list in scipy's numbering, edge by edge (ps_merges_from_tree) -- what
+        `tree_parsimony` takes"""
+        from .parsimony import merges_from_tree
+        return merges_from_tree(self.lo, self.hi, self.pop_size)
+
     def as_dict(self):
         out = self._head()
         out.update(lo=self.lo, hi=self.hi, num=self.num, den=self.den, distance=self.distance)
@@ -368,6 +374,18 @@ def tree_from_counts(r1, r2, core_h, acc_inter, acc_union, pop_size, core_sites,
                       int(core_sites), int(core_genes))
 
 
+class _MergeCount(int):
+    """`UpgmaTree.merges`: the number of merges, as before, which called gives the merge list (left, right) as
+    `tree_parsimony` takes it -- `merges()` like the other two trees without renaming the summary field"""
+    def __new__(cls, value, left, right):
+        self = super().__new__(cls, value)
+        self._lists = (left, right)
+        return self
+
+    def __call__(self):
+        return self._lists
+
+
 class UpgmaTree(_Summary):
     """The result of `upgma_tree` (ps_upgma_t + the merges; docs/UPGMA_TREE.md): the summary fields as integer attributes and the
     pop_size - 1 merges in the order the sequential algorithm performs them, scipy's linkage matrix with exact fractions --
@@ -379,6 +397,7 @@ class UpgmaTree(_Summary):
         self._take(t)
         n = self.merges
         self.left, self.right, self.size, self.num, self.den = left[:n], right[:n], size[:n], num[:n], den[:n]
+        self.merges = _MergeCount(n, self.left, self.right)
         self.distance = self.num.astype(np.float64) / self.den.astype(np.float64)
 
     def _kept(self, num, den):
@@ -924,6 +943,22 @@ class Population:
     def group_differentiation_timing(self):
         """device ms of (the membership tables, the core pass, the gene pass) of the last group_differentiation() on this core handle"""
         return _timing(self._lib.ps_group_differentiation_timing, 3, self._h)
+
+    def tree_parsimony(self, left, right, acc=None, per_site=False, branches=False, genes=False):
+        """Fitch parsimony of every site of this core population and, with `genes`, every gene of the accessory population
+        `acc` of the same individuals on the tree of the merge list (left, right) -- `UpgmaTree.merges()`,
+        `LinkageTree.merges()`, `GenealogyResult.merges()[:2]`; leaves are rows of the reference's row order
+        (ps_tree_parsimony; docs/TREE_PARSIMONY.md) -> a TreeParsimony.  `per_site`: site_changes as well; `branches`:
+        branch_changes (and with `genes` branch_gains, branch_losses) as well; `genes`: gene_changes, gene_gains, gene_losses."""
+        from .parsimony import _pars_call
+        if genes and acc is None:
+            raise ValueError("genes=True needs the accessory population")
+        return _pars_call(self._lib.ps_tree_parsimony, left, right, self.size, self.ncols, acc.ncols if genes else 0, per_site, branches,
+                          genes, self._h, acc._h if acc is not None else None)
+
+    def tree_parsimony_timing(self):
+        """device ms of (the schedule's upload, the core pass, the gene pass) of the last tree_parsimony() on this core handle"""
+        return _timing(self._lib.ps_tree_parsimony_timing, 3, self._h)
 
     def locus_ld(self, r2_bins=64, lag_bins=1, min_minor=1, max_loci=4096, loci=None):
         """linkage disequilibrium between the columns of this handle -- core sites or accessory genes by its kind

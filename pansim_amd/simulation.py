@@ -254,6 +254,17 @@ class Simulation:
         return _diff_call(self._lib.ps_sim_group_differentiation, labels, self.params.pop_size, self.core_genome.ncols,
                           self.pan_genome.ncols, max_groups, min_size, per_site, counts, True, self._h)
 
+    def tree_parsimony(self, left, right, per_site=False, branches=False, genes=False):
+        """Population.tree_parsimony() of the run's two matrices (ps_sim_tree_parsimony), leaves in the reference's row order:
+        behind every queued generation, and without a change of state"""
+        from .parsimony import _pars_call
+        return _pars_call(self._lib.ps_sim_tree_parsimony, left, right, self.params.pop_size, self.core_genome.ncols,
+                          self.pan_genome.ncols if genes else 0, per_site, branches, genes, self._h)
+
+    def tree_parsimony_timing(self):
+        """device ms of (the schedule's upload, the core pass, the gene pass) of the last tree_parsimony()"""
+        return self.core_genome.tree_parsimony_timing()
+
     def linkage_tree(self, metric="core"):
         """Population.linkage_tree() of the run's two matrices (ps_sim_linkage_tree), edges in the reference's row order"""
         from .population import _tree_call, _tree_params
@@ -408,6 +419,17 @@ class MultiSimulation:
         from .population import _diff_call
         return _diff_call(self._lib.ps_multi_group_differentiation, labels, self.params.pop_size, self.params.core_size,
                           self.pan_genome.ncols, max_groups, min_size, per_site, counts, True, self._h)
+
+    def tree_parsimony(self, left, right, per_site=False, branches=False, genes=False):
+        """Population.tree_parsimony() over ALL core sites: the shards' arrays and integers added, their site_changes
+        concatenated, the genes from shard 0's accessory replica (ps_multi_tree_parsimony)"""
+        from .parsimony import _pars_call
+        return _pars_call(self._lib.ps_multi_tree_parsimony, left, right, self.params.pop_size, self.params.core_size,
+                          self.pan_genome.ncols if genes else 0, per_site, branches, genes, self._h)
+
+    def tree_parsimony_timing(self):
+        """device ms of (the schedule's upload, the core pass, the gene pass) of the last tree_parsimony() (shard 0's handle)"""
+        return self.shards[0].tree_parsimony_timing()
 
     def linkage_tree(self, metric="core"):
         """Population.linkage_tree() over ALL core sites: the shards' band counts added and kept on shard 0, the rounds
