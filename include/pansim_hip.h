@@ -1070,6 +1070,76 @@ int ps_parsimony_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols
                            uint32_t *gene_changes, uint32_t *gene_gains, uint32_t *gene_losses, uint64_t *branch_gains,
                            uint64_t *branch_losses);
 
+/* Comparison of two trees over the same leaves (docs/TREE_COMPARISON.md): how well one tree -- an inferred one -- recovers another
+ * -- the recorded genealogy: the cophenetic agreement over ALL pairs of leaves, the rooted triplets both resolve alike, the clades
+ * they share.  The reference has no such function (its trees are implicit in the parent draws of population.rs:443).
+ * Tree: a merge list as ps_tree_parsimony takes it (the rules above apply; forests are accepted, leaves are rows of the
+ * reference's row order), with a value per merge: 1 <= val[k] <= 262143 (2^18 - 1) and val[parent] >= val[child], else
+ * PS_ERR_INVALID; val == NULL means val[k] = k + 1, the merge rank.  Equal values on a parent and its child are one
+ * multifurcating node.
+ * v_T(i, j) = the value of the lowest common ancestor of leaves i, j in T; i, j in different trees of a forest are "not joined".
+ * The clade C_T(i, j) of a joined pair = the leaves below the highest ancestor of that merge with the same value (its tie-top).
+ *   joined_*            the pairs i < j by the trees that join them
+ *   sum_a .. sum_ab     over the pairs joined in both: sums of v_A, v_B, v_A^2, v_B^2, v_A v_B
+ *   joint[(bins_a + 1)(bins_b + 1)]   pairs by (bin of v_A, bin of v_B), bin = ps_clock_time_bin's min(B - 1, floor((v - 1) B / S)),
+ *                       S the span (0: the tree's largest value); row bins_a / column bins_b: not joined in A / in B
+ *   cophenetic_r        (n sum_ab - sum_a sum_b) / sqrt((n sum_aa - sum_a^2)(n sum_bb - sum_b^2)), n = joined_both, the integer
+ *                       terms exact in 128 bits; 0.0 when n = 0 or a variance term is 0
+ *   triplets != 0:      {i, j, k} is resolved as ij|k in T iff i, j are joined and v(i, j) < v(i, k) (another tree of the forest:
+ *                       infinitely far).  resolved_a = sum over the pairs joined in A of N - |C_A(i, j)|, resolved_b alike;
+ *                       shared_triplets = sum over the pairs joined in both of N - |C_A u C_B|: every triple both trees resolve
+ *                       alike, once; triples = C(N, 3); triplet_recall = shared / resolved_a, triplet_precision = shared /
+ *                       resolved_b (0.0 on a zero denominator).  triplets == 0: the fields are 0.
+ *   clades_a, clades_b  the tie-top merges of each tree; shared_clades those with equal leaf sets; rf_distance = clades_a +
+ *                       clades_b - 2 shared; clade_recall = shared / clades_a, clade_precision = shared / clades_b
+ *   in_b[merges_a]      (may be NULL) 1 iff merge k of A is a tie-top whose leaf set is a clade of B; in_a[merges_b] the same swapped
+ * Every integer is exact and independent of the launch geometry; the doubles are formed once from the integers.
+ * PS_ERR_INVALID: a null required argument, a bad tree or value, bins < 1 or > 1024, (bins_a + 1)(bins_b + 1) > 16384, a span >= 2^32. */
+typedef struct {
+    uint32_t bins_a, bins_b;           /* value bins per tree */
+    uint64_t span_a, span_b;           /* 0: the tree's largest value */
+    int32_t triplets;                  /* != 0: the triplet sums as well (a rank table of (N + 1)^2 u16 on the device) */
+} ps_tree_compare_params;
+typedef struct {
+    uint64_t pop_size, merges_a, merges_b, pairs;      /* N, M_A, M_B, N (N - 1) / 2 */
+    uint64_t joined_both, joined_a_only, joined_b_only, joined_neither;
+    uint64_t sum_a, sum_b, sum_aa, sum_bb, sum_ab;
+    uint64_t triples, resolved_a, resolved_b, shared_triplets;
+    uint64_t clades_a, clades_b, shared_clades, rf_distance;
+    uint64_t bins_a, bins_b, span_a, span_b;           /* the spans as used */
+    double cophenetic_r, triplet_recall, triplet_precision, clade_recall, clade_precision;
+} ps_tree_compare_t;
+/* Two trees over the pop_size leaves of `any` (the reference has no such function; population.rs:443): any handle -- it supplies
+ * the device, the stream and the scratch, and only its pop_size is read.  One kernel over all pairs behind two sparse tables
+ * (and the rank table).  Ordered behind the handle's queued work; changes no state.  PS_ERR_OOM names the bytes it could not
+ * allocate.  PS_ERR_NO_DEVICE before anything else when no GPU is visible. */
+int ps_tree_compare(ps_population *any, const uint32_t *left_a, const uint32_t *right_a, const uint32_t *val_a, uint64_t merges_a,
+                    const uint32_t *left_b, const uint32_t *right_b, const uint32_t *val_b, uint64_t merges_b,
+                    const ps_tree_compare_params *prm, ps_tree_compare_t *out, uint64_t *joint, uint8_t *in_b, uint8_t *in_a);
+/* The same on the core handle of a simulation (the reference has no such function; population.rs:443) */
+int ps_sim_tree_compare(ps_sim *s, const uint32_t *left_a, const uint32_t *right_a, const uint32_t *val_a, uint64_t merges_a,
+                        const uint32_t *left_b, const uint32_t *right_b, const uint32_t *val_b, uint64_t merges_b,
+                        const ps_tree_compare_params *prm, ps_tree_compare_t *out, uint64_t *joint, uint8_t *in_b, uint8_t *in_a);
+/* The same on shard 0's core handle of a sharded run: trees are global (the reference has no such function; population.rs:443) */
+int ps_multi_tree_compare(ps_multi *m, const uint32_t *left_a, const uint32_t *right_a, const uint32_t *val_a, uint64_t merges_a,
+                          const uint32_t *left_b, const uint32_t *right_b, const uint32_t *val_b, uint64_t merges_b,
+                          const ps_tree_compare_params *prm, ps_tree_compare_t *out, uint64_t *joint, uint8_t *in_b, uint8_t *in_a);
+/* The plain sequential restatement over all pairs on the host (no device is touched, as ps_parsimony_from_rows; the reference
+ * has no such function; population.rs:443), through the same checks, leaf orders, clades and finish as the device path.  With
+ * triplets it holds (pop_size + 1)^2 u16 on the host. */
+int ps_tree_compare_from_merges(uint64_t pop_size, const uint32_t *left_a, const uint32_t *right_a, const uint32_t *val_a,
+                                uint64_t merges_a, const uint32_t *left_b, const uint32_t *right_b, const uint32_t *val_b,
+                                uint64_t merges_b, const ps_tree_compare_params *prm, ps_tree_compare_t *out, uint64_t *joint,
+                                uint8_t *in_b, uint8_t *in_a);
+/* Values for ps_tree_compare from the heights of ps_upgma_tree or the sorted edges of ps_linkage_tree (host only; the reference
+ * has no such function; population.rs:787-837): the heights num[k] / den[k] must not decrease in k under the linkage tree's
+ * comparison (num1 den2 against num2 den1, here in 128 bits; den == 0 is undefined: above every defined height and equal to
+ * itself), else PS_ERR_INVALID.  levels[0] = 1, plus 1 at every strict increase (dense ranks); *distinct (may be NULL) = the last. */
+int ps_levels_from_heights(const uint64_t *num, const uint64_t *den, uint64_t merges, uint32_t *levels, uint64_t *distinct);
+/* device ms of the last ps_tree_compare on this handle (HIP events; the reference has no such function; population.rs:443): the
+ * uploads and the tables, the pass over all pairs.  PS_ERR_STATE before any call. */
+int ps_tree_compare_timing(ps_population *any, double *tables_ms, double *pairs_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,6 +202,23 @@ class Parsimony(C.Structure):
                                                  "homoplasic_sites")] + [("ci", C.c_double)]
 
 
+class TreeCompareParams(C.Structure):
+    """ps_tree_compare_params"""
+    _fields_ = [("bins_a", C.c_uint32), ("bins_b", C.c_uint32), ("span_a", C.c_uint64), ("span_b", C.c_uint64), ("triplets", C.c_int32)]
+
+
+class TreeCompare(C.Structure):
+    """ps_tree_compare_t: the summary of ps_tree_compare / ps_tree_compare_from_merges (docs/TREE_COMPARISON.md)"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "merges_a", "merges_b", "pairs", "joined_both", "joined_a_only",
+                                                 "joined_b_only", "joined_neither", "sum_a", "sum_b", "sum_aa", "sum_bb", "sum_ab",
+                                                 "triples", "resolved_a", "resolved_b", "shared_triplets", "clades_a", "clades_b",
+                                                 "shared_clades", "rf_distance", "bins_a", "bins_b", "span_a", "span_b")] + \
+               [(name, C.c_double) for name in ("cophenetic_r", "triplet_recall", "triplet_precision", "clade_recall", "clade_precision")]
+
+
+# the two trees, the parameters, the summary, joint, in_b, in_a: the tail of every ps_*tree_compare* entry
+_TCMP = [C.c_void_p] * 3 + [C.c_uint64] + [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(TreeCompareParams), C.POINTER(TreeCompare)] + [C.c_void_p] * 3
+
 # every symbol include/pansim_hip.h declares (tests/test_host_logic.py::test_library_exports_every_declared_symbol checks the header against this)
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -362,6 +379,12 @@ SIGNATURES = {
     "ps_merges_from_genealogy": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)]),
     "ps_parsimony_schedule": (_int, [_vp, _vp, _u64, _u64, _vp, C.POINTER(_u32)]),
     "ps_parsimony_from_rows": (_int, [_vp, _u64, _u64, _int, _vp, _vp, _u64, C.POINTER(Parsimony)] + [_vp] * 8),
+    "ps_tree_compare": (_int, [_vp] + _TCMP),
+    "ps_sim_tree_compare": (_int, [_vp] + _TCMP),
+    "ps_multi_tree_compare": (_int, [_vp] + _TCMP),
+    "ps_tree_compare_from_merges": (_int, [_u64] + _TCMP),
+    "ps_levels_from_heights": (_int, [_vp, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "ps_tree_compare_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

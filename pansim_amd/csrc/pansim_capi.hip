@@ -188,7 +188,7 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
 // ms of the last call's timer groups (`timed`: a call has completed)
-enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_COUNT };
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_COUNT };
 struct readout_slot {
     void *d = nullptr;
     uint64_t cap = 0;       // (bytes)
@@ -338,6 +338,8 @@ struct ps_population {
     //                   core, genes
     //   PS_RO_PARS      tree parsimony (tree_parsimony.h): the words, the schedule, the level offsets, the per-column words, the branch
     //                   counters (accessory handle: the same, then one chunk of expanded gene bytes); ms: schedule, core, genes
+    //   PS_RO_TCMP      tree comparison (tree_compare.h), on whichever handle was asked: the words and the joint bins, the two sparse
+    //                   tables, pb, the two info arrays, with triplets the u16 rank table; ms: tables, pairs
     readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
@@ -4985,6 +4987,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // parsimony of the matrices on a tree (ps_tree_parsimony, ps_merges_from_*, ps_parsimony_schedule, ps_parsimony_from_rows, ps_sim_* and ps_multi_*)
 #include "tree_parsimony.h"
+
+// comparison of two trees over all pairs of leaves (ps_tree_compare, ps_tree_compare_from_merges, ps_levels_from_heights, ps_sim_* and ps_multi_*)
+#include "tree_compare.h"
 
 // the native RCCL provider of ps_exchange_fn (ps_rccl_*, ps_exchange_rccl)
 #include "exchange_rccl.h"

@@ -76,6 +76,8 @@ static const Flag EXT_FLAGS[] = {
     { "ld_min_minor", "Smallest minor count of a locus of --print_ld. Must be a whole number >= 1.", "1", true },
     { "ld_bins", "Bins of --print_ld as <r2>,<lag>: both at least 1, lag at most 32, their product at most 16384.", "64,1", true },
     { "print_parsimony", "Put the two matrices of the final population on a tree by Fitch parsimony -- <print_parsimony> is upgma (the tree of --upgma_metric), tree (the single-linkage tree of --tree_metric) or genealogy (the recorded one: needs --print_genealogy; equal times are resolved left to right) -- and write the changes of every core site to <outpref>_parsimony_sites.tsv, per accessory gene its changes, gains and losses to <outpref>_parsimony_genes.tsv, per node its parent (-1 for a root), the core sites that change and the genes gained and lost on the branch above it to <outpref>_parsimony_branches.tsv (node, parent, site_changes, gene_gains, gene_losses), the tree with branch lengths in changes per site to <outpref>_parsimony.nwk (Newick, one line per root) and the summary with the homoplasic sites and the consistency index to <outpref>_parsimony_summary.tsv (docs/TREE_PARSIMONY.md), beside the usual outputs. Needs 2 <= pop_size <= 16384.", "", true },
+    { "print_tree_compare", "Compare two trees of the final population over ALL pairs of individuals as <a>,<b> -- each of upgma (the tree of --upgma_metric), tree (the single-linkage tree of --tree_metric) or genealogy (the recorded one: needs --print_genealogy), a read as the truth -- and write the pairs binned by the heights at which the two trees join them to <outpref>_tree_compare.tsv (bin_a, bin_b, count per non-empty bin; bin <Ba> / <Bb> holds the pairs a / b does not join), every clade of both trees to <outpref>_tree_compare_clades.tsv (tree, node, size, val, shared: 1 when the other tree has the same clade) and the summary with the cophenetic correlation, the rooted triplets both trees resolve alike and the shared clades to <outpref>_tree_compare_summary.tsv (docs/TREE_COMPARISON.md), beside the usual outputs. Heights are the dense ranks of the merge distances for upgma and tree, the coalescence times for genealogy. Needs 2 <= pop_size <= 16384.", "", true },
+    { "tree_compare_bins", "Bins of --print_tree_compare as <Ba>,<Bb>: both at least 1 and at most 1024, (Ba + 1) x (Bb + 1) at most 16384.", "32,32", true },
     { "load_state", "Start from a state file instead of a clonal population: --n_gen stays the TOTAL, generations [saved, n_gen) are run. pop_size, core_size, pan_genes and core_genes must be the file's; every other flag is this command line's (the same flags continue the saved run bit for bit, other flags branch off it). With --print_dist the earlier rows of _per_gen.tsv come from the file, which must have been saved with --print_dist. One shard only (--gpus 1).", "", true },
 };
 
@@ -469,6 +471,35 @@ int main(int argc, char **argv)
         if (pars_source == "upgma" && upgma_prm.metric == PS_TREE_ACC && p.core_genes < 1)
             die(101, "pansim: --upgma_metric acc needs core_genes >= 1, not --core_genes " + std::to_string(p.core_genes));
     }
+    // --print_tree_compare: the two trees it names and the bins, before any device work
+    std::string tcmp_source[2];
+    ps_tree_compare_params tcmp_prm = { 32, 32, 0, 0, 1 };
+    if (!val["print_tree_compare"].empty()) {
+        const std::string &t = val["print_tree_compare"];
+        const size_t comma = t.find(',');
+        tcmp_source[0] = t.substr(0, comma);
+        tcmp_source[1] = comma == std::string::npos ? "" : t.substr(comma + 1);
+        for (const std::string &x : tcmp_source)
+            if (x != "upgma" && x != "tree" && x != "genealogy")
+                die(101, "pansim: --print_tree_compare must be <a>,<b>, each of upgma, tree or genealogy, not \"" + t + "\"");
+        if (tcmp_source[0] == tcmp_source[1]) die(101, "pansim: --print_tree_compare needs two different trees, not \"" + t + "\"");
+        if ((tcmp_source[0] == "genealogy" || tcmp_source[1] == "genealogy") && val["print_genealogy"].empty())
+            die(101, "pansim: --print_tree_compare genealogy needs --print_genealogy: nothing is recorded without it");
+        if (p.pop_size < 2 || p.pop_size > PS_PARS_MAX_POP)
+            die(101, "pansim: --print_tree_compare needs 2 <= pop_size <= 16384, not --pop_size " + std::to_string(p.pop_size));
+        if ((tcmp_source[0] == "upgma" || tcmp_source[1] == "upgma") && upgma_prm.metric == PS_TREE_ACC && p.core_genes < 1)
+            die(101, "pansim: --upgma_metric acc needs core_genes >= 1, not --core_genes " + std::to_string(p.core_genes));
+        const std::string &b = val["tree_compare_bins"];
+        unsigned long long ba = 0, bb = 0;
+        int used = 0;
+        if (sscanf(b.c_str(), "%llu,%llu%n", &ba, &bb, &used) != 2 || (size_t)used != b.size() || b.find_first_of("+- ") != std::string::npos)
+            die(101, "pansim: --tree_compare_bins must be <Ba>,<Bb> (two whole numbers), not \"" + b + "\"");
+        if (ba < 1 || bb < 1) die(101, "pansim: --tree_compare_bins must be at least 1 on both axes");
+        if (ba > 1024 || bb > 1024 || (ba + 1) * (bb + 1) > 16384)
+            die(101, "pansim: --tree_compare_bins " + b + ": both must be at most 1024 and (Ba + 1) x (Bb + 1) at most 16384");
+        tcmp_prm.bins_a = (uint32_t)ba;
+        tcmp_prm.bins_b = (uint32_t)bb;
+    }
     uint32_t record_capacity = 0;
     if (!val["print_genealogy"].empty()) {
         const std::string &t = val["print_genealogy"];
@@ -478,6 +509,9 @@ int main(int argc, char **argv)
             die(101, "pansim: --print_genealogy must be a whole number, not \"" + t + "\"");
         if (c < 1 || c > 0xffffffffull) die(101, "pansim: --print_genealogy must be 1 <= X < 2^32 generations, not " + t);
         record_capacity = (uint32_t)c;
+        // (a coalescence time is a value of ps_tree_compare: at most 2^18 - 1)
+        if ((tcmp_source[0] == "genealogy" || tcmp_source[1] == "genealogy") && c > 262143)
+            die(101, "pansim: --print_tree_compare genealogy needs --print_genealogy <= 262143 generations, not " + t);
     }
     const uint64_t G = d.pan_size, P = p.max_distances;
     std::vector<double> avg_core(p.n_gen), avg_acc(p.n_gen), std_core(p.n_gen), std_acc(p.n_gen);
@@ -800,30 +834,39 @@ int main(int argc, char **argv)
                 fclose(f);
             }
         }
-        if (!pars_source.empty()) {                                    // (no counterpart in the reference: docs/TREE_PARSIMONY.md)
-            const size_t n = (size_t)p.pop_size, L = (size_t)p.core_size, G = (size_t)(p.pan_genes - p.core_genes);
-            std::vector<uint32_t> left(n), right(n);
-            uint64_t M = 0;
-            if (pars_source == "upgma") {
+        // one of the three trees as a merge list (left, right: room for pop_size values); vals (may be null): the values
+        // --print_tree_compare reads it with -- the dense ranks of its heights, the coalescence times of the genealogy
+        auto merge_list = [&](const std::string &source, uint32_t *left, uint32_t *right, uint32_t *vals, uint64_t *M) -> int {
+            const size_t n = (size_t)p.pop_size;
+            if (source == "upgma") {
                 std::vector<uint32_t> size(n);
                 std::vector<uint64_t> num(n), den(n);
                 ps_upgma_t t;
-                CK(multi ? ps_multi_upgma_tree(multi, &upgma_prm, &t, left.data(), right.data(), size.data(), num.data(), den.data())
-                         : ps_sim_upgma_tree(sim, &upgma_prm, &t, left.data(), right.data(), size.data(), num.data(), den.data()));
-                M = t.merges;
-            } else if (pars_source == "tree") {
+                CK(multi ? ps_multi_upgma_tree(multi, &upgma_prm, &t, left, right, size.data(), num.data(), den.data())
+                         : ps_sim_upgma_tree(sim, &upgma_prm, &t, left, right, size.data(), num.data(), den.data()));
+                *M = t.merges;
+                if (vals) CK(ps_levels_from_heights(num.data(), den.data(), *M, vals, nullptr));
+            } else if (source == "tree") {
                 std::vector<uint32_t> lo(n), hi(n);
                 std::vector<uint64_t> num(n), den(n);
                 ps_tree_t t;
                 CK(multi ? ps_multi_linkage_tree(multi, &tree_prm, &t, lo.data(), hi.data(), num.data(), den.data())
                          : ps_sim_linkage_tree(sim, &tree_prm, &t, lo.data(), hi.data(), num.data(), den.data()));
-                CK(ps_merges_from_tree(lo.data(), hi.data(), t.edges, n, left.data(), right.data(), &M));
+                CK(ps_merges_from_tree(lo.data(), hi.data(), t.edges, n, left, right, M));
+                if (vals) CK(ps_levels_from_heights(num.data(), den.data(), *M, vals, nullptr));
             } else {
                 std::vector<uint32_t> order(n), coal(n);
                 ps_genealogy_t g;
                 CK(multi ? ps_multi_genealogy(multi, &g, order.data(), coal.data()) : ps_sim_genealogy(sim, &g, order.data(), coal.data()));
-                CK(ps_merges_from_genealogy(order.data(), coal.data(), n, left.data(), right.data(), nullptr, &M));
+                CK(ps_merges_from_genealogy(order.data(), coal.data(), n, left, right, vals, M));
             }
+            return 0;
+        };
+        if (!pars_source.empty()) {                                    // (no counterpart in the reference: docs/TREE_PARSIMONY.md)
+            const size_t n = (size_t)p.pop_size, L = (size_t)p.core_size, G = (size_t)(p.pan_genes - p.core_genes);
+            std::vector<uint32_t> left(n), right(n);
+            uint64_t M = 0;
+            CK(merge_list(pars_source, left.data(), right.data(), nullptr, &M));
             if (M == 0) fprintf(stderr, "pansim: the %s of --print_parsimony has no merge: the _parsimony files are not written\n", pars_source.c_str());
             else {
                 const size_t nodes = n + (size_t)M;
@@ -875,6 +918,67 @@ int main(int argc, char **argv)
                     { "excess_changes", t.excess_changes }, { "homoplasic_sites", t.homoplasic_sites } };
                 for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
                 fprintf(f, "ci\t%s\ntree\t%s\n", fmt(t.ci).c_str(), pars_source.c_str());
+                fclose(f);
+            }
+        }
+        if (!tcmp_source[0].empty()) {                                 // (no counterpart in the reference: docs/TREE_COMPARISON.md)
+            const size_t n = (size_t)p.pop_size;
+            std::vector<uint32_t> left[2], right[2], vals[2];
+            uint64_t M[2] = { 0, 0 };
+            for (int x = 0; x < 2; x++) {
+                left[x].resize(n);
+                right[x].resize(n);
+                vals[x].resize(n);
+                CK(merge_list(tcmp_source[x], left[x].data(), right[x].data(), vals[x].data(), &M[x]));
+            }
+            if (M[0] == 0 || M[1] == 0)
+                fprintf(stderr, "pansim: the %s of --print_tree_compare has no merge: the _tree_compare files are not written\n",
+                        tcmp_source[M[0] == 0 ? 0 : 1].c_str());
+            else {
+                const size_t na = (size_t)tcmp_prm.bins_a + 1, nb = (size_t)tcmp_prm.bins_b + 1;
+                std::vector<uint64_t> joint(na * nb);
+                std::vector<uint8_t> in_other[2] = { std::vector<uint8_t>(M[0]), std::vector<uint8_t>(M[1]) };
+                ps_tree_compare_t t;
+                CK(multi ? ps_multi_tree_compare(multi, left[0].data(), right[0].data(), vals[0].data(), M[0], left[1].data(), right[1].data(),
+                                                 vals[1].data(), M[1], &tcmp_prm, &t, joint.data(), in_other[0].data(), in_other[1].data())
+                         : ps_sim_tree_compare(sim, left[0].data(), right[0].data(), vals[0].data(), M[0], left[1].data(), right[1].data(),
+                                               vals[1].data(), M[1], &tcmp_prm, &t, joint.data(), in_other[0].data(), in_other[1].data()));
+                FILE *f = open_out(outpref, "_tree_compare.tsv");
+                for (size_t a = 0; a < na; a++)
+                    for (size_t b = 0; b < nb; b++)
+                        if (joint[a * nb + b]) fprintf(f, "%zu\t%zu\t%llu\n", a, b, (unsigned long long)joint[a * nb + b]);
+                fclose(f);
+                // the clades: the merges whose parent carries another value (or that have none), with the leaves below them
+                f = open_out(outpref, "_tree_compare_clades.tsv");
+                for (int x = 0; x < 2; x++) {
+                    std::vector<long long> parent(M[x], -1);
+                    std::vector<uint32_t> size(M[x]);
+                    for (uint64_t k = 0; k < M[x]; k++) {
+                        size[k] = 0;
+                        for (uint32_t c : { left[x][k], right[x][k] }) {
+                            size[k] += c < n ? 1u : size[c - n];
+                            if (c >= n) parent[c - n] = (long long)k;
+                        }
+                    }
+                    for (uint64_t k = 0; k < M[x]; k++)
+                        if (parent[k] < 0 || vals[x][(size_t)parent[k]] != vals[x][k])
+                            fprintf(f, "%s\t%llu\t%u\t%u\t%u\n", tcmp_source[x].c_str(), (unsigned long long)(n + k), size[k], vals[x][k], (unsigned)in_other[x][k]);
+                }
+                fclose(f);
+                f = open_out(outpref, "_tree_compare_summary.tsv");
+                const std::pair<const char *, uint64_t> fields[] = {
+                    { "pop_size", t.pop_size }, { "merges_a", t.merges_a }, { "merges_b", t.merges_b }, { "pairs", t.pairs },
+                    { "joined_both", t.joined_both }, { "joined_a_only", t.joined_a_only }, { "joined_b_only", t.joined_b_only },
+                    { "joined_neither", t.joined_neither }, { "sum_a", t.sum_a }, { "sum_b", t.sum_b }, { "sum_aa", t.sum_aa }, { "sum_bb", t.sum_bb },
+                    { "sum_ab", t.sum_ab }, { "triples", t.triples }, { "resolved_a", t.resolved_a }, { "resolved_b", t.resolved_b },
+                    { "shared_triplets", t.shared_triplets }, { "clades_a", t.clades_a }, { "clades_b", t.clades_b }, { "shared_clades", t.shared_clades },
+                    { "rf_distance", t.rf_distance }, { "bins_a", t.bins_a }, { "bins_b", t.bins_b }, { "span_a", t.span_a }, { "span_b", t.span_b } };
+                for (const auto &x : fields) fprintf(f, "%s\t%llu\n", x.first, (unsigned long long)x.second);
+                const std::pair<const char *, double> doubles[] = {
+                    { "cophenetic_r", t.cophenetic_r }, { "triplet_recall", t.triplet_recall }, { "triplet_precision", t.triplet_precision },
+                    { "clade_recall", t.clade_recall }, { "clade_precision", t.clade_precision } };
+                for (const auto &x : doubles) fprintf(f, "%s\t%s\n", x.first, fmt(x.second).c_str());
+                fprintf(f, "a\t%s\nb\t%s\n", tcmp_source[0].c_str(), tcmp_source[1].c_str());
                 fclose(f);
             }
         }

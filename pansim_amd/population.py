@@ -346,6 +346,12 @@ class LinkageTree(_Summary):
         from .parsimony import merges_from_tree
         return merges_from_tree(self.lo, self.hi, self.pop_size)
 
+    def levels(self):
+        """uint32 per merge: the dense rank (from 1) of its edge's distance (ps_levels_from_heights) -- the values
+        `tree_compare` reads this tree with"""
+        from .tree_compare import levels_from_heights
+        return levels_from_heights(self.num, self.den)
+
     def as_dict(self):
         out = self._head()
         out.update(lo=self.lo, hi=self.hi, num=self.num, den=self.den, distance=self.distance)
@@ -399,6 +405,12 @@ class UpgmaTree(_Summary):
         self.left, self.right, self.size, self.num, self.den = left[:n], right[:n], size[:n], num[:n], den[:n]
         self.merges = _MergeCount(n, self.left, self.right)
         self.distance = self.num.astype(np.float64) / self.den.astype(np.float64)
+
+    def levels(self):
+        """uint32 per merge: the dense rank (from 1) of its height (ps_levels_from_heights) -- the values `tree_compare`
+        reads this tree with"""
+        from .tree_compare import levels_from_heights
+        return levels_from_heights(self.num, self.den)
 
     def _kept(self, num, den):
         """how many merges (a prefix: the heights do not descend) lie at or below num / den under the integer rule
@@ -959,6 +971,19 @@ class Population:
     def tree_parsimony_timing(self):
         """device ms of (the schedule's upload, the core pass, the gene pass) of the last tree_parsimony() on this core handle"""
         return _timing(self._lib.ps_tree_parsimony_timing, 3, self._h)
+
+    def tree_compare(self, a, b, bins=(32, 32), spans=(0, 0), triplets=True, values=None):
+        """How well tree `b` recovers tree `a` over the pop_size leaves of this handle (ps_tree_compare;
+        docs/TREE_COMPARISON.md) -> a TreeComparison: the cophenetic agreement over all pairs, the rooted triplets both
+        resolve alike (`triplets`), the shared clades.  A tree is a `(left, right)` or `(left, right, val)` tuple, a
+        LinkageTree or an UpgmaTree (values: `levels()`) or a GenealogyResult (values: the coalescence times); `values`:
+        a pair (val_a, val_b) that replaces them (None: keep).  Any handle will do: no matrix is read."""
+        from .tree_compare import _compare_call
+        return _compare_call(self._lib.ps_tree_compare, self._h, a, b, bins, spans, triplets, values)
+
+    def tree_compare_timing(self):
+        """device ms of (the uploads and the tables, the pass over all pairs) of the last tree_compare() on this handle"""
+        return _timing(self._lib.ps_tree_compare_timing, 2, self._h)
 
     def locus_ld(self, r2_bins=64, lag_bins=1, min_minor=1, max_loci=4096, loci=None):
         """linkage disequilibrium between the columns of this handle -- core sites or accessory genes by its kind

@@ -265,6 +265,15 @@ class Simulation:
         """device ms of (the schedule's upload, the core pass, the gene pass) of the last tree_parsimony()"""
         return self.core_genome.tree_parsimony_timing()
 
+    def tree_compare(self, a, b, bins=(32, 32), spans=(0, 0), triplets=True, values=None):
+        """Population.tree_compare() on the run's core handle (ps_sim_tree_compare): `tree_compare(genealogy(), upgma_tree())`"""
+        from .tree_compare import _compare_call
+        return _compare_call(self._lib.ps_sim_tree_compare, self._h, a, b, bins, spans, triplets, values)
+
+    def tree_compare_timing(self):
+        """device ms of (the uploads and the tables, the pass over all pairs) of the last tree_compare()"""
+        return self.core_genome.tree_compare_timing()
+
     def linkage_tree(self, metric="core"):
         """Population.linkage_tree() of the run's two matrices (ps_sim_linkage_tree), edges in the reference's row order"""
         from .population import _tree_call, _tree_params
@@ -430,6 +439,15 @@ class MultiSimulation:
     def tree_parsimony_timing(self):
         """device ms of (the schedule's upload, the core pass, the gene pass) of the last tree_parsimony() (shard 0's handle)"""
         return self.shards[0].tree_parsimony_timing()
+
+    def tree_compare(self, a, b, bins=(32, 32), spans=(0, 0), triplets=True, values=None):
+        """Population.tree_compare() on shard 0's core handle: trees are global (ps_multi_tree_compare)"""
+        from .tree_compare import _compare_call
+        return _compare_call(self._lib.ps_multi_tree_compare, self._h, a, b, bins, spans, triplets, values)
+
+    def tree_compare_timing(self):
+        """device ms of (the uploads and the tables, the pass over all pairs) of the last tree_compare() (shard 0's handle)"""
+        return self.shards[0].tree_compare_timing()
 
     def linkage_tree(self, metric="core"):
         """Population.linkage_tree() over ALL core sites: the shards' band counts added and kept on shard 0, the rounds
