@@ -229,6 +229,13 @@ _vp, _u64, _u32, _i32, _f64, _int = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int3
 # ps_exchange_fn: int (*)(void *ctx, void *d_words, uint64_t n_words, void *hip_stream)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
 
+
+def _run_forms(name, tail):
+    """the entries of a read-out of the regular shape, its arguments behind the handles typed once:
+    ps_X(core, acc, tail...), ps_sim_X(sim, tail...) and ps_multi_X(multi, tail...)"""
+    return {"ps_" + name: (_int, [_vp, _vp] + tail), "ps_sim_" + name: (_int, [_vp] + tail), "ps_multi_" + name: (_int, [_vp] + tail)}
+
+
 SIGNATURES = {
     "ps_last_error": (C.c_char_p, []),
     "ps_abi_version": (_int, []),
@@ -319,31 +326,21 @@ SIGNATURES = {
     "ps_multi_average_distance": (_int, [_vp, _int, _f64p]),
     "ps_multi_site_allele_counts": (_int, [_vp, _vp]),
     "ps_multi_core_diversity": (_int, [_vp, C.POINTER(CoreDiversity), _vp]),
-    "ps_distance_histogram": (_int, [_vp, _vp, C.POINTER(PairHistParams), C.POINTER(PairHist), _vp]),
-    "ps_sim_distance_histogram": (_int, [_vp, C.POINTER(PairHistParams), C.POINTER(PairHist), _vp]),
-    "ps_multi_distance_histogram": (_int, [_vp, C.POINTER(PairHistParams), C.POINTER(PairHist), _vp]),
+    **_run_forms("distance_histogram", [C.POINTER(PairHistParams), C.POINTER(PairHist), _vp]),
     "ps_histogram_from_counts": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, C.POINTER(PairHistParams), C.POINTER(PairHist), _vp]),
     "ps_distance_histogram_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
-    "ps_strain_clusters": (_int, [_vp, _vp, C.POINTER(ClusterParams), C.POINTER(Clusters), _vp]),
-    "ps_sim_strain_clusters": (_int, [_vp, C.POINTER(ClusterParams), C.POINTER(Clusters), _vp]),
-    "ps_multi_strain_clusters": (_int, [_vp, C.POINTER(ClusterParams), C.POINTER(Clusters), _vp]),
+    **_run_forms("strain_clusters", [C.POINTER(ClusterParams), C.POINTER(Clusters), _vp]),
     "ps_clusters_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(ClusterParams), C.POINTER(Clusters), _vp]),
     "ps_strain_clusters_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
-    "ps_linkage_tree": (_int, [_vp, _vp, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
-    "ps_sim_linkage_tree": (_int, [_vp, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
-    "ps_multi_linkage_tree": (_int, [_vp, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
+    **_run_forms("linkage_tree", [C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
     "ps_tree_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(TreeParams), C.POINTER(Tree), _vp, _vp, _vp, _vp]),
     "ps_linkage_tree_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
-    "ps_upgma_tree": (_int, [_vp, _vp, C.POINTER(TreeParams), C.POINTER(Upgma), _vp, _vp, _vp, _vp, _vp]),
-    "ps_sim_upgma_tree": (_int, [_vp, C.POINTER(TreeParams), C.POINTER(Upgma), _vp, _vp, _vp, _vp, _vp]),
-    "ps_multi_upgma_tree": (_int, [_vp, C.POINTER(TreeParams), C.POINTER(Upgma), _vp, _vp, _vp, _vp, _vp]),
+    **_run_forms("upgma_tree", [C.POINTER(TreeParams), C.POINTER(Upgma), _vp, _vp, _vp, _vp, _vp]),
     "ps_upgma_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(TreeParams), C.POINTER(Upgma), _vp, _vp, _vp, _vp,
                                     _vp]),
     "ps_upgma_newick": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     "ps_upgma_tree_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
-    "ps_nearest_neighbours": (_int, [_vp, _vp, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
-    "ps_sim_nearest_neighbours": (_int, [_vp, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
-    "ps_multi_nearest_neighbours": (_int, [_vp, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
+    **_run_forms("nearest_neighbours", [C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
     "ps_neighbours_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
     "ps_lineages_from_neighbours": (_int, [_vp, _u64, C.c_uint32, C.c_uint32, C.POINTER(Lineages), _vp]),
     "ps_nearest_neighbours_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
@@ -366,14 +363,10 @@ SIGNATURES = {
     "ps_ld_from_counts": (_int, [_vp, _vp, _vp, _u64, _u64, C.POINTER(LdParams), C.POINTER(Ld), _vp, _vp]),
     "ps_locus_ld_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_groups_from_labels": (_int, [_vp, _u64, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
-    "ps_group_differentiation": (_int, [_vp, _vp, _vp, C.POINTER(DiffParams), C.POINTER(Diff)] + [_vp] * 12),
-    "ps_sim_group_differentiation": (_int, [_vp, _vp, C.POINTER(DiffParams), C.POINTER(Diff)] + [_vp] * 12),
-    "ps_multi_group_differentiation": (_int, [_vp, _vp, C.POINTER(DiffParams), C.POINTER(Diff)] + [_vp] * 12),
+    **_run_forms("group_differentiation", [_vp, C.POINTER(DiffParams), C.POINTER(Diff)] + [_vp] * 12),
     "ps_differentiation_from_counts": (_int, [_vp, _u64, _u32, _vp, C.POINTER(Diff), _vp, _vp, _vp, _vp]),
     "ps_group_differentiation_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
-    "ps_tree_parsimony": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(Parsimony)] + [_vp] * 8),
-    "ps_sim_tree_parsimony": (_int, [_vp, _vp, _vp, _u64, C.POINTER(Parsimony)] + [_vp] * 8),
-    "ps_multi_tree_parsimony": (_int, [_vp, _vp, _vp, _u64, C.POINTER(Parsimony)] + [_vp] * 8),
+    **_run_forms("tree_parsimony", [_vp, _vp, _u64, C.POINTER(Parsimony)] + [_vp] * 8),
     "ps_tree_parsimony_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_merges_from_tree": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, C.POINTER(_u64)]),
     "ps_merges_from_genealogy": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)]),

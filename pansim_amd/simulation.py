@@ -75,8 +75,129 @@ def state_info(path, per_gen=False):
     return out
 
 
-class Simulation:
+class _Readouts:
+    """The outputs and read-outs a run has in both of its forms, written once.  Simulation resolves them to the ps_sim_
+    entries of the library and MultiSimulation to the ps_multi_ ones (`_prefix`); `_core_width` is the core width of the
+    per-site arrays a call returns and `_timed` the Simulation whose core handle holds the device times of the last call."""
+
+    def _entry(self, name):
+        return getattr(self._lib, self._prefix + name)
+
+    def run(self, count, first_generation=None):
+        """main.rs:429-464 for `count` generations (asynchronous; call sync()) (ps_sim_run / ps_multi_run)"""
+        g0 = self.generation if first_generation is None else int(first_generation)
+        check(self._entry("run")(self._h, g0, int(count)))
+        self.generation = g0 + int(count)
+
+    def sync(self):
+        check(self._entry("sync")(self._h))
+
+    # -- outputs of main.rs:467-499 ---------------------------------------------------
+    def final_distances(self):
+        """main.rs:467-470 (ps_sim_pairwise_distances / ps_multi_pairwise_distances: both matrices' kernels enqueued together)"""
+        P = self.params.max_distances
+        core, acc = np.zeros(P), np.zeros(P)
+        check(self._entry("pairwise_distances")(self._h, core, acc))
+        return core, acc
+
+    # -- the read-outs over ALL pairs and sites: behind every queued generation and without a change of state (the run
+    # continues as if it had not been asked); rows, labels and leaves in the reference's row order.  Of a sharded run they
+    # cover ALL core sites: the shards' band counts, integers and matrices are added on shard 0, their per-site arrays
+    # concatenated, and the accessory side comes from shard 0's replica ---------------------------------------------
+    def distance_histogram(self, core_bins=64, acc_bins=64, core_max=None, core_span=None):
+        """Population.distance_histogram() of the run's two matrices (ps_sim_distance_histogram / ps_multi_distance_histogram)"""
+        from .population import _hist_call, _hist_params
+        prm = _hist_params(core_bins, acc_bins, core_max, self.params.core_size, core_span)
+        return _hist_call(self._entry("distance_histogram"), prm, self._h)
+
+    def strain_clusters(self, core_max=None, acc_max=None, core_max_d=None, acc_ratio=None):
+        """Population.strain_clusters() of the run's two matrices (ps_sim_strain_clusters / ps_multi_strain_clusters)"""
+        from .population import _cluster_call, _cluster_params
+        prm = _cluster_params(self.params.core_size, core_max, acc_max, core_max_d, acc_ratio)
+        return _cluster_call(self._entry("strain_clusters"), prm, self.params.pop_size, self._h)
+
+    def group_differentiation(self, labels, max_groups=16, min_size=1, per_site=False, counts=False):
+        """Population.group_differentiation() of the run's two matrices (ps_sim_group_differentiation /
+        ps_multi_group_differentiation)"""
+        from .population import _diff_call
+        return _diff_call(self._entry("group_differentiation"), labels, self.params.pop_size, self._core_width,
+                          self.pan_genome.ncols, max_groups, min_size, per_site, counts, True, self._h)
+
+    def tree_parsimony(self, left, right, per_site=False, branches=False, genes=False):
+        """Population.tree_parsimony() of the run's two matrices (ps_sim_tree_parsimony / ps_multi_tree_parsimony)"""
+        from .parsimony import _pars_call
+        return _pars_call(self._entry("tree_parsimony"), left, right, self.params.pop_size, self._core_width,
+                          self.pan_genome.ncols if genes else 0, per_site, branches, genes, self._h)
+
+    def tree_parsimony_timing(self):
+        """device ms of (the schedule's upload, the core pass, the gene pass) of the last tree_parsimony()"""
+        return self._timed.core_genome.tree_parsimony_timing()
+
+    def tree_compare(self, a, b, bins=(32, 32), spans=(0, 0), triplets=True, values=None):
+        """Population.tree_compare() on the run's core handle, shard 0's of a sharded run: trees are global (ps_sim_tree_compare /
+        ps_multi_tree_compare): `tree_compare(genealogy(), upgma_tree())`"""
+        from .tree_compare import _compare_call
+        return _compare_call(self._entry("tree_compare"), self._h, a, b, bins, spans, triplets, values)
+
+    def tree_compare_timing(self):
+        """device ms of (the uploads and the tables, the pass over all pairs) of the last tree_compare()"""
+        return self._timed.core_genome.tree_compare_timing()
+
+    def linkage_tree(self, metric="core"):
+        """Population.linkage_tree() of the run's two matrices (ps_sim_linkage_tree / ps_multi_linkage_tree)"""
+        from .population import _tree_call, _tree_params
+        return _tree_call(self._entry("linkage_tree"), _tree_params(metric), self.params.pop_size, self._h)
+
+    def upgma_tree(self, metric="core"):
+        """Population.upgma_tree() of the run's two matrices (ps_sim_upgma_tree / ps_multi_upgma_tree)"""
+        from .population import _tree_params, _upgma_call
+        return _upgma_call(self._entry("upgma_tree"), _tree_params(metric), self.params.pop_size, self._h)
+
+    def nearest_neighbours(self, k, metric="core"):
+        """Population.nearest_neighbours() of the run's two matrices (ps_sim_nearest_neighbours / ps_multi_nearest_neighbours)"""
+        from .population import _knn_call, _knn_params
+        return _knn_call(self._entry("nearest_neighbours"), _knn_params(k, metric), self.params.pop_size, self._h)
+
+    # -- the recorded genealogy (docs/GENEALOGY.md) --------------------------------------
+    def record_ancestry(self, capacity):
+        """keep the parent draws of the last `capacity` generations on the device (ps_sim_record_ancestry /
+        ps_multi_record_ancestry: every shard draws the same parents, shard 0 records alone); 0 switches the recording off.
+        The matrices of the run do not change by a bit."""
+        check(self._entry("record_ancestry")(self._h, int(capacity)))
+
+    def genealogy(self):
+        """the comb of the present population from the recorded draws (ps_sim_genealogy / ps_multi_genealogy) -> a
+        GenealogyResult with order, coal, pair(i, j), clusters(t), newick(); rows in the reference's row order"""
+        from .genealogy import _genealogy_call
+        return _genealogy_call(self._entry("genealogy"), self.params.pop_size, self._h)
+
+    def clock_histogram(self, metric="core", time_bins=32, dist_bins=64, time_span=None, core_max=None, core_span=None):
+        """ALL pairs binned by (divergence time from the record, distance) (ps_sim_clock_histogram / ps_multi_clock_histogram)
+        -> a ClockHistogram"""
+        from .genealogy import _clock_call, _clock_params
+        prm = _clock_params(metric, time_bins, dist_bins, time_span, core_max, self.params.core_size, core_span)
+        return _clock_call(self._entry("clock_histogram"), prm, self._h)
+
+    def clock_histogram_timing(self):
+        """device ms of (the count kernels; the comb, the table and the binning) of the last clock_histogram()"""
+        t = [C.c_double(), C.c_double()]
+        check(self._lib.ps_clock_histogram_timing(self._lib.ps_sim_core(self._timed._h), *map(C.byref, t)))
+        return tuple(x.value for x in t)
+
+    def locus_ld(self, metric="core", r2_bins=64, lag_bins=1, min_minor=1, max_loci=4096, loci=None):
+        """linkage disequilibrium between the core sites (every shard selects and packs its own, shard 0 contracts and bins;
+        columns are global) or the accessory genes of the run (ps_sim_locus_ld / ps_multi_locus_ld;
+        docs/LINKAGE_DISEQUILIBRIUM.md) -> a LocusLd"""
+        from .linkage import _ld_call, _ld_params, _metric
+        m = _metric(metric)
+        return _ld_call(self._entry("locus_ld"), _ld_params(r2_bins, lag_bins, min_minor, max_loci), loci, self._h, m)
+
+
+class Simulation(_Readouts):
     """State of main() between main.rs:259 and :553 for one process (one GPU)."""
+    _prefix = "ps_sim_"
+    _core_width = property(lambda self: self.core_genome.ncols)       # the shard's columns when it is a shard
+    _timed = property(lambda self: self)
 
     def __init__(self, params=None, _handle=None, **kw):
         self._lib = _lib.load()
@@ -117,15 +238,6 @@ class Simulation:
             self.close()
         except Exception:
             pass
-
-    def run(self, count, first_generation=None):
-        """main.rs:429-464 for `count` generations (asynchronous; call sync())"""
-        g0 = self.generation if first_generation is None else int(first_generation)
-        check(self._lib.ps_sim_run(self._h, g0, int(count)))
-        self.generation = g0 + int(count)
-
-    def sync(self):
-        check(self._lib.ps_sim_sync(self._h))
 
     # -- state files (ps_sim_save / ps_sim_load; docs/STATE_FORMAT.md) -----------------
     def save(self, path, per_gen=None):
@@ -219,107 +331,11 @@ class Simulation:
         check(self._lib.ps_sim_host_timing(self._h, int(reset), C.byref(n), C.byref(a), C.byref(b), C.byref(c)))
         return n.value, a.value, b.value, c.value
 
-    # -- outputs of main.rs:467-499 ---------------------------------------------------
-    def final_distances(self):
-        """main.rs:467-470 (ps_sim_pairwise_distances: both matrices' kernels enqueued together)"""
-        P = self.params.max_distances
-        core, acc = np.zeros(P), np.zeros(P)
-        check(self._lib.ps_sim_pairwise_distances(self._h, core, acc))
-        return core, acc
-
     def distance_timing(self):
         """device ms of the core / accessory distance kernels of the last final_distances() call"""
         a, b = C.c_double(), C.c_double()
         check(self._lib.ps_sim_distance_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
-
-    def distance_histogram(self, core_bins=64, acc_bins=64, core_max=None, core_span=None):
-        """Population.distance_histogram() of the run's two matrices (ps_sim_distance_histogram): behind every queued
-        generation, and without a change of state -- the run continues as if it had not been asked"""
-        from .population import _hist_call, _hist_params
-        prm = _hist_params(core_bins, acc_bins, core_max, self.params.core_size, core_span)
-        return _hist_call(self._lib.ps_sim_distance_histogram, prm, self._h)
-
-    def strain_clusters(self, core_max=None, acc_max=None, core_max_d=None, acc_ratio=None):
-        """Population.strain_clusters() of the run's two matrices (ps_sim_strain_clusters), labels in the reference's row
-        order: behind every queued generation, and without a change of state"""
-        from .population import _cluster_call, _cluster_params
-        prm = _cluster_params(self.params.core_size, core_max, acc_max, core_max_d, acc_ratio)
-        return _cluster_call(self._lib.ps_sim_strain_clusters, prm, self.params.pop_size, self._h)
-
-    def group_differentiation(self, labels, max_groups=16, min_size=1, per_site=False, counts=False):
-        """Population.group_differentiation() of the run's two matrices (ps_sim_group_differentiation), labels in the
-        reference's row order: behind every queued generation, and without a change of state"""
-        from .population import _diff_call
-        return _diff_call(self._lib.ps_sim_group_differentiation, labels, self.params.pop_size, self.core_genome.ncols,
-                          self.pan_genome.ncols, max_groups, min_size, per_site, counts, True, self._h)
-
-    def tree_parsimony(self, left, right, per_site=False, branches=False, genes=False):
-        """Population.tree_parsimony() of the run's two matrices (ps_sim_tree_parsimony), leaves in the reference's row order:
-        behind every queued generation, and without a change of state"""
-        from .parsimony import _pars_call
-        return _pars_call(self._lib.ps_sim_tree_parsimony, left, right, self.params.pop_size, self.core_genome.ncols,
-                          self.pan_genome.ncols if genes else 0, per_site, branches, genes, self._h)
-
-    def tree_parsimony_timing(self):
-        """device ms of (the schedule's upload, the core pass, the gene pass) of the last tree_parsimony()"""
-        return self.core_genome.tree_parsimony_timing()
-
-    def tree_compare(self, a, b, bins=(32, 32), spans=(0, 0), triplets=True, values=None):
-        """Population.tree_compare() on the run's core handle (ps_sim_tree_compare): `tree_compare(genealogy(), upgma_tree())`"""
-        from .tree_compare import _compare_call
-        return _compare_call(self._lib.ps_sim_tree_compare, self._h, a, b, bins, spans, triplets, values)
-
-    def tree_compare_timing(self):
-        """device ms of (the uploads and the tables, the pass over all pairs) of the last tree_compare()"""
-        return self.core_genome.tree_compare_timing()
-
-    def linkage_tree(self, metric="core"):
-        """Population.linkage_tree() of the run's two matrices (ps_sim_linkage_tree), edges in the reference's row order"""
-        from .population import _tree_call, _tree_params
-        return _tree_call(self._lib.ps_sim_linkage_tree, _tree_params(metric), self.params.pop_size, self._h)
-
-    def upgma_tree(self, metric="core"):
-        """Population.upgma_tree() of the run's two matrices (ps_sim_upgma_tree), leaves in the reference's row order"""
-        from .population import _tree_params, _upgma_call
-        return _upgma_call(self._lib.ps_sim_upgma_tree, _tree_params(metric), self.params.pop_size, self._h)
-
-    def nearest_neighbours(self, k, metric="core"):
-        """Population.nearest_neighbours() of the run's two matrices (ps_sim_nearest_neighbours), rows and neighbours in the
-        reference's row order"""
-        from .population import _knn_call, _knn_params
-        return _knn_call(self._lib.ps_sim_nearest_neighbours, _knn_params(k, metric), self.params.pop_size, self._h)
-
-    # -- the recorded genealogy (docs/GENEALOGY.md) --------------------------------------
-    def record_ancestry(self, capacity):
-        """keep the parent draws of the last `capacity` generations on the device (ps_sim_record_ancestry); 0 switches the
-        recording off.  The matrices of the run do not change by a bit."""
-        check(self._lib.ps_sim_record_ancestry(self._h, int(capacity)))
-
-    def genealogy(self):
-        """the comb of the present population from the recorded draws (ps_sim_genealogy) -> a GenealogyResult with order,
-        coal, pair(i, j), clusters(t), newick(); rows in the reference's row order"""
-        from .genealogy import _genealogy_call
-        return _genealogy_call(self._lib.ps_sim_genealogy, self.params.pop_size, self._h)
-
-    def clock_histogram(self, metric="core", time_bins=32, dist_bins=64, time_span=None, core_max=None, core_span=None):
-        """ALL pairs binned by (divergence time from the record, distance) (ps_sim_clock_histogram) -> a ClockHistogram"""
-        from .genealogy import _clock_call, _clock_params
-        prm = _clock_params(metric, time_bins, dist_bins, time_span, core_max, self.params.core_size, core_span)
-        return _clock_call(self._lib.ps_sim_clock_histogram, prm, self._h)
-
-    def locus_ld(self, metric="core", r2_bins=64, lag_bins=1, min_minor=1, max_loci=4096, loci=None):
-        """linkage disequilibrium between the core sites or the accessory genes of the run (ps_sim_locus_ld;
-        docs/LINKAGE_DISEQUILIBRIUM.md) -> a LocusLd"""
-        from .linkage import _ld_call, _ld_params, _metric
-        m = _metric(metric)
-        return _ld_call(self._lib.ps_sim_locus_ld, _ld_params(r2_bins, lag_bins, min_minor, max_loci), loci, self._h, m)
-
-    def clock_histogram_timing(self):
-        """device ms of (the count kernels; the comb, the table and the binning) of the last clock_histogram()"""
-        t = [C.c_double(), C.c_double()]
-        check(self._lib.ps_clock_histogram_timing(self._lib.ps_sim_core(self._h), *map(C.byref, t)))
-        return tuple(x.value for x in t)
 
     def write_outputs(self, outpref):
         core, acc = self.final_distances()
@@ -332,9 +348,12 @@ class Simulation:
             self.pan_genome.write(outpref)
 
 
-class MultiSimulation:
+class MultiSimulation(_Readouts):
     """The run sharded by core site inside ONE process (ps_multi): shard k on HIP device devices[k]
     (ordinals may repeat), one host thread per shard inside each call; results equal the unsharded run."""
+    _prefix = "ps_multi_"
+    _core_width = property(lambda self: self.params.core_size)
+    _timed = property(lambda self: self.shards[0])
 
     def __init__(self, params, n_shards, devices=None):
         self._lib = _lib.load()
@@ -371,24 +390,10 @@ class MultiSimulation:
         except Exception:
             pass
 
-    def run(self, count, first_generation=None):
-        g0 = self.generation if first_generation is None else int(first_generation)
-        check(self._lib.ps_multi_run(self._h, g0, int(count)))
-        self.generation = g0 + int(count)
-
-    def sync(self):
-        check(self._lib.ps_multi_sync(self._h))
-
     def pairwise_counts(self):
         out = np.zeros(self.params.max_distances, np.uint32)
         check(self._lib.ps_multi_pairwise_counts(self._h, out))
         return out
-
-    def final_distances(self):
-        P = self.params.max_distances
-        core, acc = np.zeros(P), np.zeros(P)
-        check(self._lib.ps_multi_pairwise_distances(self._h, core, acc))
-        return core, acc
 
     def average_distance(self, core=True):
         """population.rs:753-784 of the run's core matrix (the shards' counts summed) or of its accessory matrix"""
@@ -407,93 +412,6 @@ class MultiSimulation:
         """Population.core_diversity() of the whole core matrix: the shards' integers and spectra added"""
         from .population import _diversity_call
         return _diversity_call(self._lib.ps_multi_core_diversity, self.params.pop_size, spectrum, self._h)
-
-    def distance_histogram(self, core_bins=64, acc_bins=64, core_max=None, core_span=None):
-        """Population.distance_histogram() over ALL core sites: the shards' band counts added on shard 0, then halved and
-        binned against its accessory replica (ps_multi_distance_histogram)"""
-        from .population import _hist_call, _hist_params
-        prm = _hist_params(core_bins, acc_bins, core_max, self.params.core_size, core_span)
-        return _hist_call(self._lib.ps_multi_distance_histogram, prm, self._h)
-
-    def strain_clusters(self, core_max=None, acc_max=None, core_max_d=None, acc_ratio=None):
-        """Population.strain_clusters() over ALL core sites: the shards' band counts added on shard 0, edges and labels
-        against its accessory replica (ps_multi_strain_clusters)"""
-        from .population import _cluster_call, _cluster_params
-        prm = _cluster_params(self.params.core_size, core_max, acc_max, core_max_d, acc_ratio)
-        return _cluster_call(self._lib.ps_multi_strain_clusters, prm, self.params.pop_size, self._h)
-
-    def group_differentiation(self, labels, max_groups=16, min_size=1, per_site=False, counts=False):
-        """Population.group_differentiation() over ALL core sites: the shards' matrices and integers added, their per-site
-        arrays and counts concatenated, the genes from shard 0's accessory replica (ps_multi_group_differentiation)"""
-        from .population import _diff_call
-        return _diff_call(self._lib.ps_multi_group_differentiation, labels, self.params.pop_size, self.params.core_size,
-                          self.pan_genome.ncols, max_groups, min_size, per_site, counts, True, self._h)
-
-    def tree_parsimony(self, left, right, per_site=False, branches=False, genes=False):
-        """Population.tree_parsimony() over ALL core sites: the shards' arrays and integers added, their site_changes
-        concatenated, the genes from shard 0's accessory replica (ps_multi_tree_parsimony)"""
-        from .parsimony import _pars_call
-        return _pars_call(self._lib.ps_multi_tree_parsimony, left, right, self.params.pop_size, self.params.core_size,
-                          self.pan_genome.ncols if genes else 0, per_site, branches, genes, self._h)
-
-    def tree_parsimony_timing(self):
-        """device ms of (the schedule's upload, the core pass, the gene pass) of the last tree_parsimony() (shard 0's handle)"""
-        return self.shards[0].tree_parsimony_timing()
-
-    def tree_compare(self, a, b, bins=(32, 32), spans=(0, 0), triplets=True, values=None):
-        """Population.tree_compare() on shard 0's core handle: trees are global (ps_multi_tree_compare)"""
-        from .tree_compare import _compare_call
-        return _compare_call(self._lib.ps_multi_tree_compare, self._h, a, b, bins, spans, triplets, values)
-
-    def tree_compare_timing(self):
-        """device ms of (the uploads and the tables, the pass over all pairs) of the last tree_compare() (shard 0's handle)"""
-        return self.shards[0].tree_compare_timing()
-
-    def linkage_tree(self, metric="core"):
-        """Population.linkage_tree() over ALL core sites: the shards' band counts added and kept on shard 0, the rounds
-        against its accessory replica (ps_multi_linkage_tree)"""
-        from .population import _tree_call, _tree_params
-        return _tree_call(self._lib.ps_multi_linkage_tree, _tree_params(metric), self.params.pop_size, self._h)
-
-    def upgma_tree(self, metric="core"):
-        """Population.upgma_tree() over ALL core sites: the shards' band counts added and kept on shard 0, the rounds
-        against its accessory replica (ps_multi_upgma_tree)"""
-        from .population import _tree_params, _upgma_call
-        return _upgma_call(self._lib.ps_multi_upgma_tree, _tree_params(metric), self.params.pop_size, self._h)
-
-    def nearest_neighbours(self, k, metric="core"):
-        """Population.nearest_neighbours() over ALL core sites: the shards' band counts added on shard 0, the selection
-        against its accessory replica (ps_multi_nearest_neighbours)"""
-        from .population import _knn_call, _knn_params
-        return _knn_call(self._lib.ps_multi_nearest_neighbours, _knn_params(k, metric), self.params.pop_size, self._h)
-
-    def record_ancestry(self, capacity):
-        """Simulation.record_ancestry() for the sharded run: every shard draws the same parents, shard 0 records alone
-        (ps_multi_record_ancestry)"""
-        check(self._lib.ps_multi_record_ancestry(self._h, int(capacity)))
-
-    def genealogy(self):
-        """Simulation.genealogy() from shard 0's record (ps_multi_genealogy)"""
-        from .genealogy import _genealogy_call
-        return _genealogy_call(self._lib.ps_multi_genealogy, self.params.pop_size, self._h)
-
-    def clock_histogram(self, metric="core", time_bins=32, dist_bins=64, time_span=None, core_max=None, core_span=None):
-        """Simulation.clock_histogram() over ALL core sites: the shards' band counts added on shard 0, binned against its
-        record and accessory replica (ps_multi_clock_histogram)"""
-        from .genealogy import _clock_call, _clock_params
-        prm = _clock_params(metric, time_bins, dist_bins, time_span, core_max, self.params.core_size, core_span)
-        return _clock_call(self._lib.ps_multi_clock_histogram, prm, self._h)
-
-    def locus_ld(self, metric="core", r2_bins=64, lag_bins=1, min_minor=1, max_loci=4096, loci=None):
-        """Simulation.locus_ld() over ALL core sites (every shard selects and packs its own, shard 0 contracts and bins) or
-        over shard 0's accessory replica (ps_multi_locus_ld); columns are global"""
-        from .linkage import _ld_call, _ld_params, _metric
-        m = _metric(metric)
-        return _ld_call(self._lib.ps_multi_locus_ld, _ld_params(r2_bins, lag_bins, min_minor, max_loci), loci, self._h, m)
-
-    def clock_histogram_timing(self):
-        """device ms of (the count kernels; the comb, the table and the binning) of the last clock_histogram() (shard 0's handle)"""
-        return self.shards[0].clock_histogram_timing()
 
     def write(self, outpref):
         check(self._lib.ps_multi_write(self._h, str(outpref).encode()))

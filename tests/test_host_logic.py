@@ -27,6 +27,36 @@ def test_library_exports_every_declared_symbol(pa):
     assert lib.ps_abi_version() == 3      # round 4: ps_rccl_*, ps_sim_emulated_link_time, ps_last_sweep_form
 
 
+def test_run_methods_resolve_to_the_declared_symbols_of_their_class(pa):
+    # Simulation and MultiSimulation share the methods of one base class, which finds its library entry by the class's
+    # prefix: every such method must ask for a symbol that exists (and is typed), in the right family, in both classes.  No
+    # device: the library is replaced by an object that only notes the first symbol a method asks for.
+    from pansim_amd import _lib, simulation
+
+    class Asked(Exception):
+        pass
+
+    class Library:
+        def __getattr__(self, name):
+            raise Asked(name)
+
+    calls = dict(run=(1,), sync=(), final_distances=(), distance_histogram=(), strain_clusters=(0.1,), group_differentiation=([0] * 8,),
+                 tree_parsimony=([0], [1]), tree_compare=(None, None), linkage_tree=(), upgma_tree=(), nearest_neighbours=(2,),
+                 record_ancestry=(4,), genealogy=(), clock_histogram=(), locus_ld=())
+    timings = {"tree_parsimony_timing", "tree_compare_timing", "clock_histogram_timing"}      # (ask the core handle of `_timed`)
+    shared = {m for m in vars(simulation._Readouts) if not m.startswith("_")}
+    assert shared == set(calls) | timings
+    for cls, prefix in ((pa.Simulation, "ps_sim_"), (pa.MultiSimulation, "ps_multi_")):
+        assert not shared & set(vars(cls)), "defined again in %s" % cls.__name__
+        run = object.__new__(cls)
+        run._lib, run._h, run.generation = Library(), None, 0
+        run.params = _lib.SimParams(pop_size=8, core_size=100, pan_genes=60, core_genes=20, max_distances=10)
+        for method, args in calls.items():
+            with pytest.raises(Asked) as e:
+                getattr(run, method)(*args)
+            assert str(e.value).startswith(prefix) and str(e.value) in _lib.SIGNATURES, (cls.__name__, method, str(e.value))
+
+
 def test_no_cpu_fallback_without_device(pa):
     # in the CPU container every compute entry point must fail loudly, never fall back
     if pa.load().ps_device_count() > 0:
