@@ -2,11 +2,14 @@
 thread_rng() (population.rs:493, :517, :596), so only their DISTRIBUTIONS are contractual.  The
 keyed dense form the HIP kernels implement (restated in the oracle) is checked here against
 the closed forms of SURVEY 8(a) and against the event-driven reference algorithm (orc_ref_*).
-All CPU; the GPU path is bit-exact with the dense oracle (tests/test_gpu_parity.py).
+All CPU; the GPU path is bit-exact with the dense oracle (tests/test_gpu_parity.py) and is held to the same closed forms
+(tests/stat_laws.py) at 10^9 cells by tests/test_gpu_stat_conformance.py.
 """
 import math
 
 import numpy as np
+
+import stat_laws as sl
 
 
 def test_core_mutation_rate_and_alleles(orc):
@@ -14,7 +17,8 @@ def test_core_mutation_rate_and_alleles(orc):
     m0 = np.ones((N, L), np.uint8)
     plan = orc.core_plan(lam, 0.0, L)
     m = orc.mutate_core(m0.copy(), 0, 123, 0, plan)
-    p = -math.expm1(-lam / L)
+    p, _ = sl.core_pq(lam, 0.0, L)
+    assert p == -math.expm1(-lam / L)
     hit = (m != 1)
     n = N * L
     assert abs(hit.mean() - p) < 5 * math.sqrt(p * (1 - p) / n)
@@ -66,7 +70,8 @@ def test_acc_flip_probabilities(orc):
     lam = [900.0, 100000.0]                              # rates 1.0 and 1000 per site (main.rs:348, :361)
     m0 = np.zeros((N, G), np.uint8)
     m = orc.mutate_acc(m0.copy(), 3, 0, cb, ce, lam)
-    p1 = (1 - math.exp(-2.0)) / 2                         # 0.43233235838169365
+    p1 = sl.p_flip(900.0, 900)                            # (1 - exp(-2)) / 2 = 0.43233235838169365
+    assert abs(p1 - (1 - math.exp(-2.0)) / 2) < 1e-15
     f1, f2 = m[:, :900].mean(), m[:, 900:].mean()
     assert abs(f1 - p1) < 5 * math.sqrt(p1 * (1 - p1) / (N * 900))
     assert abs(f2 - 0.5) < 5 * math.sqrt(0.25 / (N * 100))
