@@ -911,6 +911,78 @@ int ps_ld_from_counts(const uint32_t *locus_index, const uint32_t *locus_count, 
  * before any call. */
 int ps_locus_ld_timing(ps_population *p, double *select_ms, double *pack_ms, double *counts_ms, double *stats_ms);
 
+/* Gene-site association (docs/GENE_SITE_ASSOCIATION.md) -- the cross block ps_locus_ld leaves out: r^2 over all pairs (accessory
+ * gene g, core site s) of two selected lists.  The reference has no such function (the signature of its recombination is read off
+ * population.rs:544-751, the counts are those of :840-863).  Indicators, c and "monomorphic" are those of ps_locus_ld.  The
+ * selection rule of ps_locus_ld runs on each side on its own: sites with site_min_minor / max_sites or the strictly ascending
+ * list `sites`, genes with gene_min_minor / max_genes or `genes`; Ms sites, Mg genes, either may be 0 (no pairs).  Per pair, n11 =
+ * the individuals with both indicators set: a pair with a monomorphic locus is counted in undefined_pairs and nowhere else;
+ * otherwise q, the sign of D, the four-gamete flag and `complete` are those of ps_locus_ld, r^2 bin = min(r2_bins - 1,
+ * (q r2_bins) >> 16), frequency bin of the gene = min(freq_bins - 1, floor(2 m freq_bins / N)) with m = min(c_g, N - c_g),
+ * hist[freq * r2_bins + r2] += 1, freq_sum_q[freq] += q, and the pair is strong when q >= strong_q.  Best tag of a gene: over its
+ * defined pairs the site with the largest q, ties to the lowest column (a gene whose every q is 0 reports its lowest defined
+ * site; one without a defined pair PS_GS_NONE, q 0, sign 0); of a site: the gene, likewise.  Every result but mean_r2 is an
+ * integer sum or a maximum under a strict order: nothing depends on the launch geometry, the bands, the sharding or the order of
+ * the individuals.  Limits: pop_size <= 65536, max_sites (or n_sites) + max_genes (or n_genes) <= 65536, each automatic cap and
+ * both minors >= 1, r2_bins >= 1, freq_bins >= 1, r2_bins x freq_bins <= 16384, 1 <= strong_q <= 65536; else PS_ERR_INVALID. */
+#define PS_GS_NONE 0xFFFFFFFFu
+typedef struct {
+    uint32_t r2_bins, freq_bins;
+    uint32_t site_min_minor, gene_min_minor;   /* automatic selection of a side: candidates have min(c, N - c) >= this */
+    uint32_t max_sites, max_genes;             /* automatic selection of a side: at most this many */
+    uint32_t strong_q;                         /* a pair with q >= strong_q is strong (32768: r^2 >= 0.5) */
+} ps_gs_params;
+typedef struct {
+    uint64_t pop_size, site_columns, gene_columns;
+    uint64_t site_candidates, gene_candidates;             /* C of an automatic side; the polymorphic entries of an explicit list */
+    uint64_t sites, genes;                                 /* Ms, Mg */
+    uint64_t pairs, defined_pairs, undefined_pairs;        /* pairs = Ms Mg = defined + undefined */
+    uint64_t four_gamete_pairs, complete_pairs, positive_pairs, negative_pairs;
+    uint64_t strong_pairs;                                 /* q >= strong_q */
+    uint64_t genes_tagged, sites_tagging;                  /* genes / sites whose best q >= strong_q */
+    uint64_t sum_q;
+    double mean_r2;                                        /* (double)sum_q / 65536.0 / (double)defined_pairs; 0.0 without defined pairs */
+    uint64_t r2_bins, freq_bins, site_min_minor, gene_min_minor, max_sites, max_genes, strong_q;
+} ps_gs_t;
+/* The per-locus arrays of one side, each NULL or with room for the side's cap (its n_ when explicit); the first Ms (Mg) entries
+ * are written: the column, its ones, the best partner's column (or PS_GS_NONE), its q, the locus' strong pairs, the sign of D
+ * with the best partner (-1 / 0 / +1). */
+typedef struct {
+    uint32_t *index, *count, *best, *best_q, *strong;
+    int32_t *best_sign;
+} ps_gs_side;
+/* The core handle and the accessory handle of the same individuals on one device (the reference has no such function;
+ * population.rs:544-751, :840-863).  sites == NULL / genes == NULL: that side is selected automatically.  site_out, gene_out: NULL
+ * or the arrays wanted.  hist: freq_bins x r2_bins values; freq_sum_q: freq_bins.  Genes are packed on the accessory handle's
+ * stream and sites on the core handle's, each behind its handle's queued work (a two-generation sweep launch included); changes
+ * no state.  PS_ERR_NO_DEVICE before anything else when no GPU is visible; a site shard fails with a message that points to
+ * ps_multi_gene_site_ld. */
+int ps_gene_site_ld(ps_population *core, ps_population *acc, const ps_gs_params *prm, const uint32_t *sites, uint32_t n_sites,
+                    const uint32_t *genes, uint32_t n_genes, ps_gs_t *out, const ps_gs_side *site_out, const ps_gs_side *gene_out,
+                    uint64_t *hist, uint64_t *freq_sum_q);
+/* The same for the two matrices of a simulation (the reference has no such function; population.rs:544-751, :840-863) */
+int ps_sim_gene_site_ld(ps_sim *s, const ps_gs_params *prm, const uint32_t *sites, uint32_t n_sites, const uint32_t *genes,
+                        uint32_t n_genes, ps_gs_t *out, const ps_gs_side *site_out, const ps_gs_side *gene_out, uint64_t *hist,
+                        uint64_t *freq_sum_q);
+/* The same for a sharded run (the reference has no such function; population.rs:544-751, :840-863): every shard counts, selects
+ * and packs its own sites, the bit rows travel to shard 0, whose accessory replica provides the genes and which contracts and
+ * bins; column indices are global. */
+int ps_multi_gene_site_ld(ps_multi *m, const ps_gs_params *prm, const uint32_t *sites, uint32_t n_sites, const uint32_t *genes,
+                          uint32_t n_genes, ps_gs_t *out, const ps_gs_side *site_out, const ps_gs_side *gene_out, uint64_t *hist,
+                          uint64_t *freq_sum_q);
+/* The per-pair rules and the best tags on the host alone (no device is touched; the reference has no such function;
+ * population.rs:544-751, :840-863): the two lists with strictly ascending columns and their counts, n11 of the n_genes x n_sites
+ * pairs, row-major (NULL without pairs).  The index and count members of the two sides are not written.  A count above pop_size,
+ * or an n11 that the two counts do not allow, is PS_ERR_INVALID.  The columns and the candidates of `out` are 0. */
+int ps_gene_site_from_counts(const uint32_t *site_index, const uint32_t *site_count, uint64_t n_sites, const uint32_t *gene_index,
+                             const uint32_t *gene_count, uint64_t n_genes, const uint32_t *n11, uint64_t pop_size,
+                             const ps_gs_params *prm, ps_gs_t *out, const ps_gs_side *site_out, const ps_gs_side *gene_out,
+                             uint64_t *hist, uint64_t *freq_sum_q);
+/* device ms of the last ps_gene_site_ld on this core handle (shard 0's after ps_multi_gene_site_ld; HIP events; the reference has
+ * no such function; population.rs:544-751): counts and selection of both sides, packing, the contraction, the pair statistics.
+ * PS_ERR_STATE before any call. */
+int ps_gene_site_ld_timing(ps_population *core, double *select_ms, double *pack_ms, double *counts_ms, double *stats_ms);
+
 /* Group differentiation (docs/GROUP_DIFFERENTIATION.md): what the labels of strain_clusters, the trees' clusters_at, the
  * lineages and the genealogy's clusters say about the matrices.  The reference has no such function (the counts are the grouped
  * form of population.rs:840-863).  Groups: a distinct label value with at least min_size members is a candidate, candidates are

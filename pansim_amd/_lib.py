@@ -163,6 +163,29 @@ class Ld(C.Structure):
                 + [(name, C.c_uint64) for name in ("r2_bins", "lag_bins", "min_minor", "max_loci")])
 
 
+PS_GS_NONE = 0xFFFFFFFF
+
+
+class GsParams(C.Structure):
+    """ps_gs_params: the bins, the automatic selection of both sides and the strong threshold of ps_gene_site_ld
+    (docs/GENE_SITE_ASSOCIATION.md)"""
+    _fields_ = [(name, C.c_uint32) for name in ("r2_bins", "freq_bins", "site_min_minor", "gene_min_minor", "max_sites", "max_genes", "strong_q")]
+
+
+class Gs(C.Structure):
+    """ps_gs_t: the summary of ps_gene_site_ld / ps_gene_site_from_counts"""
+    _fields_ = ([(name, C.c_uint64) for name in ("pop_size", "site_columns", "gene_columns", "site_candidates", "gene_candidates", "sites", "genes",
+                                                  "pairs", "defined_pairs", "undefined_pairs", "four_gamete_pairs", "complete_pairs",
+                                                  "positive_pairs", "negative_pairs", "strong_pairs", "genes_tagged", "sites_tagging", "sum_q")]
+                + [("mean_r2", C.c_double)]
+                + [(name, C.c_uint64) for name in ("r2_bins", "freq_bins", "site_min_minor", "gene_min_minor", "max_sites", "max_genes", "strong_q")])
+
+
+class GsSide(C.Structure):
+    """ps_gs_side: the per-locus arrays of one side of ps_gene_site_ld, any of them NULL"""
+    _fields_ = [(name, C.c_void_p) for name in ("index", "count", "best", "best_q", "strong", "best_sign")]
+
+
 class ClockParams(C.Structure):
     """ps_clock_params: the metric, bins and spans of ps_sim_clock_histogram (docs/GENEALOGY.md); a span of 0 = automatic"""
     _fields_ = [("metric", C.c_int32), ("time_bins", C.c_uint32), ("dist_bins", C.c_uint32), ("time_span", C.c_uint64),
@@ -362,6 +385,12 @@ SIGNATURES = {
     "ps_ld_select_loci": (_int, [_vp, _u64, _u64, _u32, _u32, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "ps_ld_from_counts": (_int, [_vp, _vp, _vp, _u64, _u64, C.POINTER(LdParams), C.POINTER(Ld), _vp, _vp]),
     "ps_locus_ld_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_gene_site_ld": (_int, [_vp, _vp, C.POINTER(GsParams), _vp, _u32, _vp, _u32, C.POINTER(Gs), C.POINTER(GsSide), C.POINTER(GsSide), _vp, _vp]),
+    "ps_sim_gene_site_ld": (_int, [_vp, C.POINTER(GsParams), _vp, _u32, _vp, _u32, C.POINTER(Gs), C.POINTER(GsSide), C.POINTER(GsSide), _vp, _vp]),
+    "ps_multi_gene_site_ld": (_int, [_vp, C.POINTER(GsParams), _vp, _u32, _vp, _u32, C.POINTER(Gs), C.POINTER(GsSide), C.POINTER(GsSide), _vp, _vp]),
+    "ps_gene_site_from_counts": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, C.POINTER(GsParams), C.POINTER(Gs), C.POINTER(GsSide),
+                                        C.POINTER(GsSide), _vp, _vp]),
+    "ps_gene_site_ld_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_groups_from_labels": (_int, [_vp, _u64, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
     **_run_forms("group_differentiation", [_vp, C.POINTER(DiffParams), C.POINTER(Diff)] + [_vp] * 12),
     "ps_differentiation_from_counts": (_int, [_vp, _u64, _u32, _vp, C.POINTER(Diff), _vp, _vp, _vp, _vp]),

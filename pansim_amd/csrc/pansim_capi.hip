@@ -188,7 +188,7 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
 // ms of the last call's timer groups (`timed`: a call has completed)
-enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_COUNT };
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_COUNT };
 struct readout_slot {
     void *d = nullptr;
     uint64_t cap = 0;       // (bytes)
@@ -340,6 +340,8 @@ struct ps_population {
     //                   counters (accessory handle: the same, then one chunk of expanded gene bytes); ms: schedule, core, genes
     //   PS_RO_TCMP      tree comparison (tree_compare.h), on whichever handle was asked: the words and the joint bins, the two sparse
     //                   tables, pb, the two info arrays, with triplets the u16 rank table; ms: tables, pairs
+    //   PS_RO_GS        gene-site association (gene_site_ld.h): summary words, frequency sums, bins, arg-max keys, strong counts, list,
+    //                   bit rows of genes then sites, landing rows, one band of n11; ms: select, pack, counts, stats
     readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
@@ -4981,6 +4983,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // linkage disequilibrium of loci (ps_locus_ld, ps_ld_select_loci, ps_ld_from_counts, ps_sim_* and ps_multi_*)
 #include "locus_ld.h"
+
+// gene-site association: r^2 of all accessory gene x core site pairs (ps_gene_site_ld, ps_gene_site_from_counts, ps_sim_* and ps_multi_*)
+#include "gene_site_ld.h"
 
 // group differentiation from labels (ps_group_differentiation, ps_groups_from_labels, ps_differentiation_from_counts, ps_sim_* and ps_multi_*)
 #include "group_differentiation.h"

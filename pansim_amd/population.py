@@ -997,6 +997,20 @@ class Population:
         """device ms of (counts and selection, packing, the contraction, the pair statistics) of the last locus_ld()"""
         return _timing(self._lib.ps_locus_ld_timing, 4, self._h)
 
+    def gene_site_ld(self, acc, r2_bins=64, freq_bins=1, site_min_minor=1, gene_min_minor=1, max_sites=4096, max_genes=4096, strong_q=32768,
+                     sites=None, genes=None):
+        """gene-site association of this core handle's sites with the genes of the accessory handle `acc` of the same individuals
+        (ps_gene_site_ld; docs/GENE_SITE_ASSOCIATION.md) -> a GeneSiteLd: r^2 over all (gene, site) pairs of the two selected
+        lists, binned by r^2 and the gene's minor frequency, and the best tag of every gene and site; `sites` / `genes`: an
+        explicit strictly ascending list of columns instead of that side's automatic selection"""
+        from .association import _gs_call, _gs_params
+        prm = _gs_params(r2_bins, freq_bins, site_min_minor, gene_min_minor, max_sites, max_genes, strong_q)
+        return _gs_call(self._lib.ps_gene_site_ld, prm, sites, genes, self._h, acc._h)
+
+    def gene_site_ld_timing(self):
+        """device ms of (counts and selection, packing, the contraction, the pair statistics) of the last gene_site_ld()"""
+        return _timing(self._lib.ps_gene_site_ld_timing, 4, self._h)
+
     def core_diversity_timing(self):
         """device ms of the counts kernel of the last site_allele_counts() / core_diversity() call"""
         ms = C.c_double()

@@ -193,7 +193,25 @@ class _Readouts:
         return _ld_call(self._entry("locus_ld"), _ld_params(r2_bins, lag_bins, min_minor, max_loci), loci, self._h, m)
 
 
-class Simulation(_Readouts):
+class _Associations:
+    """The read-outs that pair the run's two matrices along the axis of LOCI, written once for both forms of a run as
+    `_Readouts` writes the others (it resolves them through the same `_entry`)."""
+
+    def gene_site_ld(self, r2_bins=64, freq_bins=1, site_min_minor=1, gene_min_minor=1, max_sites=4096, max_genes=4096, strong_q=32768,
+                     sites=None, genes=None):
+        """Population.gene_site_ld() of the run's two matrices: every shard selects and packs its own sites, shard 0 adds the
+        genes of its replica, contracts and bins; columns are global (ps_sim_gene_site_ld / ps_multi_gene_site_ld;
+        docs/GENE_SITE_ASSOCIATION.md) -> a GeneSiteLd"""
+        from .association import _gs_call, _gs_params
+        prm = _gs_params(r2_bins, freq_bins, site_min_minor, gene_min_minor, max_sites, max_genes, strong_q)
+        return _gs_call(self._entry("gene_site_ld"), prm, sites, genes, self._h)
+
+    def gene_site_ld_timing(self):
+        """device ms of (counts and selection, packing, the contraction, the pair statistics) of the last gene_site_ld()"""
+        return self._timed.core_genome.gene_site_ld_timing()
+
+
+class Simulation(_Readouts, _Associations):
     """State of main() between main.rs:259 and :553 for one process (one GPU)."""
     _prefix = "ps_sim_"
     _core_width = property(lambda self: self.core_genome.ncols)       # the shard's columns when it is a shard
@@ -348,7 +366,7 @@ class Simulation(_Readouts):
             self.pan_genome.write(outpref)
 
 
-class MultiSimulation(_Readouts):
+class MultiSimulation(_Readouts, _Associations):
     """The run sharded by core site inside ONE process (ps_multi): shard k on HIP device devices[k]
     (ordinals may repeat), one host thread per shard inside each call; results equal the unsharded run."""
     _prefix = "ps_multi_"
