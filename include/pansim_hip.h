@@ -983,6 +983,67 @@ int ps_gene_site_from_counts(const uint32_t *site_index, const uint32_t *site_co
  * PS_ERR_STATE before any call. */
 int ps_gene_site_ld_timing(ps_population *core, double *select_ms, double *pack_ms, double *counts_ms, double *stats_ms);
 
+/* Core allele profiles, cgMLST (docs/ALLELE_PROFILES.md).  The reference has no such function (the sequences are the rows of the
+ * core matrix, population.rs:164-170).  The L core sites are cut into n_loci loci: without `bounds` locus g is the sites
+ * [floor(g L / n_loci), floor((g + 1) L / n_loci)) (n_loci <= L); with `bounds` (n_loci + 1 values, strictly ascending, the last
+ * <= L) locus g is [bounds[g], bounds[g + 1]) and the sites outside belong to no locus.  Two individuals carry the same allele of
+ * a locus iff their bytes agree at every site of it (bytes outside 1 / 2 / 4 / 8 are just other values); the alleles of a locus
+ * are numbered 0 .. A_g - 1 by first appearance in output row order (the reference's row order, as the labels of
+ * ps_strain_clusters).  locus_alleles[g] = A_g, locus_same_pairs[g] = the pairs of individuals with the same allele.  Per pair
+ * i < j, d = the loci at which the numbers differ: hist[floor(d dist_bins / (n_loci + 1))] += 1, sum_d, min_d, max_d,
+ * identical_pairs (d = 0), edges (d <= complex_max).  st[k]: the smallest output row with the profile of k (the sequence type);
+ * complex_of[k]: the smallest output row of k's connected component of the graph d <= complex_max (single linkage).  The device
+ * compares 128-bit keyed fingerprints of the loci (key_seed; key_bits < 64 shortens the keys, for tests) and then verifies every
+ * class byte for byte: a fingerprint collision ends the call with PS_ERR_STATE and changes no result.  Every result but
+ * mean_distance is an exact integer and depends on the sequences and the row order only.  Limits, else PS_ERR_INVALID: 2 <=
+ * pop_size <= 65536, 1 <= n_loci <= 65535, n_loci x pop_size <= 2^30, 1 <= dist_bins <= 16384, complex_max <= n_loci, 1 <=
+ * key_bits <= 64. */
+typedef struct {
+    uint32_t n_loci, dist_bins, complex_max, key_bits;
+    uint64_t key_seed;
+} ps_mlst_params;
+typedef struct {
+    uint64_t pop_size, pairs, core_sites;
+    uint64_t loci, sites_covered;                              /* sites_covered: the sites inside a locus */
+    uint64_t alleles_total, max_alleles, monomorphic_loci;     /* the sum and the maximum of A_g; the loci with A_g = 1 */
+    uint64_t sequence_types, singleton_sts, largest_st;
+    uint64_t identical_pairs;                                  /* = the sum over sequence types of size (size - 1) / 2 */
+    uint64_t complexes, largest_complex;
+    uint64_t edges;
+    uint64_t sum_d, min_d, max_d;                              /* sum_d = the sum over loci of (pairs - locus_same_pairs) */
+    double mean_distance;                                      /* (double)sum_d / (double)pairs / (double)loci */
+    uint64_t dist_bins, complex_max;
+    uint64_t rounds;                                           /* label rounds taken on the device (0 from the host form) */
+} ps_mlst_t;
+/* A core handle that holds all sites (the reference has no such function; population.rs:164-170).  bounds: NULL or n_loci + 1
+ * values.  locus_alleles: n_loci u32; locus_same_pairs: n_loci u64; st, complex_of: pop_size u32; hist: dist_bins u64; profiles:
+ * NULL or pop_size x n_loci u16, individual-major.  Runs on the handle's stream behind its queued work (a two-generation sweep
+ * launch included); changes no state; the tuning key "mlst_band" forces the loci per band of the fingerprint table.
+ * PS_ERR_NO_DEVICE before anything else when no GPU is visible; a site shard fails with a message that points to
+ * ps_multi_allele_profiles. */
+int ps_allele_profiles(ps_population *core, const ps_mlst_params *prm, const uint64_t *bounds, ps_mlst_t *out, uint32_t *locus_alleles,
+                       uint64_t *locus_same_pairs, uint32_t *st, uint32_t *complex_of, uint64_t *hist, uint16_t *profiles);
+/* The same for the core matrix of a simulation (the reference has no such function; population.rs:164-170); the run is not
+ * synchronised. */
+int ps_sim_allele_profiles(ps_sim *s, const ps_mlst_params *prm, const uint64_t *bounds, ps_mlst_t *out, uint32_t *locus_alleles,
+                           uint64_t *locus_same_pairs, uint32_t *st, uint32_t *complex_of, uint64_t *hist, uint16_t *profiles);
+/* The same for a sharded run (the reference has no such function; population.rs:164-170): every shard fingerprints the sites it
+ * holds (a locus may straddle shards), the tables add on shard 0, which numbers the alleles and runs the pairs; every shard
+ * verifies its own sites. */
+int ps_multi_allele_profiles(ps_multi *m, const ps_mlst_params *prm, const uint64_t *bounds, ps_mlst_t *out, uint32_t *locus_alleles,
+                             uint64_t *locus_same_pairs, uint32_t *st, uint32_t *complex_of, uint64_t *hist, uint16_t *profiles);
+/* Everything above from any table of allele ids on the host alone (no device is touched; the reference has no such function;
+ * population.rs:164-170): alleles = pop_size x n_loci u32, individual-major, in output row order; the ids of a locus need not be
+ * dense and are renumbered by first appearance.  core_sites and sites_covered of `out` are 0; key_bits and key_seed are not
+ * used (key_bits is still checked). */
+int ps_profiles_from_alleles(const uint32_t *alleles, uint64_t pop_size, const ps_mlst_params *prm, ps_mlst_t *out, uint32_t *locus_alleles,
+                             uint64_t *locus_same_pairs, uint32_t *st, uint32_t *complex_of, uint64_t *hist, uint16_t *profiles);
+/* device ms of the last ps_allele_profiles on this core handle (shard 0's after ps_multi_allele_profiles; HIP events; the
+ * reference has no such function; population.rs:164-170): the fingerprints, the allele numbers, the verification, the pairs, the
+ * label rounds.  PS_ERR_STATE before any call. */
+int ps_allele_profiles_timing(ps_population *core, double *fingerprint_ms, double *canon_ms, double *verify_ms, double *pairs_ms,
+                              double *labels_ms);
+
 /* Group differentiation (docs/GROUP_DIFFERENTIATION.md): what the labels of strain_clusters, the trees' clusters_at, the
  * lineages and the genealogy's clusters say about the matrices.  The reference has no such function (the counts are the grouped
  * form of population.rs:840-863).  Groups: a distinct label value with at least min_size members is a candidate, candidates are

@@ -186,6 +186,25 @@ class GsSide(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("index", "count", "best", "best_q", "strong", "best_sign")]
 
 
+class MlstParams(C.Structure):
+    """ps_mlst_params: the loci, the bins, the complex threshold and the fingerprint keys of ps_allele_profiles
+    (docs/ALLELE_PROFILES.md)"""
+    _fields_ = [(name, C.c_uint32) for name in ("n_loci", "dist_bins", "complex_max", "key_bits")] + [("key_seed", C.c_uint64)]
+
+
+class Mlst(C.Structure):
+    """ps_mlst_t: the summary of ps_allele_profiles / ps_profiles_from_alleles"""
+    _fields_ = ([(name, C.c_uint64) for name in ("pop_size", "pairs", "core_sites", "loci", "sites_covered", "alleles_total", "max_alleles",
+                                                  "monomorphic_loci", "sequence_types", "singleton_sts", "largest_st", "identical_pairs",
+                                                  "complexes", "largest_complex", "edges", "sum_d", "min_d", "max_d")]
+                + [("mean_distance", C.c_double)]
+                + [(name, C.c_uint64) for name in ("dist_bins", "complex_max", "rounds")])
+
+
+# &params, bounds | &summary, locus_alleles, locus_same_pairs, st, complex, hist, profiles: the tail of every ps_*allele_profiles entry
+_MLST = [C.POINTER(MlstParams), C.c_void_p, C.POINTER(Mlst)] + [C.c_void_p] * 6
+
+
 class ClockParams(C.Structure):
     """ps_clock_params: the metric, bins and spans of ps_sim_clock_histogram (docs/GENEALOGY.md); a span of 0 = automatic"""
     _fields_ = [("metric", C.c_int32), ("time_bins", C.c_uint32), ("dist_bins", C.c_uint32), ("time_span", C.c_uint64),
@@ -391,6 +410,11 @@ SIGNATURES = {
     "ps_gene_site_from_counts": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, C.POINTER(GsParams), C.POINTER(Gs), C.POINTER(GsSide),
                                         C.POINTER(GsSide), _vp, _vp]),
     "ps_gene_site_ld_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_allele_profiles": (_int, [_vp] + _MLST),
+    "ps_sim_allele_profiles": (_int, [_vp] + _MLST),
+    "ps_multi_allele_profiles": (_int, [_vp] + _MLST),
+    "ps_profiles_from_alleles": (_int, [_vp, _u64, C.POINTER(MlstParams), C.POINTER(Mlst)] + [_vp] * 6),
+    "ps_allele_profiles_timing": (_int, [_vp] + [C.POINTER(_f64)] * 5),
     "ps_groups_from_labels": (_int, [_vp, _u64, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
     **_run_forms("group_differentiation", [_vp, C.POINTER(DiffParams), C.POINTER(Diff)] + [_vp] * 12),
     "ps_differentiation_from_counts": (_int, [_vp, _u64, _u32, _vp, C.POINTER(Diff), _vp, _vp, _vp, _vp]),

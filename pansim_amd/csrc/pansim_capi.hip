@@ -188,11 +188,11 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
 // ms of the last call's timer groups (`timed`: a call has completed)
-enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_COUNT };
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_COUNT };
 struct readout_slot {
     void *d = nullptr;
     uint64_t cap = 0;       // (bytes)
-    double ms[4] = {};
+    double ms[5] = {};
     bool timed = false;
 };
 
@@ -342,8 +342,12 @@ struct ps_population {
     //                   tables, pb, the two info arrays, with triplets the u16 rank table; ms: tables, pairs
     //   PS_RO_GS        gene-site association (gene_site_ld.h): summary words, frequency sums, bins, arg-max keys, strong counts, list,
     //                   bit rows of genes then sites, landing rows, one band of n11; ms: select, pack, counts, stats
+    //   PS_RO_MLST      core allele profiles (allele_profiles.h): words, bins, allele numbers, adjacency bit matrix (zeroed per call),
+    //                   per-locus counts, the two label arrays, `changed`, bounds, one band of fingerprints, landing table, one band
+    //                   of representatives, the tables of the canonicalise workgroups; ms: fingerprint, canon, verify, pairs, labels
     readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
+    uint32_t mlst_band = 0;                 // loci per band of the fingerprint table of ps_allele_profiles, 0 = choose ("mlst_band")
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
     unsigned long long *h_stamps = nullptr, *d_stamps = nullptr;   // diagnostic phase stamps
 };
@@ -660,6 +664,9 @@ extern "C" int ps_set_tuning(ps_population *p, const char *key, int64_t value)
     } else if (k == "ld_band") {
         if (value < 0 || value > 65536) return ps_fail(PS_ERR_INVALID, "ld_band must be 0 (choose)..65536 rows of loci");
         p->ld_band = (uint32_t)value;
+    } else if (k == "mlst_band") {
+        if (value < 0 || value > 65535) return ps_fail(PS_ERR_INVALID, "mlst_band must be 0 (choose)..65535 loci");
+        p->mlst_band = (uint32_t)value;
     } else if (k == "core_davg_band") {
         if (value < 0 || value > (1ll << 31)) return ps_fail(PS_ERR_INVALID, "core_davg_band must be 0 (choose)..2^31 rows");
         p->core_davg_band = (uint32_t)value;
@@ -4986,6 +4993,9 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // gene-site association: r^2 of all accessory gene x core site pairs (ps_gene_site_ld, ps_gene_site_from_counts, ps_sim_* and ps_multi_*)
 #include "gene_site_ld.h"
+
+// core allele profiles, cgMLST: sequence types, clonal complexes and allele distances (ps_allele_profiles, ps_profiles_from_alleles, ps_sim_* and ps_multi_*)
+#include "allele_profiles.h"
 
 // group differentiation from labels (ps_group_differentiation, ps_groups_from_labels, ps_differentiation_from_counts, ps_sim_* and ps_multi_*)
 #include "group_differentiation.h"

@@ -44,10 +44,10 @@ static int scratch_get(readout_slot &ro, uint64_t bytes, uint8_t **base, const c
     return PS_OK;
 }
 
-// HIP events around pieces of work in up to four groups, all on one device; the totals once the streams have been synchronised
+// HIP events around pieces of work in up to five groups, all on one device; the totals once the streams have been synchronised
 struct event_timer {
     std::vector<hipEvent_t> pool;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> timers[4];
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> timers[5];
     ~event_timer() { for (hipEvent_t e : pool) (void)hipEventDestroy(e); }
     int make(hipEvent_t *out)
     {

@@ -1011,6 +1011,21 @@ class Population:
         """device ms of (counts and selection, packing, the contraction, the pair statistics) of the last gene_site_ld()"""
         return _timing(self._lib.ps_gene_site_ld_timing, 4, self._h)
 
+    def allele_profiles(self, n_loci, bounds=None, dist_bins=None, complex_max=0, want_profiles=True, key_seed=0, key_bits=64):
+        """core allele profiles (cgMLST) of this core handle (ps_allele_profiles; docs/ALLELE_PROFILES.md) -> an AlleleProfiles:
+        the sites are cut into `n_loci` loci (evenly, or at the n_loci + 1 sites of `bounds`), every distinct sequence of a locus
+        is an allele, and two individuals are as far apart as they have loci with different alleles; the sequence types, the
+        single-linkage complexes at `complex_max` loci and the histogram of all pairs (`dist_bins`: n_loci + 1, capped at 16384,
+        when None)"""
+        from .mlst import _mlst_device_call
+        return _mlst_device_call(self._lib.ps_allele_profiles, self._h, self.size, n_loci, bounds, dist_bins, complex_max, want_profiles, key_seed,
+                                 key_bits)
+
+    def allele_profiles_timing(self):
+        """device ms of (the fingerprints, the allele numbers, the verification, the pairs, the label rounds) of the last
+        allele_profiles()"""
+        return _timing(self._lib.ps_allele_profiles_timing, 5, self._h)
+
     def core_diversity_timing(self):
         """device ms of the counts kernel of the last site_allele_counts() / core_diversity() call"""
         ms = C.c_double()

@@ -211,7 +211,25 @@ class _Associations:
         return self._timed.core_genome.gene_site_ld_timing()
 
 
-class Simulation(_Readouts, _Associations):
+class _Profiles:
+    """The read-outs that cut the core matrix into loci, written once for both forms of a run as `_Readouts` writes the others
+    (it resolves them through the same `_entry`)."""
+
+    def allele_profiles(self, n_loci, bounds=None, dist_bins=None, complex_max=0, want_profiles=True, key_seed=0, key_bits=64):
+        """Population.allele_profiles() of the run's core matrix, all sites: every shard fingerprints the sites it holds, shard 0
+        adds the tables, numbers the alleles and runs the pairs (ps_sim_allele_profiles / ps_multi_allele_profiles;
+        docs/ALLELE_PROFILES.md) -> an AlleleProfiles"""
+        from .mlst import _mlst_device_call
+        return _mlst_device_call(self._entry("allele_profiles"), self._h, self.params.pop_size, n_loci, bounds, dist_bins, complex_max,
+                                 want_profiles, key_seed, key_bits)
+
+    def allele_profiles_timing(self):
+        """device ms of (the fingerprints, the allele numbers, the verification, the pairs, the label rounds) of the last
+        allele_profiles()"""
+        return self._timed.core_genome.allele_profiles_timing()
+
+
+class Simulation(_Readouts, _Associations, _Profiles):
     """State of main() between main.rs:259 and :553 for one process (one GPU)."""
     _prefix = "ps_sim_"
     _core_width = property(lambda self: self.core_genome.ncols)       # the shard's columns when it is a shard
@@ -366,7 +384,7 @@ class Simulation(_Readouts, _Associations):
             self.pan_genome.write(outpref)
 
 
-class MultiSimulation(_Readouts, _Associations):
+class MultiSimulation(_Readouts, _Associations, _Profiles):
     """The run sharded by core site inside ONE process (ps_multi): shard k on HIP device devices[k]
     (ordinals may repeat), one host thread per shard inside each call; results equal the unsharded run."""
     _prefix = "ps_multi_"
