@@ -1044,6 +1044,48 @@ int ps_profiles_from_alleles(const uint32_t *alleles, uint64_t pop_size, const p
 int ps_allele_profiles_timing(ps_population *core, double *fingerprint_ms, double *canon_ms, double *verify_ms, double *pairs_ms,
                               double *labels_ms);
 
+/* Isolate samples (docs/ISOLATE_SAMPLES.md): some rows of one or more populations as a NEW handle on the device, so that every
+ * read-out of this header answers for a sample (a few hundred isolates, a bootstrap replicate, serial samples pooled over time) as
+ * it answers for a population.  The reference has no such function (its only sample is the random pairs of main.rs:413-427; the
+ * rows are those of population.rs:164-170).  The new handle is a full, independent ps_population on the device of parts[0] with a
+ * stream of its own, made as ps_population_create makes one: cfg of parts[0] with pop_size = the sum of n_rows, no rates set,
+ * output row order = internal order, row j = the j-th requested row; nibble / one-hot safety = the AND over the parts; the pad
+ * bytes of the core rows and the pad bits of the accessory rows are zero.  It is destroyed with ps_population_destroy, in any
+ * order relative to its sources.  A source is read on its own stream behind whatever is queued there (a two-generation sweep
+ * launch included) and never written: its matrix, edit epoch, cached pair lists and read-out scratch do not change, and a run
+ * continues bit for bit.  The call returns with the gathers complete.  PS_ERR_INVALID, naming the field or index, `*out` null: a
+ * null argument, n_parts = 0, the sum of n_rows = 0 or beyond what ps_population_create accepts, a row >= its part's pop_size,
+ * parts that are not all core or all accessory, that differ in ncols, col_offset, global_cols or core_genes, or that are on
+ * different devices.  The core matrix is gathered within every site row by core_gather_rows_kernel, which stages the source row in
+ * LDS or, for source rows beyond 64 KiB and for 48 n < pitch, loads the bytes from global memory; the tuning key "gather_form"
+ * of the SOURCE handle forces the form (0 = choose, 1 = LDS, 2 = direct). */
+/* rows of parts[k] (rows == NULL or rows[k] == NULL: all of them, n_rows[k] = that part's pop_size), in that handle's OUTPUT row
+ * order as every read-out numbers rows; rows may repeat (the reference has no such function; population.rs:164-170) */
+int ps_population_pool(ps_population *const *parts, const uint32_t *const *rows, const uint64_t *n_rows, uint32_t n_parts,
+                       ps_population **out);
+/* = the pool of one part (the reference has no such function; population.rs:164-170) */
+int ps_population_subset(ps_population *src, const uint32_t *rows, uint64_t n_rows, ps_population **out);
+/* the core and the accessory sample of a run from the same rows; either out pointer may be NULL; the run is not synchronised
+ * (the reference has no such function; population.rs:164-170) */
+int ps_sim_subset(ps_sim *s, const uint32_t *rows, uint64_t n_rows, ps_population **core_out, ps_population **acc_out);
+/* the same for a sharded run (the reference has no such function; population.rs:164-170): the core sample is a WHOLE handle
+ * (col_offset 0, ncols = global_cols) on shard 0's device -- every shard gathers the sites it holds, whose block lands
+ * contiguously at col_offset x pitch, directly on shard 0's device and through a peer copy from another; the accessory sample
+ * comes from shard 0's replica */
+int ps_multi_subset(ps_multi *m, const uint32_t *rows, uint64_t n_rows, ps_population **core_out, ps_population **acc_out);
+/* device ms of the gather(s) that filled `made` (HIP events on the sources' streams, the peer copies of shards included; the
+ * reference has no such function; population.rs:164-170).  PS_ERR_STATE on a handle that none of the calls above made. */
+int ps_population_subset_timing(ps_population *made, double *gather_ms);
+/* Host only, no device: the comb of ps_sim_genealogy (docs/GENEALOGY.md) restricted to `rows` (n_rows >= 1 output rows below n;
+ * they may repeat).  The reference has no such function (the parents are the draws of population.rs:443).  The positions are
+ * walked in ascending order and those whose row is in `rows` kept; a row asked for several times gives several entries at its
+ * position, in the order of their indices in `rows`, with coalescence time 0 between them.  order_out (n_rows u32): the INDEX IN
+ * `rows` of every kept entry, which is its row in the handle ps_sim_subset makes from the same rows; coal_out (n_rows - 1 u32):
+ * the maximum of coal between two neighbouring kept entries (PS_GEN_BEYOND is the largest value).  So for all a, b:
+ * pair(restricted, a, b) == pair(full, rows[a], rows[b]). */
+int ps_genealogy_restrict(const uint32_t *order, const uint32_t *coal, uint64_t n, const uint32_t *rows, uint64_t n_rows,
+                          uint32_t *order_out, uint32_t *coal_out);
+
 /* Group differentiation (docs/GROUP_DIFFERENTIATION.md): what the labels of strain_clusters, the trees' clusters_at, the
  * lineages and the genealogy's clusters say about the matrices.  The reference has no such function (the counts are the grouped
  * form of population.rs:840-863).  Groups: a distinct label value with at least min_size members is a candidate, candidates are

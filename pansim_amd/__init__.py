@@ -11,6 +11,7 @@ from .population import (DistanceHistogram, GroupDifferentiation, LinkageTree, N
 from .linkage import LocusLd, ld_from_counts, ld_select_loci  # noqa: F401
 from .association import GeneSiteLd, gene_site_from_counts  # noqa: F401
 from .mlst import AlleleProfiles, profiles_from_alleles  # noqa: F401
+from .samples import genealogy_restrict, pool  # noqa: F401
 from .genealogy import (PS_GEN_BEYOND, ClockHistogram, GenealogyResult, clock_from_counts, genealogy_clusters, genealogy_newick,  # noqa: F401
                         genealogy_pair, genealogy_pairs)
 from .parsimony import (PS_PARS_BINS, PS_PARS_MAX_POP, TreeParsimony, merges_from_genealogy, merges_from_tree, parsimony_from_rows,  # noqa: F401

@@ -415,6 +415,12 @@ SIGNATURES = {
     "ps_multi_allele_profiles": (_int, [_vp] + _MLST),
     "ps_profiles_from_alleles": (_int, [_vp, _u64, C.POINTER(MlstParams), C.POINTER(Mlst)] + [_vp] * 6),
     "ps_allele_profiles_timing": (_int, [_vp] + [C.POINTER(_f64)] * 5),
+    "ps_population_pool": (_int, [_vp, _vp, _vp, _u32, C.POINTER(_vp)]),
+    "ps_population_subset": (_int, [_vp, _vp, _u64, C.POINTER(_vp)]),
+    "ps_sim_subset": (_int, [_vp, _vp, _u64, C.POINTER(_vp), C.POINTER(_vp)]),
+    "ps_multi_subset": (_int, [_vp, _vp, _u64, C.POINTER(_vp), C.POINTER(_vp)]),
+    "ps_population_subset_timing": (_int, [_vp, C.POINTER(_f64)]),
+    "ps_genealogy_restrict": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp]),
     "ps_groups_from_labels": (_int, [_vp, _u64, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
     **_run_forms("group_differentiation", [_vp, C.POINTER(DiffParams), C.POINTER(Diff)] + [_vp] * 12),
     "ps_differentiation_from_counts": (_int, [_vp, _u64, _u32, _vp, C.POINTER(Diff), _vp, _vp, _vp, _vp]),

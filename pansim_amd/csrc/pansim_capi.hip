@@ -348,6 +348,11 @@ struct ps_population {
     readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
     uint32_t mlst_band = 0;                 // loci per band of the fingerprint table of ps_allele_profiles, 0 = choose ("mlst_band")
+    // isolate samples (isolate_samples.h): on a source, the form of the core gather; on a handle that ps_population_pool / _subset
+    // made, the device ms of the gathers that filled it
+    int gather_form = 0;                    // 0 = choose, 1 = source rows staged in LDS, 2 = bytes loaded from global memory ("gather_form")
+    double sample_ms = 0.0;
+    bool sample_timed = false;
     uint32_t *h_flag = nullptr, *d_flag = nullptr;   // host-mapped sticky device error word
     unsigned long long *h_stamps = nullptr, *d_stamps = nullptr;   // diagnostic phase stamps
 };
@@ -459,6 +464,7 @@ extern "C" void ps_population_destroy(ps_population *p)
     delete p;
 }
 
+// init_vec == nullptr (isolate_samples.h only; ps_population_create refuses it): the matrix is left for the caller to fill
 static int pop_create_impl(const ps_config *cfg, const uint8_t *init_vec, ps_population *p)
 {
     int ndev = 0;
@@ -522,7 +528,7 @@ static int pop_create_impl(const ps_config *cfg, const uint8_t *init_vec, ps_pop
     HIPCHK(hipHostGetDevicePointer((void **)&p->d_flag, p->h_flag, 0));
     uint8_t *d_vec = nullptr;
     HIPCHK(hipMalloc(&d_vec, std::max<uint64_t>(C, 1)));
-    if (C) HIPCHK(hipMemcpyAsync(d_vec, init_vec, C, hipMemcpyHostToDevice, p->stream));
+    if (C && init_vec) HIPCHK(hipMemcpyAsync(d_vec, init_vec, C, hipMemcpyHostToDevice, p->stream));
     if (cfg->core) {
         p->pitch = (uint32_t)((N + 127) / 128 * 128);
         p->cpr = p->pitch / 16;
@@ -537,7 +543,7 @@ static int pop_create_impl(const ps_config *cfg, const uint8_t *init_vec, ps_pop
             HIPCHK(hipMemsetAsync(p->d_work, 0, 2 * nctr * 128 + 256, p->stream));
             p->work_flags_ofs = (uint32_t)(2 * nctr * 32);
         }
-        if (C) {
+        if (C && init_vec) {
             const uint64_t total = C * p->cpr;
             const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 65536);
             core_init_kernel<<<blocks, 256, 0, p->stream>>>(p->state, d_vec, (uint32_t)N, p->pitch,
@@ -559,7 +565,7 @@ static int pop_create_impl(const ps_config *cfg, const uint8_t *init_vec, ps_pop
         HIPCHK(hipMalloc(&p->d_num_genes, std::max<uint64_t>(N, 1) * sizeof(int32_t)));
         HIPCHK(hipMalloc(&p->d_logw, std::max<uint64_t>(N, 1) * sizeof(double)));
         const uint64_t total = (uint64_t)p->d.G * p->d.W + (uint64_t)p->d.N * p->d.GW;
-        if (total)
+        if (total && init_vec)
             acc_init_kernel<<<(uint32_t)((total + 255) / 256), 256, 0, p->stream>>>(p->G[0], p->I[0],
                                                                                 d_vec, p->d);
         p->g_valid = true;
@@ -667,6 +673,9 @@ extern "C" int ps_set_tuning(ps_population *p, const char *key, int64_t value)
     } else if (k == "mlst_band") {
         if (value < 0 || value > 65535) return ps_fail(PS_ERR_INVALID, "mlst_band must be 0 (choose)..65535 loci");
         p->mlst_band = (uint32_t)value;
+    } else if (k == "gather_form") {
+        if (value < 0 || value > 2) return ps_fail(PS_ERR_INVALID, "gather_form must be 0 (choose), 1 (source rows staged in LDS) or 2 (bytes loaded from global memory)");
+        p->gather_form = (int)value;
     } else if (k == "core_davg_band") {
         if (value < 0 || value > (1ll << 31)) return ps_fail(PS_ERR_INVALID, "core_davg_band must be 0 (choose)..2^31 rows");
         p->core_davg_band = (uint32_t)value;
@@ -4996,6 +5005,11 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // core allele profiles, cgMLST: sequence types, clonal complexes and allele distances (ps_allele_profiles, ps_profiles_from_alleles, ps_sim_* and ps_multi_*)
 #include "allele_profiles.h"
+
+// isolate samples: rows of one or more populations gathered into a new handle on the device (ps_population_pool, ps_population_subset,
+// ps_sim_subset, ps_multi_subset, ps_genealogy_restrict)
+#include "sample_kernels.h"
+#include "isolate_samples.h"
 
 // group differentiation from labels (ps_group_differentiation, ps_groups_from_labels, ps_differentiation_from_counts, ps_sim_* and ps_multi_*)
 #include "group_differentiation.h"

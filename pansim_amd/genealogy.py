@@ -73,6 +73,17 @@ class GenealogyResult:
     def newick(self):
         return genealogy_newick(self.order, self.coal)
 
+    def restrict(self, rows):
+        """the genealogy of the sample `rows` of this generation (ps_genealogy_restrict; host only) -> a GenealogyResult over
+        the rows of the handle `subset(rows)` makes: pair(a, b) of the result == pair(rows[a], rows[b]) of this one; pop_size,
+        roots and tmrca follow from the restricted comb (docs/GENEALOGY.md), generation, capacity and depth are inherited"""
+        from .samples import genealogy_restrict
+        order, coal = genealogy_restrict(self.order, self.coal, rows)
+        g = Genealogy(**{name: getattr(self, name) for name in self.FIELDS})
+        beyond = int((coal == PS_GEN_BEYOND).sum())
+        g.pop_size, g.roots, g.tmrca = order.size, 1 + beyond, 0 if beyond or not coal.size else int(coal.max())
+        return GenealogyResult(g, order, coal)
+
     def merges(self):
         """(left, right, height): the comb as a merge list in scipy's numbering, equal times resolved left to right
         (ps_merges_from_genealogy); `tree_parsimony(*merges()[:2])`"""

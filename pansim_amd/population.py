@@ -1026,6 +1026,20 @@ class Population:
         allele_profiles()"""
         return _timing(self._lib.ps_allele_profiles_timing, 5, self._h)
 
+    def subset(self, rows=None):
+        """the rows `rows` of this population (output rows as every read-out numbers them; they may repeat; None = all) as a new,
+        owned Population on the device, to which every read-out applies (ps_population_subset; docs/ISOLATE_SAMPLES.md); this
+        population is read, not changed"""
+        from .samples import _rows, _wrap
+        r, h = _rows(rows), C.c_void_p()
+        n = self.size if r is None else r.size
+        check(self._lib.ps_population_subset(self._h, _ptr(r), n, C.byref(h)))
+        return _wrap(self, h, n)
+
+    def subset_timing(self):
+        """device ms of the gather(s) that filled this population, which subset() or pool() made"""
+        return _timing(self._lib.ps_population_subset_timing, 1, self._h)[0]
+
     def core_diversity_timing(self):
         """device ms of the counts kernel of the last site_allele_counts() / core_diversity() call"""
         ms = C.c_double()

@@ -229,7 +229,20 @@ class _Profiles:
         return self._timed.core_genome.allele_profiles_timing()
 
 
-class Simulation(_Readouts, _Associations, _Profiles):
+class _Samples:
+    """Isolate samples of a run, written once for both of its forms as `_Readouts` writes the read-outs (it resolves them through
+    the same `_entry`)."""
+
+    def subset(self, rows=None):
+        """the rows `rows` (output rows as every read-out numbers them; they may repeat; None = all) of the run's two matrices as
+        two new, owned Populations on the device -> (core, acc), to which every read-out of Population applies; the core sample
+        of a sharded run holds all sites, on shard 0's device (ps_sim_subset / ps_multi_subset; docs/ISOLATE_SAMPLES.md).  The
+        run is not synchronised and continues bit for bit."""
+        from .samples import _run_subset
+        return _run_subset(self._entry("subset"), self, rows)
+
+
+class Simulation(_Readouts, _Associations, _Profiles, _Samples):
     """State of main() between main.rs:259 and :553 for one process (one GPU)."""
     _prefix = "ps_sim_"
     _core_width = property(lambda self: self.core_genome.ncols)       # the shard's columns when it is a shard
@@ -384,7 +397,7 @@ class Simulation(_Readouts, _Associations, _Profiles):
             self.pan_genome.write(outpref)
 
 
-class MultiSimulation(_Readouts, _Associations, _Profiles):
+class MultiSimulation(_Readouts, _Associations, _Profiles, _Samples):
     """The run sharded by core site inside ONE process (ps_multi): shard k on HIP device devices[k]
     (ordinals may repeat), one host thread per shard inside each call; results equal the unsharded run."""
     _prefix = "ps_multi_"
