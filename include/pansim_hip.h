@@ -693,6 +693,69 @@ int ps_upgma_newick(const uint32_t *left, const uint32_t *right, const uint64_t 
  * PS_ERR_STATE before any call. */
 int ps_upgma_tree_timing(ps_population *core, double *counts_ms, double *store_ms, double *rounds_ms);
 
+/* Neighbour-joining tree (Saitou & Nei 1987 in the Studier-Keppler form; docs/NEIGHBOUR_JOINING.md): the tree of ALL N individuals
+ * from one distance without the assumption of a clock -- it recovers any additive (tree) metric exactly.  The reference has no
+ * such function: it writes a SAMPLE of pairs as text (population.rs:787-837), from which no tree can be built.  The metrics are
+ * those of the linkage tree (ps_tree_params as it is); every distance is an IEEE-754 binary64: core metric d = (double)(h / 2),
+ * an exact integer in differing sites; accessory metric d = (double)a / (double)b with a = U - I and b = U + core_genes, one
+ * correctly rounded division.  A node's id is the smallest row among its leaves.  Start: r_i = the sum of d(i, k) over k != i,
+ * accumulated from +0.0 in ascending row k.  While n > 2 active nodes are left: over all pairs, lo the node with the smaller
+ * id, q = ((double)(n - 2) * d(lo, hi) - r_lo) - r_hi; the pair that is smallest under the strict order (q as a number, id(lo),
+ * id(hi)) is joined with the lengths b_lo = 0.5 * d(lo, hi) + (r_lo - r_hi) / (2.0 * (double)(n - 2)) and b_hi = d(lo, hi) -
+ * b_lo; for every other active k, duk = 0.5 * ((d(lo, k) + d(hi, k)) - d(lo, hi)), r_k = ((r_k - d(lo, k)) - d(hi, k)) + duk and
+ * d(lo, k) = duk; r_lo = 0.5 * ((r_lo + r_hi) - (double)n * d(lo, hi)); the new node takes lo's place and id.  The last two nodes
+ * are joined with b_lo = d(lo, hi) and b_hi = 0 (the tree is unrooted; this edge makes the list binary).  Every line is this
+ * sequence of binary64 operations in this association, without a fused multiply-add (pansim_amd/csrc/nj_rule.h), so the device,
+ * the host form and any restatement that follows it agree bit for bit.  Join k (in the order performed) creates node pop_size +
+ * k, the leaves being the rows 0 .. pop_size - 1: left[k] (lo), right[k] (hi) its children, len_left[k], len_right[k] the
+ * branches above them, negative ones reported as they are.  (left, right) is a merge list as ps_tree_parsimony takes it.  Limits,
+ * else PS_ERR_INVALID: 2 <= pop_size <= 16384 (the matrix holds 2 GB at the cap), fewer than 2^32 core sites; under the
+ * accessory metric core_genes >= 1, at most 65535 accessory genes and core_genes + 65535 < 2^32. */
+typedef struct {
+    uint64_t pop_size, pairs, core_sites, core_genes;      /* pairs: all N (N - 1) / 2 */
+    uint64_t metric;
+    uint64_t joins;                    /* pop_size - 1 */
+    uint64_t negative_branches;        /* lengths below 0.0 among len_left and len_right */
+} ps_nj_t;
+/* All pairs of two handles of equal pop_size >= 2 on one device (the reference has no such function; population.rs:787-837
+ * writes a sample): `core` a core handle that holds all sites, `acc` an accessory handle of at most 65535 genes (required; with
+ * the core metric none of its kernels is launched).  left, right, len_left, len_right: pop_size - 1 values each.  Ordered behind
+ * all queued work of BOTH handles; changes no state.  PS_ERR_NO_DEVICE before anything else when no GPU is visible; the matrix
+ * that cannot be allocated is PS_ERR_OOM with its bytes. */
+int ps_neighbour_joining(ps_population *core, ps_population *acc, const ps_tree_params *prm, ps_nj_t *out, uint32_t *left, uint32_t *right,
+                         double *len_left, double *len_right);
+/* The same for the two matrices of a simulation (the reference has no such function; population.rs:787-837); a site shard
+ * fails with a message that points to ps_multi_neighbour_joining */
+int ps_sim_neighbour_joining(ps_sim *s, const ps_tree_params *prm, ps_nj_t *out, uint32_t *left, uint32_t *right, double *len_left,
+                             double *len_right);
+/* The same for a sharded run (the reference has no such function; population.rs:787-837): every shard counts its own sites
+ * band by band, shard 0 adds them, keeps them as distances and runs the joins against its accessory replica */
+int ps_multi_neighbour_joining(ps_multi *m, const ps_tree_params *prm, ps_nj_t *out, uint32_t *left, uint32_t *right, double *len_left,
+                               double *len_right);
+/* The same rule on the host alone, the plain O(pop_size^3) loop (no device is touched; the reference has no such function;
+ * population.rs:787-837): over the COMPLETE list of pairs (r1[k], r2[k]) with their numerators (those of the other metric may be
+ * NULL), in any order and orientation.  A missing or duplicate pair (the row sums are undefined on a partial list), an index >=
+ * pop_size, r1[k] == r2[k], an intersection above its union and the metric's limits are PS_ERR_INVALID.  It holds pop_size^2
+ * doubles and as many bytes on the host (2.3 GB at the cap; PS_ERR_OOM when they cannot be allocated) and takes about pop_size^3 / 6
+ * steps: seconds at a few thousand individuals, hours at the cap -- it is the restatement for tests and small samples. */
+int ps_nj_from_counts(const uint32_t *r1, const uint32_t *r2, const uint32_t *core_h, const uint32_t *acc_inter, const uint32_t *acc_union,
+                      uint64_t n_pairs, uint64_t pop_size, uint64_t core_sites, uint64_t core_genes, const ps_tree_params *prm, ps_nj_t *out,
+                      uint32_t *left, uint32_t *right, double *len_left, double *len_right);
+/* The tree as one line of Newick text in the usual unrooted form, three subtrees at the top (host only;
+ * the reference has no such function; population.rs:787-837): the last join is dissolved, its child that is an inner node (the
+ * right one if both are) is opened, that node's two children stand at the top level, left then right, and the other child stands
+ * beside them with the length of the last edge, len_left + len_right of the last join; pop_size == 2 gives "(0:len,1:0);".
+ * Leaves are rows, children left then right, every length written as ps_fmt_f64(len / scale), scale finite and > 0 (core_sites
+ * turns the core metric's sites into substitutions per site).  A child that is not an earlier, still free node is
+ * PS_ERR_INVALID.  `needed` counts the terminating zero; buf == NULL asks for the size alone, a buffer below it is
+ * PS_ERR_INVALID. */
+int ps_nj_newick(const uint32_t *left, const uint32_t *right, const double *len_left, const double *len_right, uint64_t pop_size, double scale,
+                 char *buf, uint64_t cap, uint64_t *needed);
+/* device ms of the last ps_neighbour_joining on this core handle (HIP events; the reference has no such function;
+ * population.rs:787-837): the count kernels of the metric, the store kernels and the initial row sums, the joins.
+ * PS_ERR_STATE before any call. */
+int ps_neighbour_joining_timing(ps_population *core, double *counts_ms, double *store_ms, double *joins_ms);
+
 /* Nearest neighbours: for every individual its k closest OTHER individuals among ALL N under one distance, and the lineages that
  * follow from them (docs/NEAREST_NEIGHBOURS.md) -- the sparse form of the distance matrix, N k entries, and the graph of
  * PopPUNK's lineage model.  The reference has no such function: it writes a SAMPLE of pairs as text (population.rs:787-837), and

@@ -115,6 +115,11 @@ class Upgma(C.Structure):
                                                  "root_num", "root_den", "rounds")]
 
 
+class Nj(C.Structure):
+    """ps_nj_t: the summary of ps_neighbour_joining / ps_nj_from_counts (docs/NEIGHBOUR_JOINING.md)"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "pairs", "core_sites", "core_genes", "metric", "joins", "negative_branches")]
+
+
 PS_KNN_CORE, PS_KNN_ACC, PS_KNN_MAX_K = 0, 1, 128
 
 
@@ -382,6 +387,10 @@ SIGNATURES = {
                                     _vp]),
     "ps_upgma_newick": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     "ps_upgma_tree_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    **_run_forms("neighbour_joining", [C.POINTER(TreeParams), C.POINTER(Nj), _vp, _vp, _vp, _vp]),
+    "ps_nj_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(TreeParams), C.POINTER(Nj), _vp, _vp, _vp, _vp]),
+    "ps_nj_newick": (_int, [_vp, _vp, _vp, _vp, _u64, _f64, _vp, _u64, C.POINTER(_u64)]),
+    "ps_neighbour_joining_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     **_run_forms("nearest_neighbours", [C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
     "ps_neighbours_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
     "ps_lineages_from_neighbours": (_int, [_vp, _u64, C.c_uint32, C.c_uint32, C.POINTER(Lineages), _vp]),

@@ -188,7 +188,7 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
 // ms of the last call's timer groups (`timed`: a call has completed)
-enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_COUNT };
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_NJ, PS_RO_COUNT };
 struct readout_slot {
     void *d = nullptr;
     uint64_t cap = 0;       // (bytes)
@@ -345,6 +345,8 @@ struct ps_population {
     //   PS_RO_MLST      core allele profiles (allele_profiles.h): words, bins, allele numbers, adjacency bit matrix (zeroed per call),
     //                   per-locus counts, the two label arrays, `changed`, bounds, one band of fingerprints, landing table, one band
     //                   of representatives, the tables of the canonicalise workgroups; ms: fingerprint, canon, verify, pairs, labels
+    //   PS_RO_NJ        neighbour-joining tree (neighbour_joining.h): ids, row order, candidate columns, row sums, candidate q, the join
+    //                   records, the N x N f64 distances; ms: counts, store and row sums, joins
     readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
     uint32_t mlst_band = 0;                 // loci per band of the fingerprint table of ps_allele_profiles, 0 = choose ("mlst_band")
@@ -4989,6 +4991,8 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // average-linkage (UPGMA) tree of all pairs (ps_upgma_tree, ps_upgma_from_counts, ps_upgma_newick, ps_multi_*)
 #include "upgma_tree.h"
+// neighbour-joining tree of all pairs (ps_neighbour_joining, ps_nj_from_counts, ps_nj_newick, ps_multi_*)
+#include "neighbour_joining.h"
 
 // nearest neighbours of all pairs and rank-k lineages (ps_nearest_neighbours, ps_neighbours_from_counts, ps_lineages_from_neighbours, ps_multi_*)
 #include "nearest_neighbours.h"

@@ -926,6 +926,18 @@ class Population:
         """device ms of (the count kernels, the store kernels, the rounds) of the last upgma_tree() on this core handle"""
         return _timing(self._lib.ps_upgma_tree_timing, 3, self._h)
 
+    def neighbour_joining(self, acc, metric="core"):
+        """the neighbour-joining tree over ALL pairs of this core population and the accessory population `acc` of the same
+        individuals under the core (`"core"`) or the accessory (`"acc"`) distance (ps_neighbour_joining;
+        docs/NEIGHBOUR_JOINING.md) -> a NeighbourJoiningTree"""
+        from .joining import _nj_call
+        return _nj_call(self._lib.ps_neighbour_joining, _tree_params(metric), self.size, self._h, acc._h)
+
+    def neighbour_joining_timing(self):
+        """device ms of (the count kernels, the store kernels and the row sums, the joins) of the last neighbour_joining() on
+        this core handle"""
+        return _timing(self._lib.ps_neighbour_joining_timing, 3, self._h)
+
     def nearest_neighbours(self, acc, k, metric="core"):
         """the k nearest other individuals of every individual among ALL of this core population and the accessory population
         `acc` of the same individuals, under the core (`"core"`) or the accessory (`"acc"`) distance, in ascending order of

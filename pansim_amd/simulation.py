@@ -242,7 +242,23 @@ class _Samples:
         return _run_subset(self._entry("subset"), self, rows)
 
 
-class Simulation(_Readouts, _Associations, _Profiles, _Samples):
+class _Joining:
+    """The neighbour-joining tree of a run, written once for both of its forms as `_Readouts` writes the other trees (it resolves
+    the entry through the same `_entry`)."""
+
+    def neighbour_joining(self, metric="core"):
+        """Population.neighbour_joining() of the run's two matrices (ps_sim_neighbour_joining / ps_multi_neighbour_joining;
+        docs/NEIGHBOUR_JOINING.md) -> a NeighbourJoiningTree"""
+        from .joining import _nj_call
+        from .population import _tree_params
+        return _nj_call(self._entry("neighbour_joining"), _tree_params(metric), self.params.pop_size, self._h)
+
+    def neighbour_joining_timing(self):
+        """device ms of (the count kernels, the store kernels and the row sums, the joins) of the last neighbour_joining()"""
+        return self._timed.core_genome.neighbour_joining_timing()
+
+
+class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining):
     """State of main() between main.rs:259 and :553 for one process (one GPU)."""
     _prefix = "ps_sim_"
     _core_width = property(lambda self: self.core_genome.ncols)       # the shard's columns when it is a shard
@@ -397,7 +413,7 @@ class Simulation(_Readouts, _Associations, _Profiles, _Samples):
             self.pan_genome.write(outpref)
 
 
-class MultiSimulation(_Readouts, _Associations, _Profiles, _Samples):
+class MultiSimulation(_Readouts, _Associations, _Profiles, _Samples, _Joining):
     """The run sharded by core site inside ONE process (ps_multi): shard k on HIP device devices[k]
     (ordinals may repeat), one host thread per shard inside each call; results equal the unsharded run."""
     _prefix = "ps_multi_"
