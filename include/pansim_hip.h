@@ -756,6 +756,69 @@ int ps_nj_newick(const uint32_t *left, const uint32_t *right, const double *len_
  * PS_ERR_STATE before any call. */
 int ps_neighbour_joining_timing(ps_population *core, double *counts_ms, double *store_ms, double *joins_ms);
 
+/* Bootstrap support of the three trees (Felsenstein 1985; docs/BOOTSTRAP_SUPPORT.md): how often the clades of the tree of ALL N
+ * individuals come back when the core sites are resampled with replacement.  The reference has no such function: it writes a
+ * SAMPLE of pairs as text (population.rs:787-837), from which no tree can be built.  Core metric only.  Replicate b is a
+ * multiset of `draws` sites of the L = global core sites (only the multiset matters); its numerator of a pair is the count that
+ * ps_pairwise_counts would return on the matrix M[:, sites_b].  Without the caller's lists, draw k of replicate b comes from the
+ * Philox4x32-10 block (k >> 1, b, 0, PS_STREAM_BOOTSTRAP = 22) under the key `seed`: the words (x, y) serve draw 2m, (z, w) draw
+ * 2m + 1, and site = the high 32 bits of the 96-bit product (x * 2^32 + y) * L, i.e. (x * L + ((y * L) >> 32)) >> 32 in 64-bit
+ * arithmetic.  The reference tree is the method's tree of the matrix itself, its merge list (left, right) what the method's own
+ * entry returns (PS_BOOT_LINKAGE: ps_merges_from_tree of ps_linkage_tree's edges); the replicates' trees come from the same
+ * device code with the same tie rules and row ids.  With S_k the leaves below merge k of the reference tree (node pop_size + k),
+ * support[k] = the replicates whose tree has a merge with exactly that leaf set (the two rooted methods), or a merge whose
+ * split of the leaves -- its set or the complement -- is that of S_k (PS_BOOT_NJ; a split with fewer than two leaves on one side
+ * is in every tree and always found).  Sets only: equal heights are not collapsed.  shared[b] = the reference merges found in
+ * replicate b, the last merge (all leaves) always among them. */
+#define PS_BOOT_LINKAGE 0
+#define PS_BOOT_UPGMA 1
+#define PS_BOOT_NJ 2
+typedef struct {
+    int32_t method;                    /* PS_BOOT_LINKAGE, PS_BOOT_UPGMA or PS_BOOT_NJ */
+    uint32_t replicates;               /* 1 .. 65535 */
+    uint64_t draws;                    /* sites drawn per replicate, 1 .. 2^31 - 1; 0: the core sites */
+    uint64_t seed;                     /* the key of the draw (not read with the caller's lists) */
+} ps_bootstrap_params;
+typedef struct {
+    uint64_t pop_size, pairs, core_sites, core_genes;      /* pairs: all N (N - 1) / 2 */
+    uint64_t method, replicates, draws;
+    uint64_t merges;                   /* pop_size - 1 */
+    uint64_t support_sum;              /* the sum of support[] over all merges */
+    uint64_t supported_50, supported_70, supported_95;     /* merges other than the last with support * 100 >= p * replicates */
+} ps_bootstrap_t;
+/* All pairs of two handles of equal pop_size >= 2 on one device (the reference has no such function; population.rs:787-837
+ * writes a sample): `core` a core handle that holds all sites, one-hot (every byte 1, 2, 4 or 8; core_davg_form not 3), `acc`
+ * its accessory handle (required as by the trees; none of its kernels is launched).  sites: NULL for the keyed draw, else
+ * replicates x draws global site indices, replicate-major (block bootstraps, jackknives); an index >= L is PS_ERR_INVALID with
+ * its replicate and position.  left, right, support: pop_size - 1 values each; shared: `replicates` values.  Limits, else
+ * PS_ERR_INVALID before anything is queued: those of the method (pop_size <= 16384 for PS_BOOT_UPGMA and PS_BOOT_NJ), 1 <=
+ * replicates <= 65535, 1 <= draws < 2^31, 1 <= L < 2^32, one-hot matrices.  Ordered behind all queued work of BOTH handles;
+ * changes no state.  PS_ERR_NO_DEVICE before anything else when no GPU is visible. */
+int ps_bootstrap_support(ps_population *core, ps_population *acc, const ps_bootstrap_params *prm, const uint32_t *sites, ps_bootstrap_t *out,
+                         uint32_t *left, uint32_t *right, uint32_t *support, uint32_t *shared);
+/* The same for the two matrices of a simulation (the reference has no such function; population.rs:787-837); a site shard
+ * fails with a message that points to ps_multi_bootstrap_support */
+int ps_sim_bootstrap_support(ps_sim *s, const ps_bootstrap_params *prm, const uint32_t *sites, ps_bootstrap_t *out, uint32_t *left, uint32_t *right,
+                             uint32_t *support, uint32_t *shared);
+/* The same for a sharded run (the reference has no such function; population.rs:787-837): every shard draws all sites of a
+ * replicate, keeps its own and counts them band by band; shard 0 adds the counts and runs the trees */
+int ps_multi_bootstrap_support(ps_multi *m, const ps_bootstrap_params *prm, const uint32_t *sites, ps_bootstrap_t *out, uint32_t *left,
+                               uint32_t *right, uint32_t *support, uint32_t *shared);
+/* The draw rule on the host alone (no device is touched; the reference has no such function; population.rs:787-837): the
+ * draws [first, first + count) of replicate `replicate` over core_sites sites (1 .. 2^32 - 1), of `draws` (1 .. 2^31 - 1) */
+int ps_bootstrap_sites(uint64_t seed, uint32_t replicate, uint64_t core_sites, uint64_t draws, uint64_t first, uint64_t count,
+                       uint32_t *out_sites);
+/* The counting on the host alone (no device is touched; the reference has no such function; population.rs:787-837):
+ * support and shared as above from the reference tree's merge list and those of `replicates` trees (rep_left, rep_right:
+ * replicates x (pop_size - 1), replicate-major), compared as rooted clades (unrooted == 0) or as splits.  Every list is checked
+ * as by ps_nj_newick: a child that is not an earlier, still free node is PS_ERR_INVALID.  O(pop_size) per replicate, exact. */
+int ps_bootstrap_from_merges(const uint32_t *ref_left, const uint32_t *ref_right, const uint32_t *rep_left, const uint32_t *rep_right,
+                             uint64_t replicates, uint64_t pop_size, int unrooted, uint32_t *support, uint32_t *shared);
+/* device ms of the last ps_bootstrap_support on this core handle (HIP events; the reference has no such function;
+ * population.rs:787-837), summed over the replicates: the site lists (draw, count, scan, expand), the operands (pack, counts,
+ * store), the trees.  PS_ERR_STATE before any call. */
+int ps_bootstrap_timing(ps_population *core, double *lists_ms, double *operands_ms, double *trees_ms);
+
 /* Nearest neighbours: for every individual its k closest OTHER individuals among ALL N under one distance, and the lineages that
  * follow from them (docs/NEAREST_NEIGHBOURS.md) -- the sparse form of the distance matrix, N k entries, and the graph of
  * PopPUNK's lineage model.  The reference has no such function: it writes a SAMPLE of pairs as text (population.rs:787-837), and

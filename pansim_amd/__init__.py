@@ -13,6 +13,7 @@ from .association import GeneSiteLd, gene_site_from_counts  # noqa: F401
 from .mlst import AlleleProfiles, profiles_from_alleles  # noqa: F401
 from .samples import genealogy_restrict, pool  # noqa: F401
 from .joining import NeighbourJoiningTree, nj_from_counts, nj_newick  # noqa: F401
+from .bootstrap import BootstrapSupport, bootstrap_from_merges, bootstrap_sites  # noqa: F401
 from .genealogy import (PS_GEN_BEYOND, ClockHistogram, GenealogyResult, clock_from_counts, genealogy_clusters, genealogy_newick,  # noqa: F401
                         genealogy_pair, genealogy_pairs)
 from .parsimony import (PS_PARS_BINS, PS_PARS_MAX_POP, TreeParsimony, merges_from_genealogy, merges_from_tree, parsimony_from_rows,  # noqa: F401

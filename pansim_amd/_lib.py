@@ -120,6 +120,21 @@ class Nj(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("pop_size", "pairs", "core_sites", "core_genes", "metric", "joins", "negative_branches")]
 
 
+PS_BOOT_LINKAGE, PS_BOOT_UPGMA, PS_BOOT_NJ = 0, 1, 2
+
+
+class BootstrapParams(C.Structure):
+    """ps_bootstrap_params: the method, the replicates, the draws per replicate (0: the core sites) and the key of the draw of
+    ps_bootstrap_support (docs/BOOTSTRAP_SUPPORT.md)"""
+    _fields_ = [("method", C.c_int32), ("replicates", C.c_uint32), ("draws", C.c_uint64), ("seed", C.c_uint64)]
+
+
+class Bootstrap(C.Structure):
+    """ps_bootstrap_t: the summary of ps_bootstrap_support"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "pairs", "core_sites", "core_genes", "method", "replicates", "draws", "merges",
+                                                 "support_sum", "supported_50", "supported_70", "supported_95")]
+
+
 PS_KNN_CORE, PS_KNN_ACC, PS_KNN_MAX_K = 0, 1, 128
 
 
@@ -391,7 +406,11 @@ SIGNATURES = {
     "ps_nj_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(TreeParams), C.POINTER(Nj), _vp, _vp, _vp, _vp]),
     "ps_nj_newick": (_int, [_vp, _vp, _vp, _vp, _u64, _f64, _vp, _u64, C.POINTER(_u64)]),
     "ps_neighbour_joining_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
-    **_run_forms("nearest_neighbours", [C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
+    **_run_forms("bootstrap_support", [C.POINTER(BootstrapParams), _vp, C.POINTER(Bootstrap), _vp, _vp, _vp, _vp]),
+    "ps_bootstrap_sites": (_int, [_u64, _u32, _u64, _u64, _u64, _u64, _vp]),
+    "ps_bootstrap_from_merges": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _vp, _vp]),
+    "ps_bootstrap_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    **_run_forms("nearest_neighbours",[C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
     "ps_neighbours_from_counts": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, C.POINTER(KnnParams), C.POINTER(Knn), _vp, _vp, _vp]),
     "ps_lineages_from_neighbours": (_int, [_vp, _u64, C.c_uint32, C.c_uint32, C.POINTER(Lineages), _vp]),
     "ps_nearest_neighbours_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),

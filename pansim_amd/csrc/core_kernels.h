@@ -1922,7 +1922,10 @@ __global__ void core_pair_lookup_kernel(const uint32_t *H, uint32_t N, const uin
 // of the chunk's 128).
 // SLOT (core D-avg on a simulation's handle): string k is internal column slot[k], i.e. the strings are in output order
 //  and so is everything computed from them; each byte is then gathered on its own.
-template <bool NIB, bool BLOCKED = false, bool PLANES = false, bool SLOT = false>
+// LIST (with BLOCKED; the resampled strings of the bootstrap, docs/BOOTSTRAP_SUPPORT.md): `slot` is a list of `rows` site rows
+// instead, and string position p holds site row slot[p] -- the strings of the matrix M[:, list].  The 64 lanes of a wave share
+// the word of an item and with it the item's 16 entries, which therefore come through the scalar cache once per item.
+template <bool NIB, bool BLOCKED = false, bool PLANES = false, bool SLOT = false, bool LIST = false>
 __global__ void __launch_bounds__(256) core_packT_kernel(const uint8_t *state, uint32_t N, uint32_t pitch, uint32_t rows,
                                                          uint32_t *packT, uint32_t WT, const uint32_t *slot = nullptr)
 {
@@ -1930,6 +1933,7 @@ __global__ void __launch_bounds__(256) core_packT_kernel(const uint8_t *state, u
     constexpr uint32_t RS = PS_PT_IB + 4u;            // LDS row stride in dwords (16-byte aligned, banks shifted by 4 per word)
     __shared__ __attribute__((aligned(16))) uint32_t T[PS_PT_WB * RS];   // T[w][individual]
     static_assert(!PLANES || (BLOCKED && !NIB), "bit planes: blocked strings of one-hot matrices");
+    static_assert(!LIST || (BLOCKED && !NIB && !PLANES && !SLOT && PS_PT_IB == 256u), "site list: the blocked 2-bit strings, a wave per word");
     const uint32_t tid = threadIdx.x;
     // consecutive workgroups take consecutive individual blocks of the same 512 (256) site rows
     const uint32_t nib = (N + PS_PT_IB - 1u) / PS_PT_IB;
@@ -1943,7 +1947,14 @@ __global__ void __launch_bounds__(256) core_packT_kernel(const uint8_t *state, u
         const uint32_t col = min(i0 + 4u * qd, pitch - 4u);       // (columns beyond N are padding zeros or unused)
         const uint8_t *base = state + (size_t)sb * pitch + col;
         uint32_t v[SPW];
-        if (SLOT) {
+        if constexpr (LIST) {
+            // (it / 64 is the word of the whole wave: the first position and the 16 entries behind it are scalars; positions
+            // past the list read its last entry and are zeroed below)
+            const uint32_t p0 = __builtin_amdgcn_readfirstlane(s_first);
+            const uint8_t *cbase = state + col;
+#pragma unroll
+            for (uint32_t b = 0; b < SPW; b++) v[b] = *(const uint32_t *)(cbase + (size_t)slot[min(p0 + b, rows - 1u)] * pitch);
+        } else if (SLOT) {
             // (individuals past N read column 0: their strings are zeroed or never stored below)
             uint32_t c4[4];
 #pragma unroll

@@ -188,7 +188,7 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
 // ms of the last call's timer groups (`timed`: a call has completed)
-enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_NJ, PS_RO_COUNT };
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_NJ, PS_RO_BOOT, PS_RO_COUNT };
 struct readout_slot {
     void *d = nullptr;
     uint64_t cap = 0;       // (bytes)
@@ -347,6 +347,9 @@ struct ps_population {
     //                   of representatives, the tables of the canonicalise workgroups; ms: fingerprint, canon, verify, pairs, labels
     //   PS_RO_NJ        neighbour-joining tree (neighbour_joining.h): ids, row order, candidate columns, row sums, candidate q, the join
     //                   records, the N x N f64 distances; ms: counts, store and row sums, joins
+    //   PS_RO_BOOT      bootstrap support (bootstrap_support.h), on every core handle of the call: the total word, the weights of the
+    //                   handle's sites, the sums of their blocks, the replicate's site list, one replicate of the caller's lists; ms
+    //                   (shard 0's handle): lists, operands, trees
     readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
     uint32_t mlst_band = 0;                 // loci per band of the fingerprint table of ps_allele_profiles, 0 = choose ("mlst_band")
@@ -2729,16 +2732,23 @@ static core_davg_bands core_davg_plan_bands(const ps_population *p, uint64_t fir
     return b;
 }
 
-// the blocked 2-bit strings of core_allpairs_mfma_fp4_kernel, in output order when d_slot is given
-static int core_davg_pack(ps_population *p, const uint32_t *d_slot, hipStream_t st, uint32_t *WT_out)
+// A list of local site rows on a handle's device, repeats allowed (the bootstrap's resampled sites, bootstrap_support.h): in
+// its place the strings of a handle are those of the matrix M[:, list].  d == nullptr: no list, the handle's own sites.
+struct core_site_list { const uint32_t *d = nullptr; uint32_t n = 0; };
+
+// the blocked 2-bit strings of core_allpairs_mfma_fp4_kernel, in output order when d_slot is given; with a list (of at least one
+// site, in internal order only) the strings of the listed site rows
+static int core_davg_pack(ps_population *p, const uint32_t *d_slot, hipStream_t st, uint32_t *WT_out, core_site_list list = {})
 {
-    const uint32_t N = (uint32_t)p->cfg.pop_size, rows = (uint32_t)p->cfg.ncols;
+    const uint32_t N = (uint32_t)p->cfg.pop_size, rows = list.d ? list.n : (uint32_t)p->cfg.ncols;
+    if (list.d && (d_slot || !rows)) return ps_fail(PS_ERR_STATE, "the strings of a site list are packed in internal order from at least one site");
     const uint32_t WT = ((rows + 15u) / 16u + PS_PT_WB - 1u) / PS_PT_WB * PS_PT_WB;
     const uint64_t need = (uint64_t)((N + 31u) / 32u * 32u) * WT;
     PSCHK(dev_grow(p->d_pack2, p->pack2_cap, need));
     const uint64_t ptiles = (uint64_t)((N + PS_PT_IB - 1u) / PS_PT_IB) * (WT / PS_PT_WB);
     if (ptiles > 0x7FFFFFFFull) return ps_fail(PS_ERR_INVALID, "matrix too large for the transposed distance form");
-    if (d_slot) core_packT_kernel<false, true, false, true><<<dim3((uint32_t)ptiles), 256, 0, st>>>(p->state, N, p->pitch, rows, p->d_pack2, WT, d_slot);
+    if (list.d) core_packT_kernel<false, true, false, false, true><<<dim3((uint32_t)ptiles), 256, 0, st>>>(p->state, N, p->pitch, rows, p->d_pack2, WT, list.d);
+    else if (d_slot) core_packT_kernel<false, true, false, true><<<dim3((uint32_t)ptiles), 256, 0, st>>>(p->state, N, p->pitch, rows, p->d_pack2, WT, d_slot);
     else core_packT_kernel<false, true><<<dim3((uint32_t)ptiles), 256, 0, st>>>(p->state, N, p->pitch, rows, p->d_pack2, WT);
     HIPCHK(hipGetLastError());
     *WT_out = WT;
@@ -2789,17 +2799,19 @@ static int core_davg_whole(ps_population *p, bool onehot, const uint32_t *d_slot
 }
 
 // phase 1 of one handle's sites for a banded call, prepared once: the strings (one-hot matrices) and the chunk ranges, or the
-// generic kernel's row slot; the band counts' scratch (x ranges) allocated
-struct core_davg_src { bool fp4; uint32_t WT, n_chunks, ranges, cpr; const uint32_t *slot; };
+// generic kernel's row slot; the band counts' scratch (x ranges) allocated.  `sites`: the sites the strings hold -- the handle's
+// own, or those of the site list they were packed through (one-hot matrices only), from which WT and the ranges are sized
+struct core_davg_src { bool fp4; uint32_t WT, n_chunks, ranges, cpr; const uint32_t *slot; uint32_t sites; };
 
 static int core_davg_prepare(ps_population *p, const core_davg_bands &b, bool fp4, const uint32_t *d_slot, hipStream_t st,
-                             core_davg_src *o)
+                             core_davg_src *o, core_site_list list = {})
 {
-    const uint32_t N = (uint32_t)p->cfg.pop_size, rows = (uint32_t)p->cfg.ncols;
-    *o = core_davg_src{ fp4 && rows > 0, 0, 0, 1, 0, d_slot };
+    const uint32_t N = (uint32_t)p->cfg.pop_size, rows = list.d ? list.n : (uint32_t)p->cfg.ncols;
+    if (list.d && !fp4) return ps_fail(PS_ERR_INVALID, "the resampled form of the core strings exists for one-hot matrices only");
+    *o = core_davg_src{ fp4 && rows > 0, 0, 0, 1, 0, d_slot, rows };
     const uint64_t slice = (uint64_t)b.band * b.ld;
     if (o->fp4) {
-        PSCHK(core_davg_pack(p, d_slot, st, &o->WT));
+        PSCHK(core_davg_pack(p, d_slot, st, &o->WT, list));
         o->n_chunks = o->WT / PS_MF_CHUNK_DW;
         // chunk ranges: at least 4 workgroups per CU, each range below 2^24 sites (exact f32 sums), scratch permitting
         const uint32_t ntile = (N + PS_MF_TILE - 1u) / PS_MF_TILE, blocks = b.band / PS_MF_TILE * ntile;
@@ -2818,7 +2830,7 @@ static int core_davg_prepare(ps_population *p, const core_davg_bands &b, bool fp
 static int core_davg_band_counts(ps_population *p, const core_davg_src &src, const core_davg_bands &b, uint32_t lo, uint32_t nrows,
                                  hipStream_t st)
 {
-    const uint32_t N = (uint32_t)p->cfg.pop_size, rows = (uint32_t)p->cfg.ncols;
+    const uint32_t N = (uint32_t)p->cfg.pop_size, rows = src.sites;      // (an empty site list counts nothing, as a handle without sites)
     uint32_t *C = p->d_cdavg;
     const uint64_t n = (uint64_t)nrows * b.ld, slice = (uint64_t)b.band * b.ld;
     if (rows == 0) {
@@ -4800,20 +4812,38 @@ struct core_band_source {
     core_davg_bands b{};
     std::vector<core_davg_src> src;
     dev_tmp<uint32_t> land;             // (without peer access: a peer's band counts copied over first)
+    bool in_output_order = false;
 
     ps_population *core(size_t k) const { return m ? m->shard[k]->core : c0; }
 
     // Rows [first, first + count) in bands.  output_order: every handle counts through its own row slot (D-avg), else in
     // internal order (histogram, clusters).  prepare == false: the bands only, counts() is not called.  Everything queued on
     // the handles before is complete or ordered on their streams (the caller's business).
-    int open(ps_population *core0, ps_multi *multi, uint64_t first, uint64_t count, bool output_order, bool prepare = true)
+    // lists (optional): one site list per handle, in whose place the handle's strings are packed; see bind()
+    int open(ps_population *core0, ps_multi *multi, uint64_t first, uint64_t count, bool output_order, bool prepare = true,
+             const core_site_list *lists = nullptr)
     {
         c0 = core0;
         m = multi;
+        in_output_order = output_order;
         const size_t K = m ? m->shard.size() : 1;
         b = core_davg_plan_bands(c0, first, count);
         src.assign(K, core_davg_src{});
         if (!prepare) return PS_OK;
+        PSCHK(bind(lists));
+        if (!m) return PS_OK;
+        PSCHK(use_device(c0));
+        if (!m->peers_ok) PSCHK(land.alloc((uint64_t)b.band * b.ld));
+        return PS_OK;
+    }
+
+    // Phase 1 of every handle, again on an open source: the strings of the handles' own sites (lists == nullptr) or those of one
+    // site list per handle (the bootstrap's replicates; internal order, one-hot matrices).  The strings live in the handle's one
+    // buffer and nothing remembers whose they are: every opening and every binding packs them anew, so neither a replicate's
+    // strings nor the matrix's are ever taken for the other's.  Ordered on the handles' streams behind their last counts().
+    int bind(const core_site_list *lists)
+    {
+        const size_t K = src.size();
         // (one-hot on every shard: the banded FP4 form on each; otherwise -- and with form 3 forced -- the generic kernel on each)
         bool onehot = c0->core_davg_form != 3;
         for (size_t k = 0; k < K; k++) onehot = onehot && core(k)->onehot_safe;
@@ -4821,14 +4851,12 @@ struct core_band_source {
             ps_population *c = core(k);
             PSCHK(use_device(c));
             const uint32_t *slot = nullptr;
-            if (output_order) PSCHK(rows_current(c, &slot));
-            return core_davg_prepare(c, b, onehot, slot ? c->d_row_slot : nullptr, c->stream, &src[k]);
+            if (in_output_order) PSCHK(rows_current(c, &slot));
+            return core_davg_prepare(c, b, onehot, slot ? c->d_row_slot : nullptr, c->stream, &src[k], lists ? lists[k] : core_site_list{});
         };
         if (!m) return prep(0);
         PSCHK(multi_for_each(m, prep));
-        PSCHK(use_device(c0));
-        if (!m->peers_ok) PSCHK(land.alloc((uint64_t)b.band * b.ld));
-        return PS_OK;
+        return use_device(c0);
     }
 
     // h(i, j) of the rows [lo, lo + nrows) in c0->d_cdavg (row pitch b.ld), ordered on c0->stream
@@ -4993,6 +5021,8 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 #include "upgma_tree.h"
 // neighbour-joining tree of all pairs (ps_neighbour_joining, ps_nj_from_counts, ps_nj_newick, ps_multi_*)
 #include "neighbour_joining.h"
+// bootstrap support of the three trees from resampled core sites (ps_bootstrap_support, ps_bootstrap_sites, ps_bootstrap_from_merges, ps_sim_* and ps_multi_*)
+#include "bootstrap_support.h"
 
 // nearest neighbours of all pairs and rank-k lineages (ps_nearest_neighbours, ps_neighbours_from_counts, ps_lineages_from_neighbours, ps_multi_*)
 #include "nearest_neighbours.h"

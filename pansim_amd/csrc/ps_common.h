@@ -19,7 +19,8 @@ enum : uint32_t {
     PS_STREAM_SELECTION = 18,
     PS_STREAM_PAIRS = 19,
     PS_STREAM_PARENTS = 20,
-    PS_STREAM_HGT_COUNT = 21
+    PS_STREAM_HGT_COUNT = 21,
+    PS_STREAM_BOOTSTRAP = 22  // ctr = (draw / 2, replicate, 0), key = the call's seed: (x, y) draw 2m, (z, w) draw 2m + 1
 };
 
 struct ps_u4 { uint32_t x, y, z, w; };
@@ -60,6 +61,19 @@ PS_HD ps_u4 ps_philox_r(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint
 PS_HD ps_u4 ps_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
 {
     return ps_philox_r<10>(c0, c1, c2, c3, k0, k1);
+}
+
+// The bootstrap's draw (docs/BOOTSTRAP_SUPPORT.md): the site in [0, L) of the 64-bit word x : y, the high half of the 96-bit
+// product with L < 2^32, in 64-bit arithmetic without overflow
+PS_HD uint32_t ps_boot_site(uint32_t x, uint32_t y, uint32_t L)
+{
+    return (uint32_t)(((uint64_t)x * L + (((uint64_t)y * L) >> 32)) >> 32);
+}
+// draw k of replicate b under the key (k0, k1)
+PS_HD uint32_t ps_boot_draw(uint64_t k, uint32_t b, uint32_t L, uint32_t k0, uint32_t k1)
+{
+    const ps_u4 w = ps_philox((uint32_t)(k >> 1), b, 0u, PS_STREAM_BOOTSTRAP, k0, k1);
+    return (k & 1) ? ps_boot_site(w.z, w.w, L) : ps_boot_site(w.x, w.y, L);
 }
 
 // Level 1 of the core cell plan: a 6-bit SYMBOL per cell, bit-sliced.  Plane k (0..5) holds bit k of the

@@ -938,6 +938,20 @@ class Population:
         this core handle"""
         return _timing(self._lib.ps_neighbour_joining_timing, 3, self._h)
 
+    def bootstrap_support(self, acc, method="nj", replicates=100, seed=0, draws=None, sites=None):
+        """Felsenstein's bootstrap of a tree of ALL pop_size individuals under the core distance (this handle the core matrix,
+        one-hot; `acc` its accessory one): the tree of `method` ("linkage", "upgma" or "nj"), then `replicates` trees of
+        `draws` (None: all) core sites resampled with replacement on the device -- drawn under the key `seed`, or the rows of
+        `sites` ((replicates, draws) global site indices) -- and how often every merge of the first comes back
+        (ps_bootstrap_support; docs/BOOTSTRAP_SUPPORT.md) -> a BootstrapSupport"""
+        from .bootstrap import _boot_call
+        return _boot_call(self._lib.ps_bootstrap_support, self.size, method, replicates, seed, draws, sites, self._h, acc._h)
+
+    def bootstrap_support_timing(self):
+        """device ms of (the site lists, the operands: pack + counts + store, the trees), summed over the replicates of the last
+        bootstrap_support() on this (core) handle (HIP events)"""
+        return _timing(self._lib.ps_bootstrap_timing, 3, self._h)
+
     def nearest_neighbours(self, acc, k, metric="core"):
         """the k nearest other individuals of every individual among ALL of this core population and the accessory population
         `acc` of the same individuals, under the core (`"core"`) or the accessory (`"acc"`) distance, in ascending order of

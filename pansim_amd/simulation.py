@@ -258,7 +258,22 @@ class _Joining:
         return self._timed.core_genome.neighbour_joining_timing()
 
 
-class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining):
+class _Bootstrap:
+    """Bootstrap support of a run's trees, written once for both of its forms as `_Joining` writes the neighbour-joining tree."""
+
+    def bootstrap_support(self, method="nj", replicates=100, seed=0, draws=None, sites=None):
+        """Population.bootstrap_support() of the run's two matrices (ps_sim_bootstrap_support / ps_multi_bootstrap_support;
+        docs/BOOTSTRAP_SUPPORT.md) -> a BootstrapSupport"""
+        from .bootstrap import _boot_call, _method
+        _method(method)                 # (a ValueError before the library is asked for anything)
+        return _boot_call(self._entry("bootstrap_support"), self.params.pop_size, method, replicates, seed, draws, sites, self._h)
+
+    def bootstrap_support_timing(self):
+        """device ms of (the site lists, the operands, the trees) of the last bootstrap_support(), summed over its replicates"""
+        return self._timed.core_genome.bootstrap_support_timing()
+
+
+class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap):
     """State of main() between main.rs:259 and :553 for one process (one GPU)."""
     _prefix = "ps_sim_"
     _core_width = property(lambda self: self.core_genome.ncols)       # the shard's columns when it is a shard
@@ -413,7 +428,7 @@ class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining):
             self.pan_genome.write(outpref)
 
 
-class MultiSimulation(_Readouts, _Associations, _Profiles, _Samples, _Joining):
+class MultiSimulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap):
     """The run sharded by core site inside ONE process (ps_multi): shard k on HIP device devices[k]
     (ordinals may repeat), one host thread per shard inside each call; results equal the unsharded run."""
     _prefix = "ps_multi_"
