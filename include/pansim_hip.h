@@ -1441,6 +1441,82 @@ int ps_levels_from_heights(const uint64_t *num, const uint64_t *den, uint64_t me
  * uploads and the tables, the pass over all pairs.  PS_ERR_STATE before any call. */
 int ps_tree_compare_timing(ps_population *any, double *tables_ms, double *pairs_ms);
 
+/* Parsimony tree search (docs/PARSIMONY_SEARCH.md): nearest-neighbour interchanges (NNI) of any spanning tree towards a local
+ * optimum of its Fitch length over the core sites.  The reference has no such function (its trees are implicit in the parent
+ * draws of population.rs:443; the columns are those of population.rs:840-863).
+ * Tree: a merge list as ps_tree_parsimony takes it (the rules above apply), SPANNING: merges == pop_size - 1, and 2 <= pop_size
+ * <= PS_NNI_MAX_POP (two LDS dwords per node); else PS_ERR_INVALID.  States: the five class bits of a core cell.
+ * Candidates of merge k, node c = pop_size + k with children a = left[k], b = right[k], parent v and sibling s: none when c is
+ * the root; below an inner node v kind 0 swaps b with s and kind 1 swaps a with s; below the root only its LEFT child beside an
+ * internal s = (p, q) has them, kind 0 swaps b with p and kind 1 swaps b with q (the root stays on its edge).
+ *   delta[2 k + kind]   total changes of the neighbour tree minus total changes of this tree over the handle's sites, exact;
+ *                       PS_NNI_NONE where there is no candidate
+ * Canonical form: internal nodes in (level as ps_parsimony_schedule defines it, smallest leaf of the clade) order, the k-th as
+ * node pop_size + k, left the child whose clade has the smaller smallest leaf: one list per rooted topology.
+ * Search: from the canonical form of the start tree, per round one pass (T and all deltas), the improving candidates in (delta,
+ * node, kind) order taken greedily while the nodes they touch ({v, c, a, b, s}; {root, l, r, a, b, p, q} on the root's edge)
+ * are unmarked, at most moves_per_round (0: no cap); a batch of several whose tree is longer than T + the best delta is
+ * discarded (a rollback) and the best candidate applied alone.  It ends at a tree without an improving candidate
+ * (local_optimum = 1) or after max_rounds rounds.  passes = rounds + rollbacks + 1.  Every integer is exact and independent of
+ * the launch geometry, the sharding and the order of the individuals. */
+#define PS_NNI_MAX_POP 8192u
+#define PS_NNI_NONE INT64_MAX
+typedef struct {
+    uint32_t max_rounds;               /* >= 1 */
+    uint32_t moves_per_round;          /* 0 = no cap */
+} ps_nni_params;
+typedef struct {
+    uint64_t pop_size, sites, merges;  /* N; core sites this result covers; N - 1 */
+    uint64_t rounds, passes, rollbacks;
+    uint64_t moves;                    /* interchanges applied in all rounds (the move arrays hold the first move_cap) */
+    uint64_t local_optimum;            /* 1 iff the returned tree has no improving candidate */
+    uint64_t start_changes, total_changes;     /* T of the start tree and of the returned tree */
+    uint64_t min_changes;              /* sum_s (classes_s - 1), as ps_parsimony_t */
+    uint64_t candidates_last;          /* improving candidates of the last pass (0 at a local optimum) */
+} ps_nni_t;
+/* One pass on the list as given, not canonicalised (the reference has no such function; population.rs:443, :840-863): *total
+ * = T, delta: 2 merges values.  A site-shard core handle answers for its own sites.  Ordered behind the handle's queued work;
+ * changes no state.  PS_ERR_NO_DEVICE before anything else when no GPU is visible. */
+int ps_tree_nni_deltas(ps_population *core, const uint32_t *left, const uint32_t *right, uint64_t merges, uint64_t *total, int64_t *delta);
+/* The search on one core handle (the reference has no such function; population.rs:443, :840-863).  out_left, out_right: the
+ * returned tree, canonical, merges values each; round_changes: max_rounds + 1 values, [0] = T of the start tree, [r] = T after
+ * round r; move_*: move_cap values each, move i of round move_round[i] (from 1) is candidate (move_node[i], move_kind[i]) of
+ * that round's canonical tree with move_delta[i].  Every array may be NULL (the move arrays with move_cap = 0).  A pass reads
+ * back 16 merges bytes; selection and surgery run on the host.  Ordered behind the handle's queued work; changes no state. */
+int ps_tree_nni(ps_population *core, const uint32_t *left, const uint32_t *right, uint64_t merges, const ps_nni_params *prm, ps_nni_t *out,
+                uint32_t *out_left, uint32_t *out_right, uint64_t *round_changes, uint32_t *move_round, uint32_t *move_node,
+                uint32_t *move_kind, int64_t *move_delta, uint64_t move_cap);
+/* The same on the core matrix of a simulation (the reference has no such function; population.rs:443, :840-863) */
+int ps_sim_tree_nni(ps_sim *s, const uint32_t *left, const uint32_t *right, uint64_t merges, const ps_nni_params *prm, ps_nni_t *out,
+                    uint32_t *out_left, uint32_t *out_right, uint64_t *round_changes, uint32_t *move_round, uint32_t *move_node,
+                    uint32_t *move_kind, int64_t *move_delta, uint64_t move_cap);
+/* The same for a sharded run (the reference has no such function; population.rs:443, :840-863): every shard passes over its own
+ * sites, T and the deltas add on the host, one selection. */
+int ps_multi_tree_nni(ps_multi *m, const uint32_t *left, const uint32_t *right, uint64_t merges, const ps_nni_params *prm, ps_nni_t *out,
+                      uint32_t *out_left, uint32_t *out_right, uint64_t *round_changes, uint32_t *move_round, uint32_t *move_node,
+                      uint32_t *move_kind, int64_t *move_delta, uint64_t move_cap);
+/* device ms of the last ps_tree_nni or ps_tree_nni_deltas on this core handle, summed over its passes (each shard's own after
+ * the ps_multi form; HIP events; the reference has no such function; population.rs:443): the uploads of the schedules, the
+ * kernels.  PS_ERR_STATE before any call. */
+int ps_tree_nni_timing(ps_population *core, double *schedule_ms, double *pass_ms);
+/* One pass on the host (no device is touched, as ps_parsimony_from_rows; the reference has no such function; population.rs:443,
+ * :840-863), through the same per-node functions as the kernel.  rows: individual-major pop_size x cols bytes, row k = leaf k. */
+int ps_nni_deltas_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right,
+                            uint64_t merges, uint64_t *total, int64_t *delta);
+/* The search on the host (no device is touched; the reference has no such function; population.rs:443, :840-863): the same loop,
+ * selection and surgery as ps_tree_nni over host passes. */
+int ps_nni_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right, uint64_t merges,
+                     const ps_nni_params *prm, ps_nni_t *out, uint32_t *out_left, uint32_t *out_right, uint64_t *round_changes,
+                     uint32_t *move_round, uint32_t *move_node, uint32_t *move_kind, int64_t *move_delta, uint64_t move_cap);
+/* The canonical form of a spanning merge list (host only; the reference has no such function; population.rs:443).  A parent's id
+ * is above its children's, so the list needs no values in ps_tree_compare.  out_left, out_right: merges values each. */
+int ps_merges_canonical(const uint32_t *left, const uint32_t *right, uint64_t merges, uint64_t pop_size, uint32_t *out_left,
+                        uint32_t *out_right);
+/* Candidate (node, kind) of the list as given applied, the result in canonical form (host only; the reference has no such
+ * function; population.rs:443).  A node without candidates or kind > 1 is PS_ERR_INVALID. */
+int ps_nni_apply(const uint32_t *left, const uint32_t *right, uint64_t merges, uint64_t pop_size, uint32_t node, uint32_t kind,
+                 uint32_t *out_left, uint32_t *out_right);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ from .genealogy import (PS_GEN_BEYOND, ClockHistogram, GenealogyResult, clock_fr
                         genealogy_pair, genealogy_pairs)
 from .parsimony import (PS_PARS_BINS, PS_PARS_MAX_POP, TreeParsimony, merges_from_genealogy, merges_from_tree, parsimony_from_rows,  # noqa: F401
                         parsimony_schedule)
+from .search import PS_NNI_MAX_POP, PS_NNI_NONE, ParsimonySearch, merges_canonical, nni_apply, nni_deltas_from_rows, nni_from_rows  # noqa: F401
 from .tree_compare import TreeComparison, levels_from_heights, tree_compare_from_merges  # noqa: F401
 from .simulation import (DEFAULTS, MultiSimulation, Simulation, derive, make_params, sample_pairs,  # noqa: F401
                          selection_coefficients, state_info, validate)

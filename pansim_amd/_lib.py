@@ -264,6 +264,24 @@ class Parsimony(C.Structure):
                                                  "homoplasic_sites")] + [("ci", C.c_double)]
 
 
+PS_NNI_MAX_POP, PS_NNI_NONE = 8192, 2**63 - 1
+
+
+class NniParams(C.Structure):
+    """ps_nni_params: the limits of ps_tree_nni (docs/PARSIMONY_SEARCH.md)"""
+    _fields_ = [("max_rounds", C.c_uint32), ("moves_per_round", C.c_uint32)]
+
+
+class Nni(C.Structure):
+    """ps_nni_t: the summary of ps_tree_nni / ps_nni_from_rows"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "sites", "merges", "rounds", "passes", "rollbacks", "moves", "local_optimum",
+                                                 "start_changes", "total_changes", "min_changes", "candidates_last")]
+
+
+# the tree, the parameters, the summary, the returned tree, round_changes, the four move arrays, move_cap: the tail of every ps_*nni entry that searches
+_NNI = [C.c_void_p] * 2 + [C.c_uint64, C.POINTER(NniParams), C.POINTER(Nni)] + [C.c_void_p] * 7 + [C.c_uint64]
+
+
 class TreeCompareParams(C.Structure):
     """ps_tree_compare_params"""
     _fields_ = [("bins_a", C.c_uint32), ("bins_b", C.c_uint32), ("span_a", C.c_uint64), ("span_b", C.c_uint64), ("triplets", C.c_int32)]
@@ -465,6 +483,15 @@ SIGNATURES = {
     "ps_tree_compare_from_merges": (_int, [_u64] + _TCMP),
     "ps_levels_from_heights": (_int, [_vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "ps_tree_compare_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_tree_nni_deltas": (_int, [_vp, _vp, _vp, _u64, C.POINTER(_u64), _vp]),
+    "ps_tree_nni": (_int, [_vp] + _NNI),
+    "ps_sim_tree_nni": (_int, [_vp] + _NNI),
+    "ps_multi_tree_nni": (_int, [_vp] + _NNI),
+    "ps_tree_nni_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_nni_deltas_from_rows": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, C.POINTER(_u64), _vp]),
+    "ps_nni_from_rows": (_int, [_vp, _u64, _u64] + _NNI),
+    "ps_merges_canonical": (_int, [_vp, _vp, _u64, _u64, _vp, _vp]),
+    "ps_nni_apply": (_int, [_vp, _vp, _u64, _u64, _u32, _u32, _vp, _vp]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

@@ -188,7 +188,7 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
 // ms of the last call's timer groups (`timed`: a call has completed)
-enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_NJ, PS_RO_BOOT, PS_RO_COUNT };
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_NJ, PS_RO_BOOT, PS_RO_NNI, PS_RO_COUNT };
 struct readout_slot {
     void *d = nullptr;
     uint64_t cap = 0;       // (bytes)
@@ -350,6 +350,8 @@ struct ps_population {
     //   PS_RO_BOOT      bootstrap support (bootstrap_support.h), on every core handle of the call: the total word, the weights of the
     //                   handle's sites, the sums of their blocks, the replicate's site list, one replicate of the caller's lists; ms
     //                   (shard 0's handle): lists, operands, trees
+    //   PS_RO_NNI       parsimony tree search (parsimony_search.h), on every core handle of the call: the two words, the 2 M i64
+    //                   deltas per schedule position, the schedule, the level offsets; ms summed over the call's passes: schedule, pass
     readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
     uint32_t mlst_band = 0;                 // loci per band of the fingerprint table of ps_allele_profiles, 0 = choose ("mlst_band")
@@ -5050,6 +5052,10 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 
 // parsimony of the matrices on a tree (ps_tree_parsimony, ps_merges_from_*, ps_parsimony_schedule, ps_parsimony_from_rows, ps_sim_* and ps_multi_*)
 #include "tree_parsimony.h"
+
+// parsimony tree search by nearest-neighbour interchanges (ps_tree_nni, ps_tree_nni_deltas, ps_nni_from_rows, ps_nni_deltas_from_rows,
+// ps_merges_canonical, ps_nni_apply, ps_sim_* and ps_multi_*)
+#include "parsimony_search.h"
 
 // comparison of two trees over all pairs of leaves (ps_tree_compare, ps_tree_compare_from_merges, ps_levels_from_heights, ps_sim_* and ps_multi_*)
 #include "tree_compare.h"

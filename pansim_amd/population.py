@@ -998,6 +998,25 @@ class Population:
         """device ms of (the schedule's upload, the core pass, the gene pass) of the last tree_parsimony() on this core handle"""
         return _timing(self._lib.ps_tree_parsimony_timing, 3, self._h)
 
+    def tree_nni(self, left, right, max_rounds=1000, moves_per_round=0):
+        """Parsimony tree search from the spanning tree of the merge list (left, right): nearest-neighbour interchanges towards
+        a local optimum of the Fitch length over the sites of this core population (ps_tree_nni; docs/PARSIMONY_SEARCH.md) ->
+        a ParsimonySearch.  Every round is one pass of the device over the core matrix; at most `max_rounds` rounds of at most
+        `moves_per_round` interchanges (0: no cap)."""
+        from .search import _nni_call
+        return _nni_call(self._lib.ps_tree_nni, left, right, self.size, max_rounds, moves_per_round, self._h)
+
+    def nni_deltas(self, left, right):
+        """One pass on the merge list as given (ps_tree_nni_deltas) -> (total_changes, delta): delta[k, kind] = the change of
+        the total under candidate (pop_size + k, kind), PS_NNI_NONE where there is none"""
+        from .search import _deltas_call
+        return _deltas_call(self._lib.ps_tree_nni_deltas, left, right, self._h)
+
+    def tree_nni_timing(self):
+        """device ms of (the uploads of the schedules, the kernels) of the last tree_nni() or nni_deltas() on this core handle,
+        summed over its passes"""
+        return _timing(self._lib.ps_tree_nni_timing, 2, self._h)
+
     def tree_compare(self, a, b, bins=(32, 32), spans=(0, 0), triplets=True, values=None):
         """How well tree `b` recovers tree `a` over the pop_size leaves of this handle (ps_tree_compare;
         docs/TREE_COMPARISON.md) -> a TreeComparison: the cophenetic agreement over all pairs, the rooted triplets both

@@ -273,7 +273,21 @@ class _Bootstrap:
         return self._timed.core_genome.bootstrap_support_timing()
 
 
-class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap):
+class _Search:
+    """The parsimony tree search of a run, written once for both of its forms as `_Bootstrap` writes the bootstrap."""
+
+    def tree_nni(self, left, right, max_rounds=1000, moves_per_round=0):
+        """Population.tree_nni() of the run's core matrix (ps_sim_tree_nni / ps_multi_tree_nni; docs/PARSIMONY_SEARCH.md) -> a
+        ParsimonySearch"""
+        from .search import _nni_call
+        return _nni_call(self._entry("tree_nni"), left, right, self.params.pop_size, max_rounds, moves_per_round, self._h)
+
+    def tree_nni_timing(self):
+        """device ms of (the uploads of the schedules, the kernels) of the last tree_nni(), summed over its passes"""
+        return self._timed.core_genome.tree_nni_timing()
+
+
+class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search):
     """State of main() between main.rs:259 and :553 for one process (one GPU)."""
     _prefix = "ps_sim_"
     _core_width = property(lambda self: self.core_genome.ncols)       # the shard's columns when it is a shard
@@ -428,7 +442,7 @@ class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Boots
             self.pan_genome.write(outpref)
 
 
-class MultiSimulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap):
+class MultiSimulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search):
     """The run sharded by core site inside ONE process (ps_multi): shard k on HIP device devices[k]
     (ordinals may repeat), one host thread per shard inside each call; results equal the unsharded run."""
     _prefix = "ps_multi_"
