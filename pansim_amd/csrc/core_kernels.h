@@ -379,6 +379,21 @@ __device__ __forceinline__ uint32_t ps_entry_cell(uint32_t ent)
     return (row << 10) | ((ent >> 2) & 0x3F0u) | cell;
 }
 
+// Which lane gathers which child bytes of a 1024-byte LDS row (wave sweep).  Transposed against the chunk a lane owns
+// (cells 16 lane .. 16 lane + 15): lane l gathers the child dwords l + 64 m, m = 0 .. 3, i.e. children 4 (l + 64 m) + b.
+// For one ds_read_u8 (fixed m, b) the 32 lanes of an LDS lane group then read the parents of 32 neighbouring child dwords
+// -- with ps_sim's ascending parents a monotone run of about 32 dwords: equal dwords broadcast, the others fall into
+// distinct banks (scripts/lds_gather_banks.py: 2.7 LDS cycles per instruction against 5.9 for the chunk-owner mapping,
+// whose lanes read 16 bytes apart; profiles/sweep_transposed_gather.md).  Any parents give the same result.
+PS_HD uint32_t ps_gather_dword(uint32_t lane, uint32_t m) { return lane + 64u * m; }
+PS_HD uint32_t ps_gather_child(uint32_t lane, uint32_t m, uint32_t b) { return 4u * ps_gather_dword(lane, m) + b; }
+// ... and what a child that does not exist (>= N) gathers: the row's first padding byte, always 0 (in every generation of a
+// pass: that byte gathers itself).  N = pitch has no such child inside the row; what lies past the row is never stored.
+PS_HD uint32_t ps_gather_source(uint32_t child, uint32_t parent, uint32_t N, uint32_t pitch)
+{
+    return child < N ? parent : (N < pitch - 1u ? N : pitch - 1u);
+}
+
 // four zero-extended bytes -> one dword (two v_perm + v_or; the compiler's own form masks every byte again)
 __device__ __forceinline__ uint32_t ps_pack4(uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3)
 {
@@ -407,10 +422,13 @@ __host__ __device__ constexpr uint32_t ps_wave_lds(uint32_t qcap) { return PS_BA
 // generation g, complete -- the parent rows of generation g + 1.  The wave applies generations gen .. gen + T - 1 (Philox
 // keyed on gen + t, parents idx / idx_next[t - 1]) between ONE load and ONE store of the rows: the HBM traffic per
 // generation is 2 N L / T and the results are those of T launches, bit for bit.  T = 1 is the single-generation kernel
-// unchanged (64-67 VGPRs, built for PS_WAVE_LB = 6 waves per SIMD); T = 2 keeps both generations' 16 parent indices in
-// registers -- unpacked: two 10-bit indices per register would save 16 VGPRs the build does not need (it takes 90-91 of the
+// (68-70 VGPRs, built for PS_WAVE_LB = 6 waves per SIMD); T = 2 keeps both generations' 16 parent indices in
+// registers -- unpacked: two 10-bit indices per register would save 16 VGPRs the build does not need (it takes 100-101 of the
 // 128 that 4 waves per SIMD allow, the residency the generation loop launches it at; no scratch) and cost a v_bfe per
 // gathered byte on the vector ALUs, which bound a two-generation launch (profiles/sweep_two_generations.md).
+// The gather of both forms runs in the transposed lane mapping (ps_gather_child: a lane gathers child dwords lane + 64 m,
+// conflict-free in LDS for ascending parents; the chunk owner reads its 16 cells back for the mutations), and T = 2 requests
+// a row's bytes one row ahead (profiles/sweep_transposed_gather.md).
 template <bool DO_GATHER, bool DO_MUT, bool DO_HR, bool NT = false, bool WT = false, uint32_t T = 1>
 __global__ void __launch_bounds__(256, T > 1 ? 4 : PS_WAVE_LB) core_sweep_wave_kernel(core_sweep_args a)
 {
@@ -442,15 +460,24 @@ __global__ void __launch_bounds__(256, T > 1 ? 4 : PS_WAVE_LB) core_sweep_wave_k
     const uint32_t nvalid = (i0 >= a.N) ? 0u : min(16u, a.N - i0);
     const uint32_t vm = ps_valid_word(nvalid);        // the lane's cells that exist, at both sites of a plane word
 
+    // pidx[t][4 m + b] = the parent of child ps_gather_child(lane, m, b): the transposed mapping (above)
     uint32_t pidx[T][16];
     if (DO_GATHER) {
-        // cells beyond N gather the first padding byte of the row, which is always 0 (in every generation of the pass:
-        // that byte gathers itself)
 #pragma unroll
         for (uint32_t t = 0; t < T; t++) {
             const uint32_t *ix = t ? a.idx_next[t ? t - 1u : 0u] : a.idx;
+            const bool wide = ((uintptr_t)ix & 15u) == 0u;      // (wave-uniform; the library's own index buffers all are)
 #pragma unroll
-            for (uint32_t k = 0; k < 16; k++) pidx[t][k] = (k < nvalid) ? ix[i0 + k] : min(a.N, a.pitch - 1u);
+            for (uint32_t m = 0; m < 4; m++) {
+                const uint32_t c0 = ps_gather_child(lane, m, 0u);
+                if (wide && c0 + 4u <= a.N) {
+                    const uint4 p4 = *(const uint4 *)(ix + c0);
+                    pidx[t][4u * m] = p4.x, pidx[t][4u * m + 1u] = p4.y, pidx[t][4u * m + 2u] = p4.z, pidx[t][4u * m + 3u] = p4.w;
+                } else {
+#pragma unroll
+                    for (uint32_t b = 0; b < 4; b++) pidx[t][4u * m + b] = ps_gather_source(c0 + b, c0 + b < a.N ? ix[c0 + b] : 0u, a.N, a.pitch);
+                }
+            }
         }
     }
 
@@ -531,25 +558,48 @@ __global__ void __launch_bounds__(256, T > 1 ? 4 : PS_WAVE_LB) core_sweep_wave_k
             }
         }
         PS_T(2);   // level-1 Philox + class words
+        // Row by row: gather (child dwords lane + 64 m, the transposed mapping: ascending parents make the 32 lanes of an LDS
+        // lane group read a run of neighbouring dwords, i.e. distinct banks or one broadcast dword), four 4-byte stores, and
+        // the chunk owner's 16 cells back for the mutations.  T > 1 (4 waves per SIMD, 128 VGPRs: room for 16 more) requests
+        // the NEXT row's bytes behind that read-back, so that they travel while the mutations are applied -- one exposed LDS
+        // round trip per row instead of two; T = 1 keeps the rows apart (its 80 VGPRs have no room for a second row's bytes).
+        constexpr bool ahead = T > 1 && DO_GATHER;
+        uint32_t g[16] = {};
+        auto gather = [&](uint32_t rr) {
+#pragma unroll
+            for (int k = 0; k < 16; k++) g[k] = rowbuf[rr * 1024u + pidx[t][k]];
+        };
+        if (ahead) gather(0u);
 #pragma unroll
         for (uint32_t rr = 0; rr < PS_ROWS; rr++) {
             uint8_t *row = rowbuf + rr * 1024u;
             uint4 d = v[rr];
             if (DO_GATHER) {
+                if (!ahead) gather(rr);
                 uint32_t w[4];
 #pragma unroll
-                for (int j = 0; j < 4; j++)
-                    w[j] = ps_pack4(row[pidx[t][4 * j]], row[pidx[t][4 * j + 1]], row[pidx[t][4 * j + 2]], row[pidx[t][4 * j + 3]]);
-                d = make_uint4(w[0], w[1], w[2], w[3]);
+                for (int m = 0; m < 4; m++) w[m] = ps_pack4(g[4 * m], g[4 * m + 1], g[4 * m + 2], g[4 * m + 3]);
+                // the LDS row becomes the child row; every gather read precedes these stores
+                ps_wave_sync();
+#pragma unroll
+                for (uint32_t m = 0; m < 4; m++) *(uint32_t *)(row + 4u * ps_gather_dword(lane, m)) = w[m];
+                // ... and the mutations are the chunk owner's: its 16 cells back, once the whole child row stands
+                if (events && DO_MUT) {
+                    ps_wave_sync();
+                    d = *(const uint4 *)(row + i0);
+                }
+                if (ahead && rr + 1u < PS_ROWS) {
+                    __builtin_amdgcn_sched_barrier(0);      // (the read-back first: LDS returns in issue order)
+                    gather(rr + 1u);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
             // the mutations the symbols decide, in registers (population.rs:511-540)
             if (events && DO_MUT) {
                 if (rr & 1u) ps_apply_row<1u>(y[rr >> 1], d);
                 else ps_apply_row<0u>(y[rr >> 1], d);
             }
-            // the LDS row becomes the child row; every gather read precedes this store
-            if (DO_GATHER) ps_wave_sync();
-            if (DO_GATHER || events) *(uint4 *)(row + i0) = d;
+            if (events && (DO_MUT || !DO_GATHER)) *(uint4 *)(row + i0) = d;
             __builtin_amdgcn_sched_barrier(0);      // keep the rows apart (see above)
         }
         PS_T(1);   // gather + symbol-decided mutations

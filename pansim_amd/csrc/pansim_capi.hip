@@ -3638,11 +3638,12 @@ static int sim_create_impl(const ps_sim_params *p, ps_sim *s)
     // light HGT co-runs with the sweep: launch it narrow when the sweep is long enough to hide it.  The narrower it runs
     // (the more events a thread handles in sequence) the less it takes from the sweep, and the longer the chain of a
     // generation gets; the chain must stay inside the time the sweep takes PER GENERATION, launch(T) / T.
-    //  * Two generations per launch (profiles/sweep_two_generations.md): the launch is bound by its vector instructions
-    //    (cfg2: 0.65 ms = 2 N L bytes at 3.7 TB/s), the chain measures ~0.25 ms + 0.4 us per event a thread handles
-    //    (0.11 ms with the whole chip to itself), and 95 % of launch / 2 is what it gets -- cfg2, generations/s at 0 / 32 /
-    //    64 / 96 / 112 / 144 / 192 / 256 / 384 events per thread: 2470 / 2545 / 2582 / 2844 / 2837-2905 / 2918-2931 / 2944 /
-    //    2811 / 2467 (past ~200 the period follows the chain, below ~100 the wide HGT kernel slows the launch).
+    //  * Two generations per launch (profiles/sweep_transposed_gather.md 3, after profiles/sweep_two_generations.md): the
+    //    launch is bound by its vector instructions (cfg2: 0.60 ms = 2 N L bytes at 4.0 TB/s), the chain measures 0.222 ms +
+    //    0.445 us per event a thread handles, and launch / 2 is what it gets (the ~0.012 ms between two launches are its
+    //    margin) -- cfg2, generations/s at 0 / 96 / 120 / 145 / 160 / 170 / 180 / 192 / 224 / 256 / 320 / 384 events per
+    //    thread: 2699 / 3090 / 3183 / 3200 / 3205 / 3231 / 3216 / 3213 / 3076 / 2977 / 2735 / 2545 (past ~200 the period
+    //    follows the chain, below ~120 the wide HGT kernel slows the launch); the rule gives 175.
     //  * One generation per launch (the form before, kept for A/B runs at PANSIM_SWEEP_GENERATIONS=1): half of what a
     //    sweep estimated at 4.2 TB/s leaves beyond 0.3 ms, at most 112 (cfg2 at 32 / 64 / 128 / 192 / 256 / 384: 1690 /
     //    1736 / 1781 / 1775 / 1727 / 1480).
@@ -3652,8 +3653,8 @@ static int sim_create_impl(const ps_sim_params *p, ps_sim *s)
         const double bytes = 2.0 * (double)N * (double)s->core->cfg.ncols;
         double ept;
         if (sim_sweep_generations(s) >= 2u) {
-            const double per_gen_ms = bytes / 3.7e12 * 1e3 / 2.0;
-            ept = std::min((0.95 * per_gen_ms - 0.25) / 0.4e-3, 192.0);
+            const double per_gen_ms = bytes / 4.0e12 * 1e3 / 2.0;
+            ept = std::min((per_gen_ms - 0.222) / 0.445e-3, 192.0);
         } else {
             const double sweep_ms = bytes / 4.2e12 * 1e3;
             ept = std::min((sweep_ms - 0.3) / 1.0e-3 * 0.5, 112.0);
