@@ -1517,6 +1517,86 @@ int ps_merges_canonical(const uint32_t *left, const uint32_t *right, uint64_t me
 int ps_nni_apply(const uint32_t *left, const uint32_t *right, uint64_t merges, uint64_t pop_size, uint32_t node, uint32_t kind,
                  uint32_t *out_left, uint32_t *out_right);
 
+/* Likelihood of a tree under the Jukes-Cantor model (docs/TREE_LIKELIHOOD.md): lnL of a spanning tree with branch lengths over
+ * the core sites, every site's likelihood, the derivative sums of every branch, and maximum-likelihood branch lengths.  The
+ * reference has no such function (its trees are implicit in the parent draws of population.rs:443; the columns are those of
+ * population.rs:840-863, the substitution of a base by another base is population.rs:514-540).
+ * Tree: a spanning merge list as ps_tree_nni takes it, 2 <= pop_size <= PS_LIK_MAX_POP (36 LDS bytes per node and 16 per branch);
+ * else PS_ERR_INVALID.  length[pop_size + merges]: binary64, expected substitutions per site on the branch above every node, the
+ * root's entry ignored, each used as min(max(t, PS_LIK_MIN_LENGTH), PS_LIK_MAX_LENGTH); NaN or infinity is PS_ERR_INVALID.
+ * States: bytes 1, 2, 4, 8 are the bases; ANY other byte is missing data (partial (1, 1, 1, 1)) -- not a fifth state as in the
+ * parsimony entries.
+ *   site likelihood   mant * 2^exp, mant = the root's rescaled partial summed / 4; ln = log(mant) + exp ln 2
+ *   branch_g[c]       sum over sites of r = B / (A + x_c B), the site likelihood being A + x_c B in x_c = exp(-4 t_c / 3)
+ *   branch_h[c]       sum over sites of r r:  dlnL/dt_c = -(4 x / 3) g,  d2lnL/dt_c2 = (16 x x / 9)(-h) + (16 x / 9) g
+ * Every site's (mant, exp) and r are the same bits on host and device (pansim_amd/csrc/jc_rule.h); the sums over sites are taken
+ * in a fixed order per device (a repeated call returns the same bits) and differ from the host's by their rounding only. */
+#define PS_LIK_MAX_POP 2048u
+#define PS_LIK_MIN_LENGTH 1e-8
+#define PS_LIK_MAX_LENGTH 10.0
+typedef struct {
+    uint32_t max_rounds;               /* >= 1 */
+    double eps_lnl;                    /* > 0: an accepted round that gains less ends the optimisation */
+} ps_ml_params;
+typedef struct {
+    uint64_t pop_size, sites, merges;  /* N; core sites this result covers; N - 1 */
+    uint64_t clamped_lengths;          /* entries of the lengths given that the bounds changed */
+    uint64_t missing_cells;            /* cells that are none of 1 / 2 / 4 / 8 */
+    uint64_t rounds, passes, rollbacks;/* ps_tree_ml_lengths: accepted rounds, passes, halvings of the step; else 0, 1, 0 */
+    uint64_t converged;                /* 1 iff the last accepted round gained less than eps_lnl */
+    double lnl, start_lnl;             /* lnL with the returned (given) lengths, and with the start lengths */
+    double tree_length;                /* sum of the used lengths */
+} ps_likelihood_t;
+/* One pass on one core handle (the reference has no such function; population.rs:443, :840-863).  site_mant: sites f64,
+ * site_exp: sites i32, branch_g, branch_h: pop_size + merges f64 (the root's 0); each may be NULL and then costs nothing -- no
+ * down pass runs unless branch_g or branch_h is asked for.  A site-shard core handle answers for its own sites.  Ordered behind
+ * the handle's queued work; changes no state.  PS_ERR_NO_DEVICE before anything else when no GPU is visible; PS_ERR_OOM names
+ * the bytes. */
+int ps_tree_likelihood(ps_population *core, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                       ps_likelihood_t *out, double *site_mant, int32_t *site_exp, double *branch_g, double *branch_h);
+/* The same on the core matrix of a simulation (the reference has no such function; population.rs:443, :840-863) */
+int ps_sim_tree_likelihood(ps_sim *s, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                           ps_likelihood_t *out, double *site_mant, int32_t *site_exp, double *branch_g, double *branch_h);
+/* The same for a sharded run (the reference has no such function; population.rs:443, :840-863): every shard passes over its own
+ * sites, the per-site arrays are concatenated, lnL, g and h add on the host in shard order. */
+int ps_multi_tree_likelihood(ps_multi *m, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                             ps_likelihood_t *out, double *site_mant, int32_t *site_exp, double *branch_g, double *branch_h);
+/* Maximum-likelihood branch lengths of the tree from the start lengths length_in (the reference has no such function;
+ * population.rs:443, :840-863).  The right root child's length is added to the left's and held at PS_LIK_MIN_LENGTH; a round is
+ * one pass with derivatives and one damped Newton step on every other branch at once (delta = -g_t / h_t where h_t < 0, else
+ * sign(g_t) t; limited to [-t / 2, max(t, 1e-3)]; t' = clamp(t + lambda delta)); a pass that gives a lower lnL restores the
+ * lengths, halves lambda and counts as a rollback, an accepted round sets lambda back to 1.  It ends when an accepted round
+ * gains less than eps_lnl (converged = 1; a pass that gains exactly nothing ends it the same way without a round), after
+ * max_rounds rounds, or when lambda < 2^-20.  length_out: pop_size + merges values (the root's 0); round_lnl: round_cap >=
+ * max_rounds + 1 values, [0] = lnL at the start lengths, [r] = after round r, strictly increasing; either may be NULL. */
+int ps_tree_ml_lengths(ps_population *core, const uint32_t *left, const uint32_t *right, const double *length_in, uint64_t merges,
+                       const ps_ml_params *prm, ps_likelihood_t *out, double *length_out, double *round_lnl, uint64_t round_cap);
+/* The same on the core matrix of a simulation (the reference has no such function; population.rs:443, :840-863) */
+int ps_sim_tree_ml_lengths(ps_sim *s, const uint32_t *left, const uint32_t *right, const double *length_in, uint64_t merges,
+                           const ps_ml_params *prm, ps_likelihood_t *out, double *length_out, double *round_lnl, uint64_t round_cap);
+/* The same for a sharded run (the reference has no such function; population.rs:443, :840-863): one Newton step on the sums of
+ * the shards. */
+int ps_multi_tree_ml_lengths(ps_multi *m, const uint32_t *left, const uint32_t *right, const double *length_in, uint64_t merges,
+                             const ps_ml_params *prm, ps_likelihood_t *out, double *length_out, double *round_lnl, uint64_t round_cap);
+/* device ms of the last ps_tree_likelihood or ps_tree_ml_lengths on this core handle, summed over its passes (each shard's own
+ * after the ps_multi form; HIP events; the reference has no such function; population.rs:443): the uploads of the schedule and
+ * of x, the kernel, the sum of the workgroups' rows.  PS_ERR_STATE before any call. */
+int ps_tree_likelihood_timing(ps_population *core, double *schedule_ms, double *pass_ms, double *reduce_ms);
+/* One pass on the host (no device is touched; the reference has no such function; population.rs:443, :840-863), through the same
+ * jc_rule.h functions as the kernel, the sites summed in ascending order.  rows: individual-major pop_size x cols bytes, row k =
+ * leaf k. */
+int ps_likelihood_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right,
+                            const double *length, uint64_t merges, ps_likelihood_t *out, double *site_mant, int32_t *site_exp,
+                            double *branch_g, double *branch_h);
+/* The optimiser on the host (no device is touched; the reference has no such function; population.rs:443, :840-863): the same loop
+ * as ps_tree_ml_lengths over host passes. */
+int ps_ml_lengths_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right,
+                            const double *length_in, uint64_t merges, const ps_ml_params *prm, ps_likelihood_t *out, double *length_out,
+                            double *round_lnl, uint64_t round_cap);
+/* Start lengths from the branch_changes of ps_tree_parsimony over `sites` sites (host only; the reference has no such function;
+ * population.rs:514-540): with p = changes / sites, -3/4 ln(1 - 4 p / 3); PS_LIK_MAX_LENGTH from p = 0.74 on. */
+int ps_jc_lengths_from_changes(const uint64_t *branch_changes, uint64_t nodes, uint64_t sites, double *length);
+
 #ifdef __cplusplus
 }
 #endif

@@ -282,6 +282,27 @@ class Nni(C.Structure):
 _NNI = [C.c_void_p] * 2 + [C.c_uint64, C.POINTER(NniParams), C.POINTER(Nni)] + [C.c_void_p] * 7 + [C.c_uint64]
 
 
+PS_LIK_MAX_POP, PS_LIK_MIN_LENGTH, PS_LIK_MAX_LENGTH = 2048, 1e-8, 10.0
+
+
+class MlParams(C.Structure):
+    """ps_ml_params: the limits of ps_tree_ml_lengths (docs/TREE_LIKELIHOOD.md)"""
+    _fields_ = [("max_rounds", C.c_uint32), ("eps_lnl", C.c_double)]
+
+
+class Likelihood(C.Structure):
+    """ps_likelihood_t: the summary of ps_tree_likelihood / ps_tree_ml_lengths and their host restatements"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "sites", "merges", "clamped_lengths", "missing_cells", "rounds", "passes",
+                                                 "rollbacks", "converged")] + \
+               [(name, C.c_double) for name in ("lnl", "start_lnl", "tree_length")]
+
+
+# the tree, the lengths, merges, the summary, site_mant, site_exp, branch_g, branch_h: the tail of every entry that evaluates
+_LIK = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(Likelihood)] + [C.c_void_p] * 4
+# the tree, the start lengths, merges, the parameters, the summary, length_out, round_lnl, round_cap: of every entry that optimises
+_ML = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(MlParams), C.POINTER(Likelihood)] + [C.c_void_p] * 2 + [C.c_uint64]
+
+
 class TreeCompareParams(C.Structure):
     """ps_tree_compare_params"""
     _fields_ = [("bins_a", C.c_uint32), ("bins_b", C.c_uint32), ("span_a", C.c_uint64), ("span_b", C.c_uint64), ("triplets", C.c_int32)]
@@ -492,6 +513,16 @@ SIGNATURES = {
     "ps_nni_from_rows": (_int, [_vp, _u64, _u64] + _NNI),
     "ps_merges_canonical": (_int, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "ps_nni_apply": (_int, [_vp, _vp, _u64, _u64, _u32, _u32, _vp, _vp]),
+    "ps_tree_likelihood": (_int, [_vp] + _LIK),
+    "ps_sim_tree_likelihood": (_int, [_vp] + _LIK),
+    "ps_multi_tree_likelihood": (_int, [_vp] + _LIK),
+    "ps_tree_ml_lengths": (_int, [_vp] + _ML),
+    "ps_sim_tree_ml_lengths": (_int, [_vp] + _ML),
+    "ps_multi_tree_ml_lengths": (_int, [_vp] + _ML),
+    "ps_tree_likelihood_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_likelihood_from_rows": (_int, [_vp, _u64, _u64] + _LIK),
+    "ps_ml_lengths_from_rows": (_int, [_vp, _u64, _u64] + _ML),
+    "ps_jc_lengths_from_changes": (_int, [_vp, _u64, _u64, _vp]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

@@ -188,7 +188,7 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
 // ms of the last call's timer groups (`timed`: a call has completed)
-enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_NJ, PS_RO_BOOT, PS_RO_NNI, PS_RO_COUNT };
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_NJ, PS_RO_BOOT, PS_RO_NNI, PS_RO_LIK, PS_RO_COUNT };
 struct readout_slot {
     void *d = nullptr;
     uint64_t cap = 0;       // (bytes)
@@ -352,6 +352,9 @@ struct ps_population {
     //                   (shard 0's handle): lists, operands, trees
     //   PS_RO_NNI       parsimony tree search (parsimony_search.h), on every core handle of the call: the two words, the 2 M i64
     //                   deltas per schedule position, the schedule, the level offsets; ms summed over the call's passes: schedule, pass
+    //   PS_RO_LIK       tree likelihood (tree_likelihood.h), on every core handle of the call: the missing word, the summed row, the
+    //                   schedule, the level offsets, x per slot, the per-site mantissas and exponents, one row of sums per workgroup;
+    //                   ms summed over the call's passes: schedule, pass, reduce
     readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
     uint32_t mlst_band = 0;                 // loci per band of the fingerprint table of ps_allele_profiles, 0 = choose ("mlst_band")
@@ -5057,6 +5060,10 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 // parsimony tree search by nearest-neighbour interchanges (ps_tree_nni, ps_tree_nni_deltas, ps_nni_from_rows, ps_nni_deltas_from_rows,
 // ps_merges_canonical, ps_nni_apply, ps_sim_* and ps_multi_*)
 #include "parsimony_search.h"
+
+// Jukes-Cantor likelihood of a tree and maximum-likelihood branch lengths (ps_tree_likelihood, ps_tree_ml_lengths, ps_likelihood_from_rows,
+// ps_ml_lengths_from_rows, ps_jc_lengths_from_changes, ps_sim_* and ps_multi_*)
+#include "tree_likelihood.h"
 
 // comparison of two trees over all pairs of leaves (ps_tree_compare, ps_tree_compare_from_merges, ps_levels_from_heights, ps_sim_* and ps_multi_*)
 #include "tree_compare.h"

@@ -1017,6 +1017,28 @@ class Population:
         summed over its passes"""
         return _timing(self._lib.ps_tree_nni_timing, 2, self._h)
 
+    def tree_likelihood(self, left, right, lengths, per_site=False, derivatives=False):
+        """The Jukes-Cantor likelihood of the spanning tree of the merge list (left, right) with `lengths` (pop_size + merges
+        float64: substitutions per site on the branch above every node, the root's ignored) over the sites of this core
+        population, in one pass (ps_tree_likelihood; docs/TREE_LIKELIHOOD.md) -> a TreeLikelihood.  `per_site`: every site's
+        likelihood; `derivatives`: the sums behind the first and second derivative with respect to every branch."""
+        from .likelihood import _lik_call
+        return _lik_call(self._lib.ps_tree_likelihood, left, right, lengths, self.size, self.ncols, per_site, derivatives, self._h)
+
+    def tree_ml_lengths(self, left, right, lengths=None, max_rounds=50, eps_lnl=1e-3):
+        """Maximum-likelihood branch lengths of the tree under Jukes-Cantor by damped Newton steps on all branches at once
+        (ps_tree_ml_lengths; docs/TREE_LIKELIHOOD.md) -> an MlLengths.  `lengths`: the start lengths (None: the Jukes-Cantor
+        correction of the parsimony changes of every branch, jc_lengths_from_changes of tree_parsimony)."""
+        from .likelihood import _ml_call, _start_lengths
+        if lengths is None:
+            lengths = _start_lengths(self, left, right)
+        return _ml_call(self._lib.ps_tree_ml_lengths, left, right, lengths, self.size, max_rounds, eps_lnl, self._h)
+
+    def tree_likelihood_timing(self):
+        """device ms of (the uploads of the schedules, the kernels, the sums of the workgroups' rows) of the last
+        tree_likelihood() or tree_ml_lengths() on this core handle, summed over its passes"""
+        return _timing(self._lib.ps_tree_likelihood_timing, 3, self._h)
+
     def tree_compare(self, a, b, bins=(32, 32), spans=(0, 0), triplets=True, values=None):
         """How well tree `b` recovers tree `a` over the pop_size leaves of this handle (ps_tree_compare;
         docs/TREE_COMPARISON.md) -> a TreeComparison: the cophenetic agreement over all pairs, the rooted triplets both

@@ -287,7 +287,30 @@ class _Search:
         return self._timed.core_genome.tree_nni_timing()
 
 
-class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search):
+class _Likelihood:
+    """The Jukes-Cantor likelihood of a tree of a run in both of its forms (Simulation: ps_sim_, MultiSimulation: ps_multi_)."""
+
+    def tree_likelihood(self, left, right, lengths, per_site=False, derivatives=False):
+        """Population.tree_likelihood() of the run's core matrix (ps_sim_tree_likelihood / ps_multi_tree_likelihood;
+        docs/TREE_LIKELIHOOD.md) -> a TreeLikelihood"""
+        from .likelihood import _lik_call
+        return _lik_call(self._entry("tree_likelihood"), left, right, lengths, self.params.pop_size, self._core_width, per_site,
+                         derivatives, self._h)
+
+    def tree_ml_lengths(self, left, right, lengths=None, max_rounds=50, eps_lnl=1e-3):
+        """Population.tree_ml_lengths() of the run's core matrix (ps_sim_tree_ml_lengths / ps_multi_tree_ml_lengths) -> an
+        MlLengths; without `lengths` the start is the Jukes-Cantor correction of the run's tree_parsimony() on the same tree"""
+        from .likelihood import _ml_call, _start_lengths
+        if lengths is None:
+            lengths = _start_lengths(self, left, right)
+        return _ml_call(self._entry("tree_ml_lengths"), left, right, lengths, self.params.pop_size, max_rounds, eps_lnl, self._h)
+
+    def tree_likelihood_timing(self):
+        """device ms of (the uploads, the kernels, the sums of the rows) of the last tree_likelihood() or tree_ml_lengths()"""
+        return self._timed.core_genome.tree_likelihood_timing()
+
+
+class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search, _Likelihood):
     """State of main() between main.rs:259 and :553 for one process (one GPU)."""
     _prefix = "ps_sim_"
     _core_width = property(lambda self: self.core_genome.ncols)       # the shard's columns when it is a shard
@@ -442,7 +465,7 @@ class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Boots
             self.pan_genome.write(outpref)
 
 
-class MultiSimulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search):
+class MultiSimulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search, _Likelihood):
     """The run sharded by core site inside ONE process (ps_multi): shard k on HIP device devices[k]
     (ordinals may repeat), one host thread per shard inside each call; results equal the unsharded run."""
     _prefix = "ps_multi_"
