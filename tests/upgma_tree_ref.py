@@ -28,9 +28,10 @@ def matrices(metric, r1, r2, core_h, acc_inter, acc_union, pop_size, core_genes)
     return S, B
 
 
-def sequential(S, B):
+def sequential(S, B, less=None):
     """the sequential algorithm on the pair sums (changed in place) -> the merges (num, den, id a, id b, size a, size b), a < b,
-    in the order they are performed; den = |A| |B| under the core metric (B is None), else the sum of b"""
+    in the order they are performed; den = |A| |B| under the core metric (B is None), else the sum of b.  `less(num1, den1, num2,
+    den2)` takes the place of the exact num1 den2 < num2 den1, for a test that asks what a wrong comparator would produce"""
     n = len(S)
     alive, size, out = list(range(n)), [1] * n, []
     while len(alive) > 1:
@@ -41,7 +42,7 @@ def sequential(S, B):
             for b in alive[k + 1:]:
                 num = Sa[b]
                 den = Ba[b] if B else sa * size[b]
-                if ba < 0 or num * bd < bn * den:
+                if ba < 0 or (num * bd < bn * den if less is None else less(num, den, bn, bd)):
                     bn, bd, ba, bb = num, den, a, b
         out.append((bn, bd, ba, bb, size[ba], size[bb]))
         for c in alive:
@@ -143,11 +144,11 @@ def result(metric, nodes, n_pairs, pop_size, core_sites, core_genes):
                 size=np.array([e[2] for e in nodes], np.uint32), num=np.array(num, np.uint64), den=np.array(den, np.uint64))
 
 
-def tree(metric, r1, r2, core_h, acc_inter, acc_union, pop_size, core_sites, core_genes):
+def tree(metric, r1, r2, core_h, acc_inter, acc_union, pop_size, core_sites, core_genes, less=None):
     """the UPGMA tree of the complete list by the sequential algorithm (a merge's node is its place in the list)"""
     S, B = matrices(metric, r1, r2, core_h, acc_inter, acc_union, pop_size, core_genes)
     n, nodes, cur = int(pop_size), [], list(range(int(pop_size)))
-    for k, (num, den, a, b, sa, sb) in enumerate(sequential(S, B)):
+    for k, (num, den, a, b, sa, sb) in enumerate(sequential(S, B, less)):
         nodes.append((cur[a], cur[b], sa + sb, num, den))
         cur[a] = n + k
     return result(metric, nodes, len(r1), pop_size, core_sites, core_genes)
