@@ -1597,6 +1597,97 @@ int ps_ml_lengths_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t col
  * population.rs:514-540): with p = changes / sites, -3/4 ln(1 - 4 p / 3); PS_LIK_MAX_LENGTH from p = 0.74 on. */
 int ps_jc_lengths_from_changes(const uint64_t *branch_changes, uint64_t nodes, uint64_t sites, double *length);
 
+/* Likelihood of a tree under the simulator's own substitution process (docs/TREE_MODEL.md): F81 with base frequencies pi, a root
+ * distribution rho and up to 8 rate categories per site.  The reference has no such function; the process is its core mutation,
+ * which redraws a hit cell from {2, 4, 8} whatever the old allele was (population.rs:531: pi = (0, 1/3, 1/3, 1/3)), from a
+ * founding genome uniform over {1, 2, 4, 8} (population.rs:201-203: rho = 1/4 each, not stationary).
+ * P(t) = x I + (1 - x) 1 pi^T with x = exp(-(r t) / beta), beta = 1 - sum pi_a^2: lengths are expected substitutions per site at
+ * rate 1 under pi, t / beta events per site; the tree, the lengths, their clamp and the missing-data rule are ps_tree_likelihood's.
+ *   freq      pi: entries >= 0, at most one of them 0, summing to 1 within 1e-12
+ *   root      rho: entries > 0 summing to 1 within 1e-12; equal to freq bit for bit = reversible (the root rule of ps_tree_ml_lengths)
+ *   rate      r_k, finite and >= 0 (0: an invariant class); weight: w_k > 0 summing to 1 within 1e-12; categories: 1 <= K <= 8
+ *   site_class  NULL: every site is a mixture of the K categories; else one u8 < K per core site -- of the handle in
+ *             ps_tree_model_likelihood and the host entries, of the whole run (the global site index) in the ps_sim_ and ps_multi_
+ *             forms -- and site_classes = their count: the site's likelihood is its class's alone
+ * Anything else is PS_ERR_INVALID with a message that names the field.
+ *   site likelihood   assigned: the class's (mant, exp); mixture: e = the largest exponent of a category of non-zero mantissa,
+ *                     mant = sum_k w_k ldexp(mant_k, e_k - e), not renormalised; posterior post_k = w_k ldexp(..) / mant
+ *   site_rate         sum_k post_k r_k (assigned: r of the class)
+ *   branch_g[c]       sum_s D_sc, D_sc = sum_k post_sk ((r_k x_ck) ratio_sck), ratio = (D - A) / ((1 - x) A + x D)
+ *   branch_h[c]       sum_s D_sc^2;   branch_q[c] = sum_s sum_k post_sk r_k ((r_k x_ck) ratio_sck)
+ *                     dlnL/dt_c = -g / beta,  d2lnL/dt_c2 = (q - h) / beta^2
+ * With pi = rho = 1/4, K = 1, r = w = 1 every site's (mant, exp) is the same bits as ps_tree_likelihood's.  Every site's values
+ * are the same bits on host and device (pansim_amd/csrc/subst_rule.h); sums over sites are taken in a fixed order per device.
+ * With derivatives pop_size <= PS_MODEL_MAX_POP_DERIV (32 LDS bytes per branch instead of 16), else PS_LIK_MAX_POP. */
+#define PS_MODEL_MAX_CATEGORIES 8u
+#define PS_MODEL_MAX_POP_DERIV 1536u
+typedef struct {
+    double freq[4], root[4];
+    uint32_t categories;
+    double rate[8], weight[8];
+    const uint8_t *site_class;         /* NULL: mixture */
+    uint64_t site_classes;
+} ps_subst_model;
+typedef struct {
+    uint64_t pop_size, sites, merges;  /* as ps_likelihood_t */
+    uint64_t clamped_lengths, missing_cells;
+    uint64_t rounds, passes, rollbacks, converged;
+    uint64_t categories, classed;      /* K; 1 iff site_class was given */
+    double lnl, start_lnl, tree_length;
+    double beta, mean_rate;            /* 1 - sum pi_a^2; sum_k w_k r_k (reported, not enforced) */
+} ps_model_likelihood_t;
+/* One pass on one core handle (the reference has no such function; population.rs:531, :201-203).  site_mant, site_rate: sites
+ * f64, site_exp: sites i32, branch_g, branch_h, branch_q: pop_size + merges f64 (the root's 0); each may be NULL and then costs
+ * nothing -- no down pass (and no second phase of a mixture site) runs unless a branch output is asked for.  A site-shard core
+ * handle answers for its own sites.  Ordered behind the handle's queued work; changes no state.  PS_ERR_NO_DEVICE before
+ * anything else when no GPU is visible; PS_ERR_OOM names the bytes. */
+int ps_tree_model_likelihood(ps_population *core, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                             const ps_subst_model *model, ps_model_likelihood_t *out, double *site_mant, int32_t *site_exp,
+                             double *site_rate, double *branch_g, double *branch_h, double *branch_q);
+/* The same on the core matrix of a simulation (the reference has no such function; population.rs:531, :201-203) */
+int ps_sim_tree_model_likelihood(ps_sim *s, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                                 const ps_subst_model *model, ps_model_likelihood_t *out, double *site_mant, int32_t *site_exp,
+                                 double *site_rate, double *branch_g, double *branch_h, double *branch_q);
+/* The same for a sharded run (the reference has no such function; population.rs:531, :201-203): every shard passes over its own
+ * sites with its slice of site_class, the per-site arrays are concatenated, lnL, g, h and q add on the host in shard order. */
+int ps_multi_tree_model_likelihood(ps_multi *m, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                                   const ps_subst_model *model, ps_model_likelihood_t *out, double *site_mant, int32_t *site_exp,
+                                   double *site_rate, double *branch_g, double *branch_h, double *branch_q);
+/* Maximum-likelihood branch lengths under the model (the reference has no such function; population.rs:531, :201-203): the loop,
+ * the step limits, the rollback and the stopping rules of ps_tree_ml_lengths, fed with (dlnL/dt, d2lnL/dt2) of the model.  A
+ * reversible model (root == freq bit for bit) folds the right root child's length into the left's and holds it at
+ * PS_LIK_MIN_LENGTH; otherwise both root branches are optimised. */
+int ps_tree_model_ml_lengths(ps_population *core, const uint32_t *left, const uint32_t *right, const double *length_in, uint64_t merges,
+                             const ps_subst_model *model, const ps_ml_params *prm, ps_model_likelihood_t *out, double *length_out,
+                             double *round_lnl, uint64_t round_cap);
+/* The same on the core matrix of a simulation (the reference has no such function; population.rs:531, :201-203) */
+int ps_sim_tree_model_ml_lengths(ps_sim *s, const uint32_t *left, const uint32_t *right, const double *length_in, uint64_t merges,
+                                 const ps_subst_model *model, const ps_ml_params *prm, ps_model_likelihood_t *out, double *length_out,
+                                 double *round_lnl, uint64_t round_cap);
+/* The same for a sharded run (the reference has no such function; population.rs:531, :201-203): one Newton step on the sums of
+ * the shards. */
+int ps_multi_tree_model_ml_lengths(ps_multi *m, const uint32_t *left, const uint32_t *right, const double *length_in, uint64_t merges,
+                                   const ps_subst_model *model, const ps_ml_params *prm, ps_model_likelihood_t *out, double *length_out,
+                                   double *round_lnl, uint64_t round_cap);
+/* device ms of the last ps_tree_model_likelihood or ps_tree_model_ml_lengths on this core handle, summed over its passes (HIP
+ * events; the reference has no such function; population.rs:531): the uploads, the kernel, the sum of the workgroups' rows.
+ * Its own slots: ps_tree_likelihood_timing keeps its meaning.  PS_ERR_STATE before any call. */
+int ps_tree_model_timing(ps_population *core, double *schedule_ms, double *pass_ms, double *reduce_ms);
+/* One pass on the host (no device is touched; the reference has no such function; population.rs:531, :201-203), through the same
+ * subst_rule.h functions as the kernel, the sites summed in ascending order.  rows: individual-major pop_size x cols bytes. */
+int ps_model_likelihood_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right,
+                                  const double *length, uint64_t merges, const ps_subst_model *model, ps_model_likelihood_t *out,
+                                  double *site_mant, int32_t *site_exp, double *site_rate, double *branch_g, double *branch_h,
+                                  double *branch_q);
+/* The optimiser on the host (no device is touched; the reference has no such function; population.rs:531, :201-203) */
+int ps_model_ml_lengths_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right,
+                                  const double *length_in, uint64_t merges, const ps_subst_model *model, const ps_ml_params *prm,
+                                  ps_model_likelihood_t *out, double *length_out, double *round_lnl, uint64_t round_cap);
+/* Start lengths from the branch_changes of ps_tree_parsimony over `sites` sites under freq[4] (host only; the reference has no
+ * such function; population.rs:531): with p = changes / sites, -beta ln(1 - p / beta); PS_LIK_MAX_LENGTH from p = 0.98 beta on,
+ * PS_LIK_MIN_LENGTH without sites. */
+int ps_f81_lengths_from_changes(const uint64_t *branch_changes, uint64_t nodes, uint64_t sites, const double *freq, double *length);
+
 #ifdef __cplusplus
 }
 #endif

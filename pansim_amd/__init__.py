@@ -21,6 +21,8 @@ from .parsimony import (PS_PARS_BINS, PS_PARS_MAX_POP, TreeParsimony, merges_fro
 from .search import PS_NNI_MAX_POP, PS_NNI_NONE, ParsimonySearch, merges_canonical, nni_apply, nni_deltas_from_rows, nni_from_rows  # noqa: F401
 from .likelihood import (PS_LIK_MAX_LENGTH, PS_LIK_MAX_POP, PS_LIK_MIN_LENGTH, MlLengths, TreeLikelihood, jc_lengths_from_changes,  # noqa: F401
                          likelihood_from_rows, ml_lengths_from_rows)
+from .models import (PS_MODEL_MAX_CATEGORIES, PS_MODEL_MAX_POP_DERIV, ModelLikelihood, ModelMlLengths, SubstModel,  # noqa: F401
+                     f81_lengths_from_changes, gamma_bounds, gamma_rates, model_likelihood_from_rows, model_ml_lengths_from_rows)
 from .tree_compare import TreeComparison, levels_from_heights, tree_compare_from_merges  # noqa: F401
 from .simulation import (DEFAULTS, MultiSimulation, Simulation, derive, make_params, sample_pairs,  # noqa: F401
                          selection_coefficients, state_info, validate)

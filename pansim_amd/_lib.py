@@ -303,6 +303,29 @@ _LIK = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(Likelihood)] + [C.c_void_p] * 4
 _ML = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(MlParams), C.POINTER(Likelihood)] + [C.c_void_p] * 2 + [C.c_uint64]
 
 
+PS_MODEL_MAX_CATEGORIES, PS_MODEL_MAX_POP_DERIV = 8, 1536
+
+
+class SubstModelC(C.Structure):
+    """ps_subst_model: F81 base frequencies, the root distribution, the rate categories and the optional site classes
+    (docs/TREE_MODEL.md)"""
+    _fields_ = [("freq", C.c_double * 4), ("root", C.c_double * 4), ("categories", C.c_uint32), ("rate", C.c_double * 8),
+                ("weight", C.c_double * 8), ("site_class", C.c_void_p), ("site_classes", C.c_uint64)]
+
+
+class ModelLikelihood(C.Structure):
+    """ps_model_likelihood_t: the summary of ps_tree_model_likelihood / ps_tree_model_ml_lengths and their host restatements"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "sites", "merges", "clamped_lengths", "missing_cells", "rounds", "passes",
+                                                 "rollbacks", "converged", "categories", "classed")] + \
+               [(name, C.c_double) for name in ("lnl", "start_lnl", "tree_length", "beta", "mean_rate")]
+
+
+# the tree, the lengths, merges, the model, the summary, site_mant, site_exp, site_rate, branch_g, branch_h, branch_q
+_MODEL = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(SubstModelC), C.POINTER(ModelLikelihood)] + [C.c_void_p] * 6
+# the tree, the start lengths, merges, the model, the parameters, the summary, length_out, round_lnl, round_cap
+_MODEL_ML = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(SubstModelC), C.POINTER(MlParams), C.POINTER(ModelLikelihood)] + [C.c_void_p] * 2 + [C.c_uint64]
+
+
 class TreeCompareParams(C.Structure):
     """ps_tree_compare_params"""
     _fields_ = [("bins_a", C.c_uint32), ("bins_b", C.c_uint32), ("span_a", C.c_uint64), ("span_b", C.c_uint64), ("triplets", C.c_int32)]
@@ -523,6 +546,16 @@ SIGNATURES = {
     "ps_likelihood_from_rows": (_int, [_vp, _u64, _u64] + _LIK),
     "ps_ml_lengths_from_rows": (_int, [_vp, _u64, _u64] + _ML),
     "ps_jc_lengths_from_changes": (_int, [_vp, _u64, _u64, _vp]),
+    "ps_tree_model_likelihood": (_int, [_vp] + _MODEL),
+    "ps_sim_tree_model_likelihood": (_int, [_vp] + _MODEL),
+    "ps_multi_tree_model_likelihood": (_int, [_vp] + _MODEL),
+    "ps_tree_model_ml_lengths": (_int, [_vp] + _MODEL_ML),
+    "ps_sim_tree_model_ml_lengths": (_int, [_vp] + _MODEL_ML),
+    "ps_multi_tree_model_ml_lengths": (_int, [_vp] + _MODEL_ML),
+    "ps_tree_model_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_model_likelihood_from_rows": (_int, [_vp, _u64, _u64] + _MODEL),
+    "ps_model_ml_lengths_from_rows": (_int, [_vp, _u64, _u64] + _MODEL_ML),
+    "ps_f81_lengths_from_changes": (_int, [_vp, _u64, _u64, _vp, _vp]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

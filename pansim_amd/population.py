@@ -1039,6 +1039,28 @@ class Population:
         tree_likelihood() or tree_ml_lengths() on this core handle, summed over its passes"""
         return _timing(self._lib.ps_tree_likelihood_timing, 3, self._h)
 
+    def tree_model_likelihood(self, left, right, lengths, model, per_site=False, derivatives=False):
+        """The likelihood of the tree under `model` (a SubstModel: F81 base frequencies, a root distribution, rate categories) over
+        the sites of this core population, in one pass (ps_tree_model_likelihood; docs/TREE_MODEL.md) -> a ModelLikelihood.
+        `per_site`: every site's likelihood and posterior mean rate; `derivatives`: the sums behind the first and second derivative
+        with respect to every branch (pop_size <= PS_MODEL_MAX_POP_DERIV).  `model.site_class`: one entry per site of this handle."""
+        from .models import _model_call
+        return _model_call(self._lib.ps_tree_model_likelihood, left, right, lengths, model, self.size, self.ncols, per_site, derivatives, self._h)
+
+    def tree_model_ml_lengths(self, left, right, model, lengths=None, max_rounds=50, eps_lnl=1e-3):
+        """Maximum-likelihood branch lengths of the tree under `model` by the damped Newton steps of tree_ml_lengths
+        (ps_tree_model_ml_lengths; docs/TREE_MODEL.md) -> a ModelMlLengths.  `lengths`: the start lengths (None: the F81 correction
+        of the parsimony changes of every branch, f81_lengths_from_changes of tree_parsimony)."""
+        from .models import _model_ml_call, _model_start_lengths
+        if lengths is None:
+            lengths = _model_start_lengths(self, left, right, model)
+        return _model_ml_call(self._lib.ps_tree_model_ml_lengths, left, right, lengths, model, self.size, max_rounds, eps_lnl, self._h)
+
+    def tree_model_timing(self):
+        """device ms of (the uploads, the kernels, the sums of the workgroups' rows) of the last tree_model_likelihood() or
+        tree_model_ml_lengths() on this core handle, summed over its passes"""
+        return _timing(self._lib.ps_tree_model_timing, 3, self._h)
+
     def tree_compare(self, a, b, bins=(32, 32), spans=(0, 0), triplets=True, values=None):
         """How well tree `b` recovers tree `a` over the pop_size leaves of this handle (ps_tree_compare;
         docs/TREE_COMPARISON.md) -> a TreeComparison: the cophenetic agreement over all pairs, the rooted triplets both

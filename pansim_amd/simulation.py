@@ -309,6 +309,27 @@ class _Likelihood:
         """device ms of (the uploads, the kernels, the sums of the rows) of the last tree_likelihood() or tree_ml_lengths()"""
         return self._timed.core_genome.tree_likelihood_timing()
 
+    def tree_model_likelihood(self, left, right, lengths, model, per_site=False, derivatives=False):
+        """Population.tree_model_likelihood() of the run's core matrix (ps_sim_tree_model_likelihood /
+        ps_multi_tree_model_likelihood; docs/TREE_MODEL.md) -> a ModelLikelihood.  `model.site_class`: one entry per core site of
+        the whole run."""
+        from .models import _model_call
+        return _model_call(self._entry("tree_model_likelihood"), left, right, lengths, model, self.params.pop_size, self._core_width, per_site,
+                           derivatives, self._h)
+
+    def tree_model_ml_lengths(self, left, right, model, lengths=None, max_rounds=50, eps_lnl=1e-3):
+        """Population.tree_model_ml_lengths() of the run's core matrix (ps_sim_tree_model_ml_lengths /
+        ps_multi_tree_model_ml_lengths) -> a ModelMlLengths; without `lengths` the start is the F81 correction of the run's
+        tree_parsimony() on the same tree"""
+        from .models import _model_ml_call, _model_start_lengths
+        if lengths is None:
+            lengths = _model_start_lengths(self, left, right, model)
+        return _model_ml_call(self._entry("tree_model_ml_lengths"), left, right, lengths, model, self.params.pop_size, max_rounds, eps_lnl, self._h)
+
+    def tree_model_timing(self):
+        """device ms of (the uploads, the kernels, the sums of the rows) of the last tree_model_likelihood() or tree_model_ml_lengths()"""
+        return self._timed.core_genome.tree_model_timing()
+
 
 class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search, _Likelihood):
     """State of main() between main.rs:259 and :553 for one process (one GPU)."""
