@@ -1688,6 +1688,107 @@ int ps_model_ml_lengths_from_rows(const uint8_t *rows, uint64_t pop_size, uint64
  * PS_LIK_MIN_LENGTH without sites. */
 int ps_f81_lengths_from_changes(const uint64_t *branch_changes, uint64_t nodes, uint64_t sites, const double *freq, double *length);
 
+/* Likelihood tree search (docs/LIKELIHOOD_SEARCH.md): nearest-neighbour interchanges of a spanning tree with branch lengths
+ * towards a local optimum of its likelihood under ps_subst_model over the core sites -- the likelihood twin of ps_tree_nni.  The
+ * reference has no such function (its trees are implicit in the parent draws of population.rs:443; the process is its core
+ * mutation, population.rs:531, from the founding genome of population.rs:201-203).
+ * Tree, lengths, clamp, states and model: as ps_tree_model_likelihood takes them, 2 <= pop_size <= PS_MODEL_NNI_MAX_POP (4 LDS
+ * bytes per leaf and 140 per merge); else PS_ERR_INVALID.  Candidates, kinds and the root's edge: the table of ps_tree_nni.
+ * An interchange changes none of the four pieces around its edge -- the messages of the three subtrees and the message from
+ * above -- nor any length: every subtree keeps the length of the branch above it, the edge keeps its own, the root stays on its
+ * edge.  So one pass gives, per candidate, the exact ratio of the likelihood of the neighbour tree to this tree's:
+ *   site ratio        assigned: l' / l of the class; mixture: sum_k post_sk l'_sk / l_sk, k ascending (= l'_s / l_s); a category
+ *                     of likelihood 0 adds nothing; a site of likelihood 0 in this tree is left out of every product
+ *   delta_mant/exp    [2 k + kind] of merge k: the product of the site ratios as mantissa in [1/2, 1) times 2^exp, multiplied
+ *                     and rescaled after every site (frexp; no log per site); the gain is log(mant) + exp ln 2; mant = 0.0
+ *                     where there is no candidate
+ * Every site ratio is the same bits on host and device (pansim_amd/csrc/subst_rule.h); the products are taken in a fixed order
+ * per device (a repeated call returns the same bits) and differ from the host's by their grouping only.
+ * Search: from the canonical form of the start tree (ps_merges_canonical, the lengths carried with their nodes), per round:
+ * with length_rounds > 0 up to that many rounds of the optimiser of ps_tree_model_ml_lengths (eps_lnl = eps_gain), one pass,
+ * the candidates with gain > eps_gain in (gain descending, node, kind) order taken greedily while the nodes they touch are
+ * unmarked, at most moves_per_round (0: no cap); a batch of several whose tree (after its own length rounds) has lnL below
+ * this tree's lnL + the best gain is discarded (a rollback) and the best candidate applied alone.  It ends at a tree without
+ * such a candidate (local_optimum = 1), after max_rounds rounds, or when a round fails to raise lnL.  A start tree whose lnL
+ * is not finite is PS_ERR_INVALID. */
+#define PS_MODEL_NNI_MAX_POP 1024u
+typedef struct {
+    uint32_t max_rounds;               /* >= 1 */
+    uint32_t moves_per_round;          /* 0 = no cap */
+    uint32_t length_rounds;            /* 0 = the lengths are never re-optimised */
+    double eps_gain;                   /* > 0: a candidate must gain more */
+} ps_ml_nni_params;
+typedef struct {
+    uint64_t pop_size, sites, merges;  /* N; core sites this result covers; N - 1 */
+    uint64_t rounds, passes;           /* accepted rounds; passes of the search kernel = rounds + rollbacks + 1 (+ 1 when a round failed) */
+    uint64_t length_passes;            /* passes of the likelihood kernel: the start tree's lnL and the length rounds */
+    uint64_t rollbacks, moves;         /* discarded batches; interchanges applied in all rounds */
+    uint64_t local_optimum;            /* 1 iff the returned tree has no candidate above eps_gain */
+    uint64_t candidates_last;          /* candidates above eps_gain of the last pass */
+    uint64_t zero_sites;               /* sites of likelihood 0 in the returned tree */
+    uint64_t clamped_lengths, missing_cells;
+    double start_lnl, lnl;             /* lnL of the start tree with the lengths given, and of the returned tree and lengths */
+} ps_ml_nni_t;
+/* One pass on the list as given, not canonicalised (the reference has no such function; population.rs:443, :531): *lnl,
+ * delta_mant, delta_exp: 2 merges values each, *zero_sites (may be NULL) = the sites of likelihood 0.  A site-shard core handle
+ * answers for its own sites.  Ordered behind the handle's queued work; changes no state.  PS_ERR_NO_DEVICE before anything else
+ * when no GPU is visible; PS_ERR_OOM names the bytes. */
+int ps_tree_model_nni_deltas(ps_population *core, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                             const ps_subst_model *model, double *lnl, double *delta_mant, int64_t *delta_exp, uint64_t *zero_sites);
+/* The same on the core matrix of a simulation (the reference has no such function; population.rs:443, :531) */
+int ps_sim_tree_model_nni_deltas(ps_sim *s, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                                 const ps_subst_model *model, double *lnl, double *delta_mant, int64_t *delta_exp, uint64_t *zero_sites);
+/* The same for a sharded run (the reference has no such function; population.rs:443, :531): every shard passes over its own
+ * sites, the shards' products multiply on the host in shard order, lnL adds. */
+int ps_multi_tree_model_nni_deltas(ps_multi *m, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                                   const ps_subst_model *model, double *lnl, double *delta_mant, int64_t *delta_exp, uint64_t *zero_sites);
+/* The search on one core handle (the reference has no such function; population.rs:443, :531).  out_left, out_right: the
+ * returned tree, canonical, merges values each; length_out: pop_size + merges values, its lengths (the root's 0); round_lnl:
+ * max_rounds + 1 values, [0] = lnL of the first pass, [r] = after round r, strictly increasing; move_*: move_cap values each,
+ * move i of round move_round[i] (from 1) is candidate (move_node[i], move_kind[i]) of that round's canonical tree with
+ * move_gain[i].  Every array may be NULL (the move arrays with move_cap = 0).  Selection and surgery run on the host.  Ordered
+ * behind the handle's queued work; changes no state. */
+int ps_tree_model_nni(ps_population *core, const uint32_t *left, const uint32_t *right, const double *length_in, uint64_t merges,
+                      const ps_subst_model *model, const ps_ml_nni_params *prm, ps_ml_nni_t *out, uint32_t *out_left, uint32_t *out_right,
+                      double *length_out, double *round_lnl, uint32_t *move_round, uint32_t *move_node, uint32_t *move_kind,
+                      double *move_gain, uint64_t move_cap);
+/* The same on the core matrix of a simulation (the reference has no such function; population.rs:443, :531) */
+int ps_sim_tree_model_nni(ps_sim *s, const uint32_t *left, const uint32_t *right, const double *length_in, uint64_t merges,
+                          const ps_subst_model *model, const ps_ml_nni_params *prm, ps_ml_nni_t *out, uint32_t *out_left, uint32_t *out_right,
+                          double *length_out, double *round_lnl, uint32_t *move_round, uint32_t *move_node, uint32_t *move_kind,
+                          double *move_gain, uint64_t move_cap);
+/* The same for a sharded run (the reference has no such function; population.rs:443, :531): one selection on the combined
+ * products, one Newton step on the sums of the shards. */
+int ps_multi_tree_model_nni(ps_multi *m, const uint32_t *left, const uint32_t *right, const double *length_in, uint64_t merges,
+                            const ps_subst_model *model, const ps_ml_nni_params *prm, ps_ml_nni_t *out, uint32_t *out_left, uint32_t *out_right,
+                            double *length_out, double *round_lnl, uint32_t *move_round, uint32_t *move_node, uint32_t *move_kind,
+                            double *move_gain, uint64_t move_cap);
+/* device ms of the search kernel's passes of the last ps_tree_model_nni or ps_tree_model_nni_deltas on this core handle, summed
+ * (each shard's own after the ps_multi form; HIP events; the reference has no such function; population.rs:443): the uploads,
+ * the kernels, the products of the workgroups' rows.  The length rounds report to ps_tree_model_timing.  PS_ERR_STATE before
+ * any call. */
+int ps_tree_model_nni_timing(ps_population *core, double *schedule_ms, double *pass_ms, double *reduce_ms);
+/* One pass on the host (no device is touched; the reference has no such function; population.rs:443, :531), through the same
+ * subst_rule.h functions as the kernel, the sites multiplied in ascending order.  rows: individual-major pop_size x cols bytes. */
+int ps_model_nni_deltas_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right,
+                                  const double *length, uint64_t merges, const ps_subst_model *model, double *lnl, double *delta_mant,
+                                  int64_t *delta_exp, uint64_t *zero_sites);
+/* The search on the host (no device is touched; the reference has no such function; population.rs:443, :531): the same loop,
+ * selection, surgery and length rounds as ps_tree_model_nni over host passes. */
+int ps_model_nni_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right,
+                           const double *length_in, uint64_t merges, const ps_subst_model *model, const ps_ml_nni_params *prm,
+                           ps_ml_nni_t *out, uint32_t *out_left, uint32_t *out_right, double *length_out, double *round_lnl,
+                           uint32_t *move_round, uint32_t *move_node, uint32_t *move_kind, double *move_gain, uint64_t move_cap);
+/* The canonical form of a spanning merge list with its lengths (host only; the reference has no such function;
+ * population.rs:443): a length belongs to the node below its branch and follows it to its new id.  length, length_out: pop_size
+ * + merges values. */
+int ps_merges_canonical_lengths(const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges, uint64_t pop_size,
+                                uint32_t *out_left, uint32_t *out_right, double *length_out);
+/* Candidate (node, kind) of the list as given applied, the result and its lengths in canonical form (host only; the reference
+ * has no such function; population.rs:443): every subtree keeps the length of the branch above it. */
+int ps_nni_apply_lengths(const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges, uint64_t pop_size, uint32_t node,
+                         uint32_t kind, uint32_t *out_left, uint32_t *out_right, double *length_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -326,6 +326,28 @@ _MODEL = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(SubstModelC), C.POINTER(Model
 _MODEL_ML = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(SubstModelC), C.POINTER(MlParams), C.POINTER(ModelLikelihood)] + [C.c_void_p] * 2 + [C.c_uint64]
 
 
+PS_MODEL_NNI_MAX_POP = 1024
+
+
+class MlNniParams(C.Structure):
+    """ps_ml_nni_params: the limits of ps_tree_model_nni (docs/LIKELIHOOD_SEARCH.md)"""
+    _fields_ = [("max_rounds", C.c_uint32), ("moves_per_round", C.c_uint32), ("length_rounds", C.c_uint32), ("eps_gain", C.c_double)]
+
+
+class MlNni(C.Structure):
+    """ps_ml_nni_t: the summary of ps_tree_model_nni / ps_model_nni_from_rows"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "sites", "merges", "rounds", "passes", "length_passes", "rollbacks", "moves",
+                                                 "local_optimum", "candidates_last", "zero_sites", "clamped_lengths", "missing_cells")] + \
+               [(name, C.c_double) for name in ("start_lnl", "lnl")]
+
+
+# the tree, the lengths, merges, the model, lnl, delta_mant, delta_exp, zero_sites: the tail of every entry that makes one search pass
+_MNNI_DELTAS = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(SubstModelC), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+# the tree, the start lengths, merges, the model, the parameters, the summary, the returned tree, length_out, round_lnl, the four
+# move arrays, move_cap
+_MNNI = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(SubstModelC), C.POINTER(MlNniParams), C.POINTER(MlNni)] + [C.c_void_p] * 8 + [C.c_uint64]
+
+
 class TreeCompareParams(C.Structure):
     """ps_tree_compare_params"""
     _fields_ = [("bins_a", C.c_uint32), ("bins_b", C.c_uint32), ("span_a", C.c_uint64), ("span_b", C.c_uint64), ("triplets", C.c_int32)]
@@ -556,6 +578,17 @@ SIGNATURES = {
     "ps_model_likelihood_from_rows": (_int, [_vp, _u64, _u64] + _MODEL),
     "ps_model_ml_lengths_from_rows": (_int, [_vp, _u64, _u64] + _MODEL_ML),
     "ps_f81_lengths_from_changes": (_int, [_vp, _u64, _u64, _vp, _vp]),
+    "ps_tree_model_nni_deltas": (_int, [_vp] + _MNNI_DELTAS),
+    "ps_sim_tree_model_nni_deltas": (_int, [_vp] + _MNNI_DELTAS),
+    "ps_multi_tree_model_nni_deltas": (_int, [_vp] + _MNNI_DELTAS),
+    "ps_tree_model_nni": (_int, [_vp] + _MNNI),
+    "ps_sim_tree_model_nni": (_int, [_vp] + _MNNI),
+    "ps_multi_tree_model_nni": (_int, [_vp] + _MNNI),
+    "ps_tree_model_nni_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_model_nni_deltas_from_rows": (_int, [_vp, _u64, _u64] + _MNNI_DELTAS),
+    "ps_model_nni_from_rows": (_int, [_vp, _u64, _u64] + _MNNI),
+    "ps_merges_canonical_lengths": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "ps_nni_apply_lengths": (_int, [_vp, _vp, _vp, _u64, _u64, _u32, _u32, _vp, _vp, _vp]),
     "ps_multi_set_site_weights": (_int, [_vp, _vp, _vp, _vp]),
     "ps_multi_write": (_int, [_vp, C.c_char_p]),
 }

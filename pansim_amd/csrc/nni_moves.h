@@ -142,3 +142,68 @@ static std::vector<nni_candidate> nni_select(const nni_topology &t, const int64_
     }
     return batch;
 }
+
+// ---- branch lengths and binary64 gains: the likelihood search (ps_tree_model_nni; docs/LIKELIHOOD_SEARCH.md) ----
+// A length belongs to the node below its branch, and every node keeps its id through nni_apply_move: a move carries
+// length[N + M] along as it is.  Only the canonical form renumbers.  (inline: a program that includes this header for the
+// parsimony rules alone does not use them.)
+
+// nni_to_canonical with the lengths carried to the new ids: length_out[new id of x] = length_in[x] (the root's too)
+static inline void nni_to_canonical_lengths(const nni_topology &t, const double *length_in, uint32_t *left, uint32_t *right, double *length_out)
+{
+    const uint32_t N = t.N, M = N - 1u;
+    nni_to_canonical(t, left, right);
+    // the new id of every old node, children first: the merge of the canonical list that joins the new ids of its two children
+    std::vector<std::pair<uint64_t, uint32_t>> joins(M);
+    for (uint32_t k = 0; k < M; k++) joins[k] = { ((uint64_t)std::min(left[k], right[k]) << 32) | std::max(left[k], right[k]), N + k };
+    std::sort(joins.begin(), joins.end());
+    std::vector<uint32_t> id((size_t)N + M, NNI_NO_NODE), order, stack;
+    for (uint32_t i = 0; i < N; i++) id[i] = i;
+    if (M) stack.push_back(t.root);
+    while (!stack.empty()) {
+        const uint32_t x = stack.back();
+        stack.pop_back();
+        order.push_back(x);
+        for (uint32_t c : { t.left(x), t.right(x) })
+            if (c >= N) stack.push_back(c);
+    }
+    for (size_t i = order.size(); i-- > 0;) {
+        const uint32_t x = order[i], l = id[t.left(x)], r = id[t.right(x)];
+        const uint64_t key = ((uint64_t)std::min(l, r) << 32) | std::max(l, r);
+        id[x] = std::lower_bound(joins.begin(), joins.end(), std::make_pair(key, 0u))->second;
+    }
+    for (uint32_t x = 0; x < N + M; x++) length_out[id[x]] = length_in[x];
+}
+
+struct nni_gain_candidate {
+    double gain;
+    uint32_t node, kind;
+};
+
+// The round's batch over binary64 gains: the candidates of gain[2 M] (NaN: no candidate) with gain > eps in (gain descending,
+// node, kind) order, taken greedily while no node they touch is marked, at most `cap` (0: no cap).  *improving = their number
+// before the selection.  The first of the batch is the best candidate.
+static inline std::vector<nni_gain_candidate> nni_select_gains(const nni_topology &t, const double *gain, double eps, uint32_t cap, uint64_t *improving)
+{
+    const uint32_t N = t.N, M = N - 1u;
+    std::vector<nni_gain_candidate> all, batch;
+    for (uint32_t k = 0; k < M; k++)
+        for (uint32_t kind = 0; kind < 2u; kind++)
+            if (gain[2u * k + kind] > eps) all.push_back({ gain[2u * k + kind], N + k, kind });
+    std::sort(all.begin(), all.end(), [](const nni_gain_candidate &a, const nni_gain_candidate &b) {
+        return a.gain != b.gain ? a.gain > b.gain : a.node != b.node ? a.node < b.node : a.kind < b.kind;
+    });
+    *improving = all.size();
+    std::vector<uint8_t> marked((size_t)N + M, 0);
+    for (const nni_gain_candidate &c : all) {
+        if (cap && batch.size() >= cap) break;
+        uint32_t touched[7];
+        const uint32_t n = nni_touched(t, c.node, touched);
+        bool is_free = n != 0u;
+        for (uint32_t i = 0; i < n; i++) is_free = is_free && !marked[touched[i]];
+        if (!is_free) continue;
+        for (uint32_t i = 0; i < n; i++) marked[touched[i]] = 1;
+        batch.push_back(c);
+    }
+    return batch;
+}

@@ -114,3 +114,83 @@ PS_JC_FN double ps_subst_length_from_changes(uint64_t changes, uint64_t sites, d
     if (p >= 0.98 * beta) return PS_LIK_MAX_LENGTH;
     return -beta * log(1.0 - p / beta);
 }
+
+// ---- the likelihood of a neighbour tree (docs/LIKELIHOOD_SEARCH.md) ----
+// An internal edge v - c, c = (a, b), with sibling s: the four pieces around it are the messages m^a, m^b, m^s (ps_subst_up of the
+// inside partials) and T(v), the message into v from above (rho at the root).  A nearest-neighbour interchange regroups them into
+// an inside pair I (joined below the edge) and an outside pair O (joined above it) and changes none of them, nor x_c.
+
+// the join of two pieces, NOT rescaled: the three arrangements of an edge share one scale, so their ratios need no exponent
+PS_JC_FN void ps_subst_pair(const double a[4], const double b[4], double out[4])
+{
+    out[0] = a[0] * b[0];
+    out[1] = a[1] * b[1];
+    out[2] = a[2] * b[2];
+    out[3] = a[3] * b[3];
+}
+
+// the site likelihood with I below and O above an edge with x, up to the common power of two: (1 - x)(pi . I)(sum O) + x sum O_a I_a,
+// the shape of ps_subst_ratio's denominator, a sum of non-negative terms
+PS_JC_FN double ps_subst_nni_lik(double x, const double pi[4], const double I[4], const double O[4])
+{
+    const double A = ps_subst_dot(pi, I) * ps_jc_sum(O);
+    const double D = (O[0] * I[0] + O[1] * I[1]) + (O[2] * I[2] + O[3] * I[3]);
+    return (1.0 - x) * A + x * D;
+}
+
+// the same on the root's edge, the root between c (x_c, I below it) and s (x_s, O below it): sum_a rho_a up(x_c, I)_a up(x_s, O)_a
+PS_JC_FN double ps_subst_nni_root(double xc, double xs, const double pi[4], const double rho[4], const double I[4], const double O[4])
+{
+    double u[4], w[4];
+    ps_subst_up(xc, pi, I, u);
+    ps_subst_up(xs, pi, O, w);
+    return ((rho[0] * u[0]) * w[0] + (rho[1] * u[1]) * w[1]) + ((rho[2] * u[2]) * w[2] + (rho[3] * u[3]) * w[3]);
+}
+
+// The three arrangements below an inner node, (m^a, m^b | m^s, T(v)): l[0] the tree as it stands, l[1] kind 0 (b <-> s:
+// (a, s | b, T)), l[2] kind 1 (a <-> s: (s, b | a, T))
+PS_JC_FN void ps_subst_nni_edge(double x, const double pi[4], const double px[4], const double py[4], const double pz[4], const double pw[4],
+                                double l[3])
+{
+    double I[4], O[4];
+    ps_subst_pair(px, py, I);
+    ps_subst_pair(pz, pw, O);
+    l[0] = ps_subst_nni_lik(x, pi, I, O);
+    ps_subst_pair(px, pz, I);
+    ps_subst_pair(py, pw, O);
+    l[1] = ps_subst_nni_lik(x, pi, I, O);
+    ps_subst_pair(pz, py, I);
+    ps_subst_pair(px, pw, O);
+    l[2] = ps_subst_nni_lik(x, pi, I, O);
+}
+
+// The three arrangements on the root's edge, c = (a, b) with x_c beside s = (p, q) with x_s, both keeping their lengths: l[0] the
+// tree as it stands, l[1] kind 0 (b <-> p: c = (a, p), s = (b, q)), l[2] kind 1 (b <-> q: c = (a, q), s = (p, b))
+PS_JC_FN void ps_subst_nni_root_edge(double xc, double xs, const double pi[4], const double rho[4], const double pa[4], const double pb[4],
+                                     const double pp[4], const double pq[4], double l[3])
+{
+    double I[4], O[4];
+    ps_subst_pair(pa, pb, I);
+    ps_subst_pair(pp, pq, O);
+    l[0] = ps_subst_nni_root(xc, xs, pi, rho, I, O);
+    ps_subst_pair(pa, pp, I);
+    ps_subst_pair(pb, pq, O);
+    l[1] = ps_subst_nni_root(xc, xs, pi, rho, I, O);
+    ps_subst_pair(pa, pq, I);
+    ps_subst_pair(pp, pb, O);
+    l[2] = ps_subst_nni_root(xc, xs, pi, rho, I, O);
+}
+
+// What category k adds to a site's ratio l' / l of an interchange: post_k (l'_k / l_k); a category whose likelihood is 0 in this tree
+// adds nothing (its posterior is 0 and its ratio 0 / 0).  An assigned site has post = 1: the ratio itself.
+PS_JC_FN double ps_subst_nni_term(double post, double lk, double l0) { return l0 > 0.0 ? post * (lk / l0) : 0.0; }
+
+// A running product kept as (mantissa in [1/2, 1), exponent): the mantissa times r, rescaled; *k = the binary exponent taken out,
+// which the caller adds to the product's.  One (1/2, 1) is the empty product.  frexp is exact.
+PS_JC_FN double ps_subst_prod(double mant, double r, int32_t *k)
+{
+    int e = 0;
+    const double m = frexp(mant * r, &e);
+    *k = (int32_t)e;
+    return m;
+}

@@ -1056,6 +1056,30 @@ class Population:
             lengths = _model_start_lengths(self, left, right, model)
         return _model_ml_call(self._lib.ps_tree_model_ml_lengths, left, right, lengths, model, self.size, max_rounds, eps_lnl, self._h)
 
+    def model_nni_deltas(self, left, right, lengths, model):
+        """One pass of the likelihood tree search on the merge list as given (ps_tree_model_nni_deltas;
+        docs/LIKELIHOOD_SEARCH.md) -> a ModelNniDeltas: `lnl` of the tree under `model` over the sites of this core population and
+        `delta[k, kind]`, the exact change of lnL under interchange (pop_size + k, kind), NaN where there is no candidate"""
+        from .ml_search import _deltas_call
+        return _deltas_call(self._lib.ps_tree_model_nni_deltas, left, right, lengths, model, self.size, self._h)
+
+    def tree_model_nni(self, left, right, model, lengths=None, max_rounds=1000, moves_per_round=0, length_rounds=5, eps_gain=1e-3):
+        """Nearest-neighbour interchanges of the spanning tree (left, right) with branch lengths towards a local optimum of its
+        likelihood under `model` over the sites of this core population (ps_tree_model_nni; docs/LIKELIHOOD_SEARCH.md) -> a
+        LikelihoodSearch.  `lengths`: the start lengths (None: the F81 correction of the parsimony changes); `length_rounds`: rounds
+        of tree_model_ml_lengths before every pass (0: the lengths travel with their subtrees unchanged)."""
+        from .ml_search import _search_call
+        from .models import _model_start_lengths
+        if lengths is None:
+            lengths = _model_start_lengths(self, left, right, model)
+        return _search_call(self._lib.ps_tree_model_nni, left, right, lengths, model, self.size, max_rounds, moves_per_round, length_rounds,
+                            eps_gain, self._h)
+
+    def tree_model_nni_timing(self):
+        """device ms of (the uploads, the kernels, the products of the workgroups' rows) of the search passes of the last
+        tree_model_nni() or model_nni_deltas() on this core handle, summed"""
+        return _timing(self._lib.ps_tree_model_nni_timing, 3, self._h)
+
     def tree_model_timing(self):
         """device ms of (the uploads, the kernels, the sums of the workgroups' rows) of the last tree_model_likelihood() or
         tree_model_ml_lengths() on this core handle, summed over its passes"""

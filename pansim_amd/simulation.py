@@ -326,6 +326,27 @@ class _Likelihood:
             lengths = _model_start_lengths(self, left, right, model)
         return _model_ml_call(self._entry("tree_model_ml_lengths"), left, right, lengths, model, self.params.pop_size, max_rounds, eps_lnl, self._h)
 
+    def model_nni_deltas(self, left, right, lengths, model):
+        """Population.model_nni_deltas() of the run's core matrix (ps_sim_tree_model_nni_deltas / ps_multi_tree_model_nni_deltas;
+        docs/LIKELIHOOD_SEARCH.md) -> a ModelNniDeltas"""
+        from .ml_search import _deltas_call
+        return _deltas_call(self._entry("tree_model_nni_deltas"), left, right, lengths, model, self.params.pop_size, self._h)
+
+    def tree_model_nni(self, left, right, model, lengths=None, max_rounds=1000, moves_per_round=0, length_rounds=5, eps_gain=1e-3):
+        """Population.tree_model_nni() of the run's core matrix (ps_sim_tree_model_nni / ps_multi_tree_model_nni) -> a
+        LikelihoodSearch; without `lengths` the start is the F81 correction of the run's parsimony changes"""
+        from .ml_search import _search_call
+        from .models import _model_start_lengths
+        if lengths is None:
+            lengths = _model_start_lengths(self, left, right, model)
+        return _search_call(self._entry("tree_model_nni"), left, right, lengths, model, self.params.pop_size, max_rounds, moves_per_round,
+                            length_rounds, eps_gain, self._h)
+
+    def tree_model_nni_timing(self):
+        """device ms of (the uploads, the kernels, the products of the rows) of the search passes of the last tree_model_nni() or
+        model_nni_deltas()"""
+        return self._timed.core_genome.tree_model_nni_timing()
+
     def tree_model_timing(self):
         """device ms of (the uploads, the kernels, the sums of the rows) of the last tree_model_likelihood() or tree_model_ml_lengths()"""
         return self._timed.core_genome.tree_model_timing()
