@@ -1789,6 +1789,66 @@ int ps_merges_canonical_lengths(const uint32_t *left, const uint32_t *right, con
 int ps_nni_apply_lengths(const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges, uint64_t pop_size, uint32_t node,
                          uint32_t kind, uint32_t *out_left, uint32_t *out_right, double *length_out);
 
+/* Marginal ancestral states (docs/ANCESTRAL_STATES.md): the sequences at the inner nodes of a spanning tree with branch lengths,
+ * reconstructed under ps_subst_model.  The reference has no such function (its ancestors are overwritten generation by
+ * generation, population.rs:443; the process is its core mutation, population.rs:531, from the founding genome of
+ * population.rs:201-203).  Tree, lengths, clamp, states, missing-data rule and model: as ps_tree_model_likelihood takes them;
+ * the list is spanning (merges = pop_size - 1) and is not canonicalised: node pop_size + k is merge k as given.
+ * pop_size <= PS_ANC_MAX_POP for assigned sites (site_class given, or one category: 12 LDS bytes per leaf and 56 per merge),
+ * <= PS_ANC_MAX_POP_MIX for a mixture (32 more per merge); else PS_ERR_INVALID.
+ *   node posterior    in a category, from T (the message into the node from above, rho at the root) and the messages ml, mr of
+ *                     its children: w_a = (T_a ml_a) mr_a, p_a = w_a / sum_a w_a; a mixture site: p_a = sum_k post_sk p_{k,a}, k
+ *                     ascending, post of ps_tree_model_likelihood; a category whose sum is 0 adds nothing
+ *   state             per (site, inner node) the one-hot byte 1 << argmax_a p_a, exact ties to the lowest a; byte 0 where
+ *                     pmax < min_posterior (counted in masked_cells; min_posterior = 0 masks nothing)
+ *   node_conf[k]      sum_s pmax of merge k (masked cells included)
+ *   branch_diff[c]    sum_s of the posterior probability that the two ends of the branch above node c differ,
+ *                     sum_k post_sk (1 - x) max(A - S, 0) / ((1 - x) A + x D), S = sum_a pi_a (U_a L_a); the root's 0
+ * A site of likelihood 0 in this tree (an assigned invariant class at a variable site) is byte 0 at every node, adds nothing to
+ * any sum and is counted in zero_sites.  Every cell's posterior is the same bits on host and device
+ * (pansim_amd/csrc/subst_rule.h); sums over sites are taken in a fixed order per device. */
+#define PS_ANC_MAX_POP 2304u
+#define PS_ANC_MAX_POP_MIX 1536u
+typedef struct {
+    uint64_t pop_size, sites, merges;  /* N; core sites this result covers; N - 1 */
+    uint64_t categories, classed;      /* K; 1 iff site_class was given */
+    uint64_t masked_cells, zero_sites;
+    uint64_t missing_cells, clamped_lengths;   /* as ps_model_likelihood_t */
+    double lnl;                        /* as ps_tree_model_likelihood returns it */
+    double mean_conf;                  /* sum node_conf / (merges (sites - zero_sites)) */
+    double total_diff;                 /* sum branch_diff */
+} ps_ancestral_t;
+/* One pass on one core handle (the reference has no such function; population.rs:443, :531, :201-203).  *anc: a NEW core handle
+ * of pop_size = merges with the source's ncols, col_offset, global_cols and core_genes, made as ps_population_pool makes one (a
+ * stream of its own, output order = internal order, no rates set), row k = node pop_size + k, filled on the device; destroyed with
+ * ps_population_destroy in any order relative to its source; its one-hot flag is set only if the source's is and no cell was
+ * written 0.  anc may be NULL: no matrix is allocated or stored.  node_conf: merges f64, branch_diff: pop_size + merges f64; each
+ * may be NULL.  A site-shard core handle answers for its own sites.  The source is read behind its queued work and never written.
+ * PS_ERR_NO_DEVICE before anything else when no GPU is visible; PS_ERR_OOM names the bytes. */
+int ps_tree_ancestral_states(ps_population *core, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                             const ps_subst_model *model, double min_posterior, ps_ancestral_t *out, ps_population **anc, double *node_conf,
+                             double *branch_diff);
+/* The same on the core matrix of a simulation (the reference has no such function; population.rs:443, :531); site_class goes by
+ * the global site */
+int ps_sim_tree_ancestral_states(ps_sim *s, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                                 const ps_subst_model *model, double min_posterior, ps_ancestral_t *out, ps_population **anc,
+                                 double *node_conf, double *branch_diff);
+/* The same for a sharded run (the reference has no such function; population.rs:443, :531): *anc is a WHOLE handle on shard 0's
+ * device, every shard's block of site rows placed as ps_multi_subset places it; the sums add on the host in shard order. */
+int ps_multi_tree_ancestral_states(ps_multi *m, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                                   const ps_subst_model *model, double min_posterior, ps_ancestral_t *out, ps_population **anc,
+                                   double *node_conf, double *branch_diff);
+/* device ms of the last ps_tree_ancestral_states on this core handle (each shard's own after the ps_multi form; HIP events; the
+ * reference has no such function; population.rs:443): the uploads, the kernel with its stores, the sum of the workgroups' rows.
+ * PS_ERR_STATE before any call. */
+int ps_ancestral_states_timing(ps_population *core, double *upload_ms, double *pass_ms, double *reduce_ms);
+/* One pass on the host (no device is touched; the reference has no such function; population.rs:443, :531), through the same
+ * subst_rule.h functions as the kernel, the sites summed in ascending order.  rows: individual-major pop_size x cols bytes;
+ * anc_rows (may be NULL): individual-major merges x cols bytes, row k = node pop_size + k. */
+int ps_ancestral_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right,
+                           const double *length, uint64_t merges, const ps_subst_model *model, double min_posterior, ps_ancestral_t *out,
+                           uint8_t *anc_rows, double *node_conf, double *branch_diff);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ from .models import (PS_MODEL_MAX_CATEGORIES, PS_MODEL_MAX_POP_DERIV, ModelLikel
                      f81_lengths_from_changes, gamma_bounds, gamma_rates, model_likelihood_from_rows, model_ml_lengths_from_rows)
 from .ml_search import (PS_MODEL_NNI_MAX_POP, LikelihoodSearch, ModelNniDeltas, merges_canonical_lengths, model_nni_deltas_from_rows,  # noqa: F401
                         model_nni_from_rows, nni_apply_lengths)
+from .ancestral import PS_ANC_MAX_POP, PS_ANC_MAX_POP_MIX, AncestralStates, ancestral_from_rows  # noqa: F401
 from .tree_compare import TreeComparison, levels_from_heights, tree_compare_from_merges  # noqa: F401
 from .simulation import (DEFAULTS, MultiSimulation, Simulation, derive, make_params, sample_pairs,  # noqa: F401
                          selection_coefficients, state_info, validate)

@@ -348,6 +348,20 @@ _MNNI_DELTAS = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(SubstModelC), C.POINTER
 _MNNI = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(SubstModelC), C.POINTER(MlNniParams), C.POINTER(MlNni)] + [C.c_void_p] * 8 + [C.c_uint64]
 
 
+PS_ANC_MAX_POP, PS_ANC_MAX_POP_MIX = 2304, 1536
+
+
+class Ancestral(C.Structure):
+    """ps_ancestral_t: the summary of ps_tree_ancestral_states / ps_ancestral_from_rows (docs/ANCESTRAL_STATES.md)"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "sites", "merges", "categories", "classed", "masked_cells", "zero_sites",
+                                                 "missing_cells", "clamped_lengths")] + \
+               [(name, C.c_double) for name in ("lnl", "mean_conf", "total_diff")]
+
+
+# the tree, the lengths, merges, the model, min_posterior, the summary, the new handle (or the host rows), node_conf, branch_diff
+_ANC = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(SubstModelC), C.c_double, C.POINTER(Ancestral)] + [C.c_void_p] * 3
+
+
 class TreeCompareParams(C.Structure):
     """ps_tree_compare_params"""
     _fields_ = [("bins_a", C.c_uint32), ("bins_b", C.c_uint32), ("span_a", C.c_uint64), ("span_b", C.c_uint64), ("triplets", C.c_int32)]
@@ -585,6 +599,11 @@ SIGNATURES = {
     "ps_sim_tree_model_nni": (_int, [_vp] + _MNNI),
     "ps_multi_tree_model_nni": (_int, [_vp] + _MNNI),
     "ps_tree_model_nni_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_tree_ancestral_states": (_int, [_vp] + _ANC),
+    "ps_sim_tree_ancestral_states": (_int, [_vp] + _ANC),
+    "ps_multi_tree_ancestral_states": (_int, [_vp] + _ANC),
+    "ps_ancestral_states_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_ancestral_from_rows": (_int, [_vp, _u64, _u64] + _ANC),
     "ps_model_nni_deltas_from_rows": (_int, [_vp, _u64, _u64] + _MNNI_DELTAS),
     "ps_model_nni_from_rows": (_int, [_vp, _u64, _u64] + _MNNI),
     "ps_merges_canonical_lengths": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp]),

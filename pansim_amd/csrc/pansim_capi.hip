@@ -188,7 +188,7 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
 // ms of the last call's timer groups (`timed`: a call has completed)
-enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_NJ, PS_RO_BOOT, PS_RO_NNI, PS_RO_LIK, PS_RO_MODEL, PS_RO_MODEL_NNI, PS_RO_COUNT };
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_NJ, PS_RO_BOOT, PS_RO_NNI, PS_RO_LIK, PS_RO_MODEL, PS_RO_MODEL_NNI, PS_RO_ANC, PS_RO_COUNT };
 struct readout_slot {
     void *d = nullptr;
     uint64_t cap = 0;       // (bytes)
@@ -359,6 +359,9 @@ struct ps_population {
     //                   x per slot and category, the handle's site classes and the per-site rates besides; ms: schedule, pass, reduce
     //   PS_RO_MODEL_NNI likelihood tree search (likelihood_search.h), on every core handle of the call: counts, lnL, the products per
     //                   candidate, the schedule, x, the site classes, one row of products per workgroup; ms: schedule, pass, reduce
+    //   PS_RO_ANC       ancestral states (ancestral_states.h), on every core handle of the call: the three counters, the summed row, the
+    //                   schedule, the level offsets, the merge of every entry, x, the site classes, one row of sums per workgroup; ms:
+    //                   uploads, pass, reduce
     readout_slot ro[PS_RO_COUNT];
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
     uint32_t mlst_band = 0;                 // loci per band of the fingerprint table of ps_allele_profiles, 0 = choose ("mlst_band")
@@ -5073,6 +5076,10 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 // ps_tree_model_ml_lengths, ps_model_likelihood_from_rows, ps_model_ml_lengths_from_rows, ps_f81_lengths_from_changes, ps_sim_* and ps_multi_*)
 #include "tree_model.h"
 #include "likelihood_search.h"
+
+// marginal ancestral states under the model as a new population handle (ps_tree_ancestral_states, ps_ancestral_from_rows,
+// ps_ancestral_states_timing, ps_sim_* and ps_multi_*)
+#include "ancestral_states.h"
 
 // comparison of two trees over all pairs of leaves (ps_tree_compare, ps_tree_compare_from_merges, ps_levels_from_heights, ps_sim_* and ps_multi_*)
 #include "tree_compare.h"

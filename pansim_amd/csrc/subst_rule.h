@@ -194,3 +194,55 @@ PS_JC_FN double ps_subst_prod(double mant, double r, int32_t *k)
     *k = (int32_t)e;
     return m;
 }
+
+// ---- marginal ancestral states (docs/ANCESTRAL_STATES.md) ----
+// The marginal posterior of an inner node from the three pieces that meet there -- T, the message into the node from above (rho at
+// the root), and the messages ml, mr of its two children: w_a = (T_a ml_a) mr_a, p_a = w_a / sum.  Returns the sum,
+// (w_0 + w_1) + (w_2 + w_3): the site likelihood of the category up to the pieces' powers of two.
+PS_JC_FN double ps_subst_node_post(const double T[4], const double ml[4], const double mr[4], double w[4])
+{
+    w[0] = (T[0] * ml[0]) * mr[0];
+    w[1] = (T[1] * ml[1]) * mr[1];
+    w[2] = (T[2] * ml[2]) * mr[2];
+    w[3] = (T[3] * ml[3]) * mr[3];
+    return (w[0] + w[1]) + (w[2] + w[3]);
+}
+
+// What category k adds to p_a of a node: post_k (w_a / sum); a category whose sum is 0 adds nothing.  An assigned site has post = 1.
+PS_JC_FN double ps_subst_post_term(double post, double w, double sum) { return sum > 0.0 ? post * (w / sum) : 0.0; }
+
+// Branch c with x, outside partial U (top of the branch) and inside partial L: the posterior probability that its two ends carry
+// different states, (1 - x) max(A - S, 0) / ((1 - x) A + x D) with A and D of ps_subst_ratio and S = sum_a pi_a (U_a L_a), the
+// products formed first.  A - S >= 0 in exact arithmetic: the max guards its rounding.  A denominator of 0 (a category of
+// likelihood 0) returns 0.
+PS_JC_FN double ps_subst_pdiff(double x, const double pi[4], const double U[4], const double L[4])
+{
+    const double A = ps_subst_dot(pi, L) * ps_jc_sum(U);
+    const double ul[4] = { U[0] * L[0], U[1] * L[1], U[2] * L[2], U[3] * L[3] };
+    const double D = (ul[0] + ul[1]) + (ul[2] + ul[3]);
+    const double S = ps_subst_dot(pi, ul);
+    const double y = 1.0 - x, den = y * A + x * D, d = A - S;
+    if (!(den > 0.0)) return 0.0;
+    return (y * (d > 0.0 ? d : 0.0)) / den;
+}
+
+// the index of the largest p_a, exact binary64 ties to the lowest a; *pmax = that p_a
+PS_JC_FN uint32_t ps_subst_map(const double p[4], double *pmax)
+{
+    uint32_t best = 0u;
+    double m = p[0];
+    if (p[1] > m) {
+        m = p[1];
+        best = 1u;
+    }
+    if (p[2] > m) {
+        m = p[2];
+        best = 2u;
+    }
+    if (p[3] > m) {
+        m = p[3];
+        best = 3u;
+    }
+    *pmax = m;
+    return best;
+}

@@ -1085,6 +1085,19 @@ class Population:
         tree_model_ml_lengths() on this core handle, summed over its passes"""
         return _timing(self._lib.ps_tree_model_timing, 3, self._h)
 
+    def ancestral_states(self, left, right, lengths, model, min_posterior=0.0, states=True):
+        """The marginal reconstruction of every inner node of the tree under `model` over the sites of this core population, in one
+        pass (ps_tree_ancestral_states; docs/ANCESTRAL_STATES.md) -> an AncestralStates whose `population` holds the merges
+        reconstructed genomes on the device (row k = node pop_size + k; None without `states`).  A cell whose largest posterior is
+        below `min_posterior` is written 0.  `model.site_class`: one entry per site of this handle."""
+        from .ancestral import _device_call
+        return _device_call(self._lib.ps_tree_ancestral_states, self, self.ncols, left, right, lengths, model, self.size, min_posterior, states, self._h)
+
+    def ancestral_states_timing(self):
+        """device ms of (the uploads, the kernel with its stores, the sums of the workgroups' rows) of the last ancestral_states()
+        on this core handle"""
+        return _timing(self._lib.ps_ancestral_states_timing, 3, self._h)
+
     def tree_compare(self, a, b, bins=(32, 32), spans=(0, 0), triplets=True, values=None):
         """How well tree `b` recovers tree `a` over the pop_size leaves of this handle (ps_tree_compare;
         docs/TREE_COMPARISON.md) -> a TreeComparison: the cophenetic agreement over all pairs, the rooted triplets both

@@ -351,6 +351,18 @@ class _Likelihood:
         """device ms of (the uploads, the kernels, the sums of the rows) of the last tree_model_likelihood() or tree_model_ml_lengths()"""
         return self._timed.core_genome.tree_model_timing()
 
+    def ancestral_states(self, left, right, lengths, model, min_posterior=0.0, states=True):
+        """Population.ancestral_states() of the run's core matrix (ps_sim_tree_ancestral_states / ps_multi_tree_ancestral_states;
+        docs/ANCESTRAL_STATES.md) -> an AncestralStates; a sharded run returns one whole Population on shard 0's device.
+        `model.site_class`: one entry per core site of the whole run."""
+        from .ancestral import _device_call
+        return _device_call(self._entry("tree_ancestral_states"), self._timed.core_genome, self._core_width, left, right, lengths, model,
+                            self.params.pop_size, min_posterior, states, self._h)
+
+    def ancestral_states_timing(self):
+        """device ms of (the uploads, the kernel with its stores, the sums of the rows) of the last ancestral_states()"""
+        return self._timed.core_genome.ancestral_states_timing()
+
 
 class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search, _Likelihood):
     """State of main() between main.rs:259 and :553 for one process (one GPU)."""
