@@ -1849,6 +1849,130 @@ int ps_ancestral_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols
                            const double *length, uint64_t merges, const ps_subst_model *model, double min_posterior, ps_ancestral_t *out,
                            uint8_t *anc_rows, double *node_conf, double *branch_diff);
 
+/* Gene gain and loss on a tree (docs/GENE_MODEL.md): the likelihood of the ACCESSORY matrix on a spanning tree with branch lengths
+ * under a two-state Markov chain per gene (0 = absent, 1 = present), its rates fitted, and the gene content of the inner nodes.
+ * The reference has no such function; the process is its gene gain / loss, a flip of a cell with p = (1 - exp(-2 lambda_c / |c|))
+ * / 2 per generation (population.rs:505), which is this model with pi = (1/2, 1/2) and r_c = lambda_c / |c| for t in
+ * generations, the compartments as rate classes.  P(t) = x I + y 1 pi^T, x = exp(-(r t) / beta), y = 1 - x formed as
+ * -expm1(-(r t) / beta) (full precision on the shortest branches), beta = 1 - pi_0^2 - pi_1^2: the gain rate is r pi_1 / beta, the
+ * loss rate r pi_0 / beta.
+ *   freq      pi: both entries > 0, summing to 1 within 1e-12;   root: rho, both > 0, summing to 1 within 1e-12
+ *   rate      r_k, finite and >= 0; weight: w_k > 0 summing to 1 within 1e-12; categories: 1 <= K <= 8
+ *   gene_class  NULL: every gene is a mixture of the K classes; else one u8 < K per gene and gene_classes = their count
+ * Anything else is PS_ERR_INVALID with a message that names the field.  Lengths: finite (else PS_ERR_INVALID), clamped below at
+ * 1e-8 (counted in clamped_lengths) and NOT above: a tree in generations is legitimate input.  The tree: as ps_tree_parsimony
+ * takes it, spanning (merges = pop_size - 1), leaf i = output row i; any byte but 0 of the host forms is present.
+ * pop_size <= PS_GENE_MAX_POP assigned (gene_class given, or one class), <= PS_GENE_MAX_POP_MIX for a mixture; else PS_ERR_INVALID.
+ *   gene likelihood   assigned: the class's (mant, exp); mixture, posterior and mean rate: as ps_tree_model_likelihood forms them
+ *   gene_post         genes x K: the class posteriors (assigned: 1 at the gene's class)
+ *   node posterior    w_a = (T_a ml_a) mr_a, p_a = w_a / (w_0 + w_1); mixture: sum_k post_k p_{k,a}, k ascending
+ *   state             1 iff p_1 > p_0 (an exact tie is absent); node_conf[k] = sum_g max(p_0, p_1), node_genes[k] = sum_g p_1 (the
+ *                     expected accessory genome size of the ancestor)
+ *   branch_gains[c]   sum_g sum_k post_k (U_0 (y pi_1)) L_1 / (y A + x D): the expected number of genes absent above
+ *                     and present below the branch above node c; branch_losses[c]: (U_1 (y pi_0)) L_0 likewise; the root's 0
+ *   gene_gains[g]     the same summed over the branches of gene g; gene_losses[g] likewise
+ * A gene of likelihood 0 (an assigned class of rate 0 at a variable gene) makes lnl -inf, is absent at every node, adds nothing to
+ * any sum and is counted in zero_genes.  Every gene's (mant, exp), posteriors, mean rate and states are the same bits on host and
+ * device (pansim_amd/csrc/gene_rule.h); sums over genes are taken in a fixed order per device.  The tuning key "gene_team" of the
+ * accessory handle forces the threads of a team (0 = choose, 64 or 256). */
+#define PS_GENE_MAX_POP 2304u
+#define PS_GENE_MAX_POP_MIX 1792u
+typedef struct {
+    double freq[2], root[2];
+    uint32_t categories;
+    double rate[8], weight[8];
+    const uint8_t *gene_class;         /* NULL: mixture */
+    uint64_t gene_classes;
+} ps_gene_model;
+typedef struct {
+    uint32_t fit_rates, fit_freq, fit_weights;   /* 0 / 1 each; fit_weights acts on a mixture only */
+    uint32_t max_rounds;               /* >= 1 */
+    double eps_lnl;                    /* > 0: a round that gains less ends the fit */
+} ps_gene_fit_params;
+typedef struct {
+    uint64_t pop_size, genes, merges;  /* N; G; N - 1 */
+    uint64_t categories, classed;      /* K; 1 iff gene_class was given */
+    uint64_t zero_genes, clamped_lengths;
+    uint64_t rounds, passes, converged;   /* the fit: rounds run, up passes, 1 iff a round gained less than eps_lnl */
+    double lnl, start_lnl;             /* start_lnl: the fit's lnL before the first round (else = lnl) */
+    double beta, mean_rate;            /* 1 - pi_0^2 - pi_1^2; sum_k w_k r_k */
+    double total_gains, total_losses;  /* sum branch_gains, sum branch_losses (the ancestral call) */
+    double mean_conf, total_genes;     /* sum node_conf / (merges (genes - zero_genes)); sum node_genes */
+} ps_gene_t;
+/* One up pass on an accessory handle (the reference has no such function; population.rs:505).  gene_mant, gene_rate: genes f64,
+ * gene_exp: genes i32, gene_post: genes x categories f64; each may be NULL and then costs nothing.  A core handle is
+ * PS_ERR_INVALID.  Ordered behind the handle's queued work; changes no state.  PS_ERR_NO_DEVICE before anything else when no GPU
+ * is visible; PS_ERR_OOM names the bytes. */
+int ps_tree_gene_likelihood(ps_population *acc, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                            const ps_gene_model *model, ps_gene_t *out, double *gene_mant, int32_t *gene_exp, double *gene_post,
+                            double *gene_rate);
+/* The same on the accessory matrix of a simulation (the reference has no such function; population.rs:505) */
+int ps_sim_tree_gene_likelihood(ps_sim *s, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                                const ps_gene_model *model, ps_gene_t *out, double *gene_mant, int32_t *gene_exp, double *gene_post,
+                                double *gene_rate);
+/* The same for a sharded run (the reference has no such function; population.rs:505): shard 0's accessory replica answers */
+int ps_multi_tree_gene_likelihood(ps_multi *m, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                                  const ps_gene_model *model, ps_gene_t *out, double *gene_mant, int32_t *gene_exp, double *gene_post,
+                                  double *gene_rate);
+/* The up and the down pass (the reference has no such function; population.rs:505).  *anc: a NEW accessory handle of pop_size
+ * = merges with the source's ncols and core_genes, made as ps_population_pool makes one (a stream of its own, no rates set), row k
+ * = node pop_size + k, both of its views filled on the device; destroyed with ps_population_destroy in any order relative to its
+ * source.  anc may be NULL: no matrix is allocated or stored.  node_conf, node_genes: merges f64; branch_gains, branch_losses:
+ * pop_size + merges f64; gene_gains, gene_losses: genes f64; each may be NULL.  The source is read behind its queued work and never
+ * written. */
+int ps_tree_gene_ancestral(ps_population *acc, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                           const ps_gene_model *model, ps_gene_t *out, ps_population **anc, double *node_conf, double *node_genes,
+                           double *branch_gains, double *branch_losses, double *gene_gains, double *gene_losses);
+/* The same on the accessory matrix of a simulation (the reference has no such function; population.rs:505) */
+int ps_sim_tree_gene_ancestral(ps_sim *s, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                               const ps_gene_model *model, ps_gene_t *out, ps_population **anc, double *node_conf, double *node_genes,
+                               double *branch_gains, double *branch_losses, double *gene_gains, double *gene_losses);
+/* The same for a sharded run (the reference has no such function; population.rs:505): shard 0's accessory replica answers */
+int ps_multi_tree_gene_ancestral(ps_multi *m, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                                 const ps_gene_model *model, ps_gene_t *out, ps_population **anc, double *node_conf, double *node_genes,
+                                 double *branch_gains, double *branch_losses, double *gene_gains, double *gene_losses);
+/* The fit of the rates, pi_1 and (a mixture) the weights from `model` as the start; rho and the lengths are never fitted (the
+ * reference has no such function; population.rs:505).  Derivative-free and deterministic.  Every 1-D search brackets the
+ * optimum from the current value by steps that double, then narrows by golden section, and keeps the best point it has seen.  Per
+ * round: the rates -- assigned classes: lnL = sum_k lnL_k and r_k touches lnL_k only, so the K searches on ln r_k advance in
+ * lockstep, one up pass evaluating one trial rate of every class; a mixture: the r_k in turn on the whole lnL; a rate of 0 is
+ * held -- then, a mixture, up to 8 EM updates w_k <- mean_g post_gk while each raises lnL, then pi_1 on logit pi_1.  lnL is formed
+ * on the host from the genes' (mant, exp) in ascending order: the device fit and ps_gene_fit_from_rows take the same decisions
+ * and return the same bits.  A round never ends below where it started; the fit ends when a round gains less than eps_lnl
+ * (converged = 1) or after max_rounds.  rate_out, weight_out: categories f64; freq_out: 2 f64; round_lnl: round_cap values, [0] =
+ * the start's lnL, [r] = after round r (as many as fit); each may be NULL. */
+int ps_tree_gene_fit(ps_population *acc, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                     const ps_gene_model *model, const ps_gene_fit_params *prm, ps_gene_t *out, double *rate_out, double *weight_out,
+                     double *freq_out, double *round_lnl, uint64_t round_cap);
+/* The same on the accessory matrix of a simulation (the reference has no such function; population.rs:505) */
+int ps_sim_tree_gene_fit(ps_sim *s, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                         const ps_gene_model *model, const ps_gene_fit_params *prm, ps_gene_t *out, double *rate_out, double *weight_out,
+                         double *freq_out, double *round_lnl, uint64_t round_cap);
+/* The same for a sharded run (the reference has no such function; population.rs:505): shard 0's accessory replica answers */
+int ps_multi_tree_gene_fit(ps_multi *m, const uint32_t *left, const uint32_t *right, const double *length, uint64_t merges,
+                           const ps_gene_model *model, const ps_gene_fit_params *prm, ps_gene_t *out, double *rate_out, double *weight_out,
+                           double *freq_out, double *round_lnl, uint64_t round_cap);
+/* device ms of the last of the three calls above on this accessory handle, summed over its passes (HIP events; the reference has
+ * no such function; population.rs:505): the uploads, the kernel with its stores and the transpose, the sum of the workgroups'
+ * rows.  PS_ERR_STATE before any call. */
+int ps_tree_gene_timing(ps_population *acc, double *upload_ms, double *pass_ms, double *reduce_ms);
+/* One up pass on the host (no device is touched; the reference has no such function; population.rs:505), through the same
+ * gene_rule.h functions as the kernel, the genes summed in ascending order.  rows: individual-major pop_size x cols bytes. */
+int ps_gene_likelihood_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right,
+                                 const double *length, uint64_t merges, const ps_gene_model *model, ps_gene_t *out, double *gene_mant,
+                                 int32_t *gene_exp, double *gene_post, double *gene_rate);
+/* The up and the down pass on the host (no device is touched; the reference has no such function; population.rs:505).
+ * anc_rows (may be NULL): individual-major merges x cols bytes 0 / 1, row k = node pop_size + k. */
+int ps_gene_ancestral_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right,
+                                const double *length, uint64_t merges, const ps_gene_model *model, ps_gene_t *out, uint8_t *anc_rows,
+                                double *node_conf, double *node_genes, double *branch_gains, double *branch_losses, double *gene_gains,
+                                double *gene_losses);
+/* The fit on the host (no device is touched; the reference has no such function; population.rs:505): the same loop over host
+ * passes. */
+int ps_gene_fit_from_rows(const uint8_t *rows, uint64_t pop_size, uint64_t cols, const uint32_t *left, const uint32_t *right,
+                          const double *length, uint64_t merges, const ps_gene_model *model, const ps_gene_fit_params *prm, ps_gene_t *out,
+                          double *rate_out, double *weight_out, double *freq_out, double *round_lnl, uint64_t round_cap);
+
 #ifdef __cplusplus
 }
 #endif

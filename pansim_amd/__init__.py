@@ -26,6 +26,8 @@ from .models import (PS_MODEL_MAX_CATEGORIES, PS_MODEL_MAX_POP_DERIV, ModelLikel
 from .ml_search import (PS_MODEL_NNI_MAX_POP, LikelihoodSearch, ModelNniDeltas, merges_canonical_lengths, model_nni_deltas_from_rows,  # noqa: F401
                         model_nni_from_rows, nni_apply_lengths)
 from .ancestral import PS_ANC_MAX_POP, PS_ANC_MAX_POP_MIX, AncestralStates, ancestral_from_rows  # noqa: F401
+from .gene_model import (PS_GENE_MAX_POP, PS_GENE_MAX_POP_MIX, GeneAncestral, GeneFit, GeneLikelihood, GeneModel,  # noqa: F401
+                         gene_ancestral_from_rows, gene_fit_from_rows, gene_likelihood_from_rows)
 from .tree_compare import TreeComparison, levels_from_heights, tree_compare_from_merges  # noqa: F401
 from .simulation import (DEFAULTS, MultiSimulation, Simulation, derive, make_params, sample_pairs,  # noqa: F401
                          selection_coefficients, state_info, validate)

@@ -362,6 +362,39 @@ class Ancestral(C.Structure):
 _ANC = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(SubstModelC), C.c_double, C.POINTER(Ancestral)] + [C.c_void_p] * 3
 
 
+PS_GENE_MAX_POP, PS_GENE_MAX_POP_MIX = 2304, 1792
+
+
+class GeneModelC(C.Structure):
+    """ps_gene_model: the two-state gain / loss chain of the accessory genes: pi, the root distribution, the rate classes and the
+    optional gene classes (docs/GENE_MODEL.md)"""
+    _fields_ = [("freq", C.c_double * 2), ("root", C.c_double * 2), ("categories", C.c_uint32), ("rate", C.c_double * 8),
+                ("weight", C.c_double * 8), ("gene_class", C.c_void_p), ("gene_classes", C.c_uint64)]
+
+
+class GeneFitParams(C.Structure):
+    """ps_gene_fit_params: what ps_tree_gene_fit fits and when it ends"""
+    _fields_ = [("fit_rates", C.c_uint32), ("fit_freq", C.c_uint32), ("fit_weights", C.c_uint32), ("max_rounds", C.c_uint32),
+                ("eps_lnl", C.c_double)]
+
+
+class GeneSummary(C.Structure):
+    """ps_gene_t: the summary of the ps_tree_gene_* entries and their host restatements"""
+    _fields_ = [(name, C.c_uint64) for name in ("pop_size", "genes", "merges", "categories", "classed", "zero_genes", "clamped_lengths",
+                                                 "rounds", "passes", "converged")] + \
+               [(name, C.c_double) for name in ("lnl", "start_lnl", "beta", "mean_rate", "total_gains", "total_losses", "mean_conf",
+                                                "total_genes")]
+
+
+# the tree, the lengths, merges, the model, the summary: the head of every gene entry; then gene_mant, gene_exp, gene_post, gene_rate
+_GENE = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(GeneModelC), C.POINTER(GeneSummary)]
+_GENE_LIK = _GENE + [C.c_void_p] * 4
+# ... the new handle (or the host rows), node_conf, node_genes, branch_gains, branch_losses, gene_gains, gene_losses
+_GENE_ANC = _GENE + [C.c_void_p] * 7
+# the tree, the lengths, merges, the model, the parameters, the summary, rate_out, weight_out, freq_out, round_lnl, round_cap
+_GENE_FIT = [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(GeneModelC), C.POINTER(GeneFitParams), C.POINTER(GeneSummary)] + [C.c_void_p] * 4 + [C.c_uint64]
+
+
 class TreeCompareParams(C.Structure):
     """ps_tree_compare_params"""
     _fields_ = [("bins_a", C.c_uint32), ("bins_b", C.c_uint32), ("span_a", C.c_uint64), ("span_b", C.c_uint64), ("triplets", C.c_int32)]
@@ -604,6 +637,19 @@ SIGNATURES = {
     "ps_multi_tree_ancestral_states": (_int, [_vp] + _ANC),
     "ps_ancestral_states_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "ps_ancestral_from_rows": (_int, [_vp, _u64, _u64] + _ANC),
+    "ps_tree_gene_likelihood": (_int, [_vp] + _GENE_LIK),
+    "ps_sim_tree_gene_likelihood": (_int, [_vp] + _GENE_LIK),
+    "ps_multi_tree_gene_likelihood": (_int, [_vp] + _GENE_LIK),
+    "ps_tree_gene_ancestral": (_int, [_vp] + _GENE_ANC),
+    "ps_sim_tree_gene_ancestral": (_int, [_vp] + _GENE_ANC),
+    "ps_multi_tree_gene_ancestral": (_int, [_vp] + _GENE_ANC),
+    "ps_tree_gene_fit": (_int, [_vp] + _GENE_FIT),
+    "ps_sim_tree_gene_fit": (_int, [_vp] + _GENE_FIT),
+    "ps_multi_tree_gene_fit": (_int, [_vp] + _GENE_FIT),
+    "ps_tree_gene_timing": (_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
+    "ps_gene_likelihood_from_rows": (_int, [_vp, _u64, _u64] + _GENE_LIK),
+    "ps_gene_ancestral_from_rows": (_int, [_vp, _u64, _u64] + _GENE_ANC),
+    "ps_gene_fit_from_rows": (_int, [_vp, _u64, _u64] + _GENE_FIT),
     "ps_model_nni_deltas_from_rows": (_int, [_vp, _u64, _u64] + _MNNI_DELTAS),
     "ps_model_nni_from_rows": (_int, [_vp, _u64, _u64] + _MNNI),
     "ps_merges_canonical_lengths": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp]),

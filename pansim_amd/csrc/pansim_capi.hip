@@ -188,7 +188,7 @@ static uint32_t acc_flip_threshold(double lam, uint64_t n_genes)
 // ---------------------------------------------------------------------------
 // What a handle keeps per device read-out (readout_common.h): the scratch from the first call on, grown as needed, and the device
 // ms of the last call's timer groups (`timed`: a call has completed)
-enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_NJ, PS_RO_BOOT, PS_RO_NNI, PS_RO_LIK, PS_RO_MODEL, PS_RO_MODEL_NNI, PS_RO_ANC, PS_RO_COUNT };
+enum { PS_RO_HIST, PS_RO_CLUSTERS, PS_RO_TREE, PS_RO_KNN, PS_RO_GEN, PS_RO_LD_SEL, PS_RO_LD, PS_RO_UPGMA, PS_RO_DIFF, PS_RO_PARS, PS_RO_TCMP, PS_RO_GS, PS_RO_MLST, PS_RO_NJ, PS_RO_BOOT, PS_RO_NNI, PS_RO_LIK, PS_RO_MODEL, PS_RO_MODEL_NNI, PS_RO_ANC, PS_RO_GENE, PS_RO_COUNT };
 struct readout_slot {
     void *d = nullptr;
     uint64_t cap = 0;       // (bytes)
@@ -362,7 +362,11 @@ struct ps_population {
     //   PS_RO_ANC       ancestral states (ancestral_states.h), on every core handle of the call: the three counters, the summed row, the
     //                   schedule, the level offsets, the merge of every entry, x, the site classes, one row of sums per workgroup; ms:
     //                   uploads, pass, reduce
+    //   PS_RO_GENE      gene gain / loss model (tree_genes.h), on the ACCESSORY handle asked: the counter, the summed row, the schedule,
+    //                   the level offsets, the merge of every entry, x, the gene classes, the per-gene arrays, one row of sums per
+    //                   workgroup; ms summed over the call's passes: uploads, pass, reduce
     readout_slot ro[PS_RO_COUNT];
+    uint32_t gene_team = 0;                 // threads of a team of tree_gene_kernel, 0 = choose, 64 or 256 ("gene_team")
     uint32_t ld_band = 0;                   // rows of loci per band (rounded up to 64), 0 = choose ("ld_band")
     uint32_t mlst_band = 0;                 // loci per band of the fingerprint table of ps_allele_profiles, 0 = choose ("mlst_band")
     // isolate samples (isolate_samples.h): on a source, the form of the core gather; on a handle that ps_population_pool / _subset
@@ -690,6 +694,9 @@ extern "C" int ps_set_tuning(ps_population *p, const char *key, int64_t value)
     } else if (k == "mlst_band") {
         if (value < 0 || value > 65535) return ps_fail(PS_ERR_INVALID, "mlst_band must be 0 (choose)..65535 loci");
         p->mlst_band = (uint32_t)value;
+    } else if (k == "gene_team") {
+        if (value != 0 && value != 64 && value != 256) return ps_fail(PS_ERR_INVALID, "gene_team must be 0 (choose), 64 or 256 threads");
+        p->gene_team = (uint32_t)value;
     } else if (k == "gather_form") {
         if (value < 0 || value > 2) return ps_fail(PS_ERR_INVALID, "gather_form must be 0 (choose), 1 (source rows staged in LDS) or 2 (bytes loaded from global memory)");
         p->gather_form = (int)value;
@@ -5080,6 +5087,11 @@ extern "C" int ps_multi_write(ps_multi *m, const char *outpref)
 // marginal ancestral states under the model as a new population handle (ps_tree_ancestral_states, ps_ancestral_from_rows,
 // ps_ancestral_states_timing, ps_sim_* and ps_multi_*)
 #include "ancestral_states.h"
+
+// gene gain and loss on a tree: the two-state likelihood of the accessory matrix, its rate fit and the ancestors' gene content as a new
+// population handle (ps_tree_gene_likelihood, ps_tree_gene_ancestral, ps_tree_gene_fit, ps_tree_gene_timing, ps_gene_*_from_rows,
+// ps_sim_* and ps_multi_*)
+#include "tree_genes.h"
 
 // comparison of two trees over all pairs of leaves (ps_tree_compare, ps_tree_compare_from_merges, ps_levels_from_heights, ps_sim_* and ps_multi_*)
 #include "tree_compare.h"

@@ -1098,6 +1098,33 @@ class Population:
         on this core handle"""
         return _timing(self._lib.ps_ancestral_states_timing, 3, self._h)
 
+    def tree_gene_likelihood(self, left, right, lengths, model, per_gene=False):
+        """The likelihood of the genes of this ACCESSORY population on the tree under the gain / loss `model` (a GeneModel), in one
+        up pass (ps_tree_gene_likelihood; docs/GENE_MODEL.md) -> a GeneLikelihood; `per_gene`: every gene's (mantissa,
+        exponent), class posteriors and posterior mean rate.  `lengths` are clamped below only: generations are fine."""
+        from .gene_model import _lik_call
+        return _lik_call(self._lib.ps_tree_gene_likelihood, left, right, lengths, model, self.size, self.ncols, per_gene, self._h)
+
+    def tree_gene_ancestral(self, left, right, lengths, model, states=True):
+        """The marginal gene content of every inner node of the tree under `model`, with the expected gains and losses of every
+        branch and gene (ps_tree_gene_ancestral) -> a GeneAncestral whose `population` is a new accessory Population of merges
+        rows on the device (row k = node pop_size + k; None without `states`)."""
+        from .gene_model import _anc_device_call
+        return _anc_device_call(self._lib.ps_tree_gene_ancestral, self, left, right, lengths, model, self.size, states, self._h)
+
+    def tree_gene_fit(self, left, right, lengths, model, fit_rates=True, fit_freq=True, fit_weights=True, max_rounds=50, eps_lnl=1e-3):
+        """The rates, pi_1 and (a mixture) the weights of `model` fitted to the genes of this accessory population on the tree,
+        derivative-free and deterministic (ps_tree_gene_fit) -> a GeneFit; equal bit for bit to gene_fit_from_rows on the same
+        matrix"""
+        from .gene_model import _fit_call
+        return _fit_call(self._lib.ps_tree_gene_fit, left, right, lengths, model, self.size, fit_rates, fit_freq, fit_weights, max_rounds,
+                         eps_lnl, self._h)
+
+    def tree_gene_timing(self):
+        """device ms of (the uploads, the kernels with their stores, the sums of the workgroups' rows) of the last tree_gene_*()
+        call on this accessory handle, summed over its passes"""
+        return _timing(self._lib.ps_tree_gene_timing, 3, self._h)
+
     def tree_compare(self, a, b, bins=(32, 32), spans=(0, 0), triplets=True, values=None):
         """How well tree `b` recovers tree `a` over the pop_size leaves of this handle (ps_tree_compare;
         docs/TREE_COMPARISON.md) -> a TreeComparison: the cophenetic agreement over all pairs, the rooted triplets both

@@ -8,6 +8,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Derived, SimParams, StateHeader, check
+from .gene_model import _GeneReadouts
 from .population import Population, fmt_f64, standard_deviation
 
 # flag names and defaults of main.rs:21-151
@@ -364,7 +365,7 @@ class _Likelihood:
         return self._timed.core_genome.ancestral_states_timing()
 
 
-class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search, _Likelihood):
+class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search, _Likelihood, _GeneReadouts):
     """State of main() between main.rs:259 and :553 for one process (one GPU)."""
     _prefix = "ps_sim_"
     _core_width = property(lambda self: self.core_genome.ncols)       # the shard's columns when it is a shard
@@ -519,7 +520,7 @@ class Simulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Boots
             self.pan_genome.write(outpref)
 
 
-class MultiSimulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search, _Likelihood):
+class MultiSimulation(_Readouts, _Associations, _Profiles, _Samples, _Joining, _Bootstrap, _Search, _Likelihood, _GeneReadouts):
     """The run sharded by core site inside ONE process (ps_multi): shard k on HIP device devices[k]
     (ordinals may repeat), one host thread per shard inside each call; results equal the unsharded run."""
     _prefix = "ps_multi_"
