@@ -238,45 +238,49 @@ int ps_calc_gene_freq(ps_population *p, double *out);
 int ps_write(ps_population *p, const char *outpref);
 /* wait for all queued device work of this handle */
 int ps_sync(ps_population *p);
-/* Launch tuning / test hooks (no reference counterpart).  Keys: "sweep_blocks_per_cu"
- * (resident 256-thread blocks per CU of the wave-per-row sweep, 1..8), "sweep_rows"
- * (2..4; accepted and ignored since round 6: a wave of that sweep takes the 4 sites of one level-1 block group per iteration),
- * "force_block_sweep" (0/1: use the block sweep even when a row fits one wavefront),
- * "force_inline_sweep" (0/1: use the queue-free inline block sweep), "pair_mode" (core
- * distances: 0 = choose by cost, 1 = sampled-pair kernel, 2 = all-pairs tiles + lookup, 3 = sampled-pair
- * kernel in its nibble form even for one-hot matrices, 4 = transposed bit strings streamed per pair -- the
- * sampled form of populations too wide for an LDS tile, 5 = all-pairs xor + popcount tiles even for one-hot matrices,
- * 6 = all pairs on the i8 matrix cores, 7 = all pairs on the FP4 path with three +-1 features per site; one-hot matrices go to the
- * matrix cores in modes 0 and 2 (FP4 form on one-hot nibbles), 6 and 7), "pair_ranges" (site ranges of the tiled
- * sampled-pair kernels, 0 = choose; the 16-bit counter cap still applies),
- * "davg_form" (average_distance: 0 = choose, 1 = LDS-tile popcount kernels, 2 = intersections on the matrix cores in one kernel --
- * the choice above pop_size 53248 --, 3 = the same in two phases, u16 counts then division + ordered fold -- the choice for row
- * shards and for 8192 < pop_size <= 53248), "davg_nb" (matrix-core forms: 32-individual fragments per wave, 0 = choose, 1, 2, or --
- * two-phase form only; the one-kernel form then chooses by itself -- 4), "davg_ib" (two-phase form: individuals per workgroup of the
- * division + fold phase, 0 = choose, 16 or 32),
- * "core_davg_form" (average_distance of the core matrix: 0 = choose, 1 = whole matrix -- FP4 all-pairs triangle, then the fold --,
- * 2 = banded -- FP4 rectangle of a band of rows, then the fold --, 3 = generic; matrices that are not one-hot always take 3),
- * "core_davg_band" (banded forms: rows per band, rounded up to a multiple of 256; 0 = choose),
- * "hgt_mode" (accessory recombination: 0 = choose, 1 = one atomic per event, 2 = two passes: bin
- * by recipient partition, OR in LDS images), "hgt_slices" (binned HGT: event slices, 0 = choose), "hgt_list_in_global" (0/1: donor gene lists in
- * global scratch instead of LDS; "hgt_bin_list_in_global": the same for the bin pass of the binned form),
- * "hgt_events_per_thread" (light HGT kernel inside the generation loop: events a thread handles in sequence -- the launch is that
- * narrow; 0 = whole chip; ps_sim sets it from the estimated sweep time),
- * "hgt_apply_threads" (binned HGT: threads per workgroup of the LDS-image pass, 256 / 512 / 1024), "window_blocks_per_cu" (window sweep:
- * workgroups per CU, 0 = choose), "davg_plain_division" (matrix-core D-avg: the compiler's f64 division in the epilogue),
- * "hgt_bin_cap" (tests: the bins of the binned HGT hold at most this many events; the rest take the overflow image),
- * "sweep_queue_cap" (tests: the sweeps treat their candidate queues and HR lists as this short, so that the queue-free
- * redo of a batch / row group -- what a full queue falls back to -- runs; 0 = real size),
- * "sweep_out_of_place" (core sweeps: -1 = choose, 0 = update the matrix in place, 1 = write the new generation to a second
- * buffer that then swaps roles with the first, 2 = the same with nontemporal row loads and stores; results are identical),
- * "lds_limit" (bytes of LDS a workgroup may use), "block_waves" (block sweep: waves per
- * workgroup, 0 = choose), "block_batch" (block sweep: segments per wave batch, 0 = choose, 2 or 4),
- * "no_block_preload" (block sweep: parent indices re-read per batch),
- * "sweep_generations" (core handle of a ps_sim: generations one launch of the wave sweep applies in ps_sim_run, 0 = choose,
- * 1 or 2; only where the wave sweep takes the loop's step -- pop_size <= 1024 -- and only for runs of at least that many
- * generations, everything else keeps one generation per launch; results are identical; the environment variable
- * PANSIM_SWEEP_GENERATIONS sets the same at creation). */
+/* Launch tuning / test hooks (no reference counterpart).  A refused value leaves the switch as it was (PS_ERR_INVALID).  The keys,
+ * one per line, in the order of ps_tuning_key:
+ *   "sweep_blocks_per_cu"     wave-per-row sweep: resident 256-thread blocks per CU, 1..8
+ *   "sweep_rows"              2..4; accepted and ignored since round 6: a wave of that sweep takes the 4 sites of one level-1 block group per iteration
+ *   "sweep_out_of_place"      core sweeps: -1 = choose, 0 = update the matrix in place, 1 = write the new generation to a second buffer that then swaps roles with the first, 2 = the same with nontemporal row loads and stores; results are identical
+ *   "hgt_apply_threads"       binned HGT: threads per workgroup of the LDS-image pass, 256 / 512 / 1024
+ *   "window_blocks_per_cu"    window sweep: workgroups per CU, 0 = choose, 1..8
+ *   "davg_form"               average_distance: 0 = choose, 1 = LDS-tile popcount kernels, 2 = intersections on the matrix cores in one kernel -- the choice above pop_size 53248 --, 3 = the same in two phases, u16 counts then division + ordered fold -- the choice for row shards and for 8192 < pop_size <= 53248
+ *   "core_davg_form"          average_distance of the core matrix: 0 = choose, 1 = whole matrix -- FP4 all-pairs triangle, then the fold --, 2 = banded -- FP4 rectangle of a band of rows, then the fold --, 3 = generic; matrices that are not one-hot always take 3
+ *   "ld_band"                 ps_locus_ld / ps_gene_site_ld: rows of loci per band (rounded up to 64), 0 = choose..65536
+ *   "mlst_band"               ps_allele_profiles: loci per band of the fingerprint table, 0 = choose..65535
+ *   "gene_team"               gene gain / loss model: threads of a team, 0 = choose, 64 or 256
+ *   "gather_form"             isolate samples, on the source: 0 = choose, 1 = source rows staged in LDS, 2 = bytes loaded from global memory
+ *   "core_davg_band"          core D-avg, banded forms: rows per band, rounded up to a multiple of 256; 0 = choose
+ *   "davg_plain_division"     0/1: matrix-core D-avg: the compiler's f64 division in the epilogue
+ *   "davg_ib"                 two-phase D-avg: individuals per workgroup of the division + fold phase, 0 = choose, 16 or 32
+ *   "davg_nb"                 matrix-core D-avg: 32-individual fragments per wave, 0 = choose, 1, 2, or -- two-phase form only; the one-kernel form then chooses by itself -- 4
+ *   "hgt_mode"                accessory recombination: 0 = choose, 1 = one atomic per event, 2 = two passes: bin by recipient partition, OR in LDS images
+ *   "pair_mode"               core distances: 0 = choose by cost, 1 = sampled-pair kernel, 2 = all-pairs tiles + lookup, 3 = sampled-pair kernel in its nibble form even for one-hot matrices, 4 = transposed bit strings streamed per pair -- the sampled form of populations too wide for an LDS tile, 5 = all-pairs xor + popcount tiles even for one-hot matrices, 6 = all pairs on the i8 matrix cores, 7 = all pairs on the FP4 path with three +-1 features per site; one-hot matrices go to the matrix cores in modes 0 and 2 (FP4 form on one-hot nibbles), 6 and 7
+ *   "pair_ranges"             site ranges of the tiled sampled-pair kernels, 0 = choose..65535; the 16-bit counter cap still applies
+ *   "force_block_sweep"       0/1: use the block sweep even when a row fits one wavefront
+ *   "force_inline_sweep"      0/1: use the queue-free inline block sweep
+ *   "hgt_slices"              binned HGT: event slices, 0 = choose..4096
+ *   "block_batch"             block sweep: segments per wave batch, 0 = choose, 2 or 4
+ *   "hgt_bin_cap"             tests: the bins of the binned HGT hold at most this many events, the rest take the overflow image; 0 = sized by the rates
+ *   "hgt_events_per_thread"   light HGT kernel inside the generation loop: events a thread handles in sequence -- the launch is that narrow; 0 = whole chip; ps_sim sets it from the estimated sweep time
+ *   "window_sweep"            window sweep for pop_size > 1024: -1 = choose, 0 = never (block sweep), 1 = wherever the parents are sorted
+ *   "sweep_generations"       core handle of a ps_sim: generations one launch of the wave sweep applies in ps_sim_run, 0 = choose, 1 or 2; only where the wave sweep takes the loop's step -- pop_size <= 1024 -- and only for runs of at least that many generations, everything else keeps one generation per launch; results are identical
+ *   "sweep_queue_cap"         tests: the sweeps treat their candidate queues and HR lists as this short, so that the queue-free redo of a batch / row group -- what a full queue falls back to -- runs; 0 = real size
+ *   "hgt_list_in_global"      0/1: light HGT: donor gene lists in global scratch instead of LDS
+ *   "hgt_bin_list_in_global"  0/1: the same for the bin pass of the binned HGT
+ *   "no_block_preload"        0/1: block sweep: parent indices re-read per batch
+ *   "block_waves"             block sweep: waves per workgroup, 0 = choose, 4, 8 or 16
+ *   "lds_limit"               bytes of LDS a workgroup may use, 1 KiB..160 KiB
+ *   "free_cus_per_xcd"        read only (ps_set_tuning does not know it; PANSIM_SWEEP_FREE_CUS at creation): CUs per XCD that the core stream's CU mask leaves to other streams, 0..8
+ *   "hgt_bin_prio"            read only (PANSIM_HGT_BIN_PRIO at creation): s_setprio level of the binned HGT's bin pass beside the sweep, 0..3
+ * The PANSIM_* environment variables that set a switch when a handle is created are listed in pansim_amd/csrc/tuning.h. */
 int ps_set_tuning(ps_population *p, const char *key, int64_t value);
+/* The value of a switch as it is now.  An accepted-and-ignored key ("sweep_rows") reads as what the library does whatever was
+ * set, 4, not as the last accepted value.  An unknown key: PS_ERR_INVALID. */
+int ps_get_tuning(ps_population *p, const char *key, int64_t *value);
+/* The key of switch `index` in the order above, NULL past the end.  No handle, no device. */
+const char *ps_tuning_key(uint32_t index);
 
 /* ------------------------------------------------------------------------ */
 /* free functions of the seam                                                */

@@ -52,7 +52,7 @@ static api *load()
     std::lock_guard<std::mutex> lock(mu);
     if (tried) return a.so ? &a : nullptr;
     tried = true;
-    const char *override_path = getenv("PANSIM_RCCL_LIBRARY");
+    const char *override_path = env_str("PANSIM_RCCL_LIBRARY");
     const char *names[] = { override_path, "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so" };
     void *so = nullptr;
     for (const char *n : names) {
@@ -179,7 +179,7 @@ extern "C" int ps_rccl_exchange_create(const uint8_t *id, int rank, int world, i
     x->rank = rank;
     x->world = world;
     x->device = device;
-    if (const char *e = getenv("PANSIM_RCCL_GATHER")) x->ring_gather = strcmp(e, "ring") == 0;
+    if (const char *e = env_str("PANSIM_RCCL_GATHER")) x->ring_gather = strcmp(e, "ring") == 0;
     ncclUniqueId uid;
     memcpy(&uid, id, sizeof(uid));
     ncclResult_t r = a->CommInitRank(&x->comm, world, uid, rank);       // (collective: every rank of the run is inside it)

@@ -293,7 +293,6 @@ struct ps_population {
     std::vector<uint32_t> h_r1, h_r2; // the caller's list the device copy was built from
     uint32_t lds_limit = 160 * 1024;
     uint32_t sweep_blocks_per_cu = 8;   // wave-per-row sweep: resident 256-thread blocks per CU (capped by LDS)
-    uint32_t sweep_rows = 4;            // (accepted and ignored since round 6: a wave takes the 4 sites of a level-1 block group per iteration)
     bool force_block_sweep = false;     // tests: run the block sweep on small populations
     bool force_inline_sweep = false;    // tests: run the inline (queue-free) block sweep
     uint32_t block_waves = 0;           // block sweep: waves per workgroup (0 = auto: 4, 8 or 16)
@@ -411,6 +410,8 @@ static int dev_grow(T *&ptr, uint64_t &cap, uint64_t need)
 
 // the device check, the scratch slots, the event timer and the grids that the read-outs share
 #include "readout_common.h"
+// the table of the tuning switches with ps_set_tuning / ps_get_tuning, and the reader of the environment
+#include "tuning.h"
 
 // a device allocation that lives for one call: freed on the device it was made on, on every way out
 template <class T>
@@ -477,7 +478,7 @@ extern "C" void ps_population_destroy(ps_population *p)
             (void)hipMemcpy(p->h_stamps, p->d_stamps, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
             (void)hipFree(p->d_stamps);
         }
-        if (getenv("PANSIM_PRINT_STAMPS"))
+        if (env_given("PANSIM_PRINT_STAMPS"))
             for (int k = 0; k < 32; k++) fprintf(stderr, "stamp[%d] = %llu\n", k, p->h_stamps[k]);
         (void)hipHostFree(p->h_stamps);
     }
@@ -497,12 +498,11 @@ static int pop_create_impl(const ps_config *cfg, const uint8_t *init_vec, ps_pop
         HIPCHK(hipGetDevice(&p->device));
     }
     PSCHK(use_device(p));
-    // PANSIM_SWEEP_FREE_CUS=n (experiment, round 5): the core stream is created with a CU mask that leaves n CUs of every
+    tuning_from_env(p);
+    // "free_cus_per_xcd" (experiment, round 5): the core stream is created with a CU mask that leaves n CUs of every
     // XCD to the other streams -- kernels that cannot share a SIMD with resident sweep waves (RCCL's 264-register
     // rcclGenericKernel) then start beside the sweep instead of behind it.  KFD deals mask bits round-robin over the XCCs
     // (bit b -> XCC b % 8): clearing the first 8 n bits takes n CUs from each (scripts/ubench/cu_mask.hip).
-    if (cfg->core)
-        if (const char *e = getenv("PANSIM_SWEEP_FREE_CUS")) p->free_cus_per_xcd = (uint32_t)std::max(0, std::min(8, atoi(e)));
     if (p->free_cus_per_xcd) {
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, p->device));
@@ -515,29 +515,6 @@ static int pop_create_impl(const ps_config *cfg, const uint8_t *init_vec, ps_pop
         }
     } else
     HIPCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    if (const char *e = getenv("PANSIM_SWEEP_BLOCKS_PER_CU")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= 8) p->sweep_blocks_per_cu = (uint32_t)v;
-    }
-    if (const char *e = getenv("PANSIM_SWEEP_GENERATIONS")) {
-        const int v = atoi(e);
-        if (v >= 0 && v <= (int)PS_SWEEP_MAX_GENS) p->sweep_generations = (uint32_t)v;
-    }
-    if (const char *e = getenv("PANSIM_HGT_MODE")) p->hgt_mode = atoi(e);
-    if (const char *e = getenv("PANSIM_SWEEP_OOP")) p->sweep_oop = std::max(-1, std::min(2, atoi(e)));
-    if (const char *e = getenv("PANSIM_WINDOW_SWEEP")) p->window_sweep = std::max(-1, std::min(1, atoi(e)));
-    if (const char *e = getenv("PANSIM_ACC_LDS_LIMIT")) { const int v = atoi(e); if (v >= 1024 && v <= 160 * 1024 && !cfg->core) p->lds_limit = (uint32_t)v; }
-    if (const char *e = getenv("PANSIM_HGT_APPLY_THREADS")) { const int v = atoi(e); if (v == 256 || v == 512 || v == 1024) p->hgt_apply_threads = (uint32_t)v; }
-    if (const char *e = getenv("PANSIM_WINDOW_BPC")) p->window_blocks_per_cu = (uint32_t)std::max(0, std::min(8, atoi(e)));
-    if (const char *e = getenv("PANSIM_BLOCK_BATCH")) p->block_batch = (uint32_t)atoi(e);
-    if (const char *e = getenv("PANSIM_BLOCK_WAVES")) p->block_waves = (uint32_t)atoi(e);
-    if (const char *e = getenv("PANSIM_HGT_SLICES")) p->hgt_slices = (uint32_t)atoi(e);
-    if (const char *e = getenv("PANSIM_HGT_BIN_LIST_GLOBAL")) p->hgt_bin_list_in_global = atoi(e) != 0;
-    if (const char *e = getenv("PANSIM_HGT_BIN_PRIO")) p->hgt_bin_prio = (uint32_t)std::max(0, std::min(3, atoi(e)));
-    if (const char *e = getenv("PANSIM_SWEEP_ROWS")) {
-        const int v = atoi(e);
-        if (v >= 2 && v <= 4) p->sweep_rows = (uint32_t)v;
-    }
     const uint64_t N = cfg->pop_size, C = cfg->ncols;
     HIPCHK(hipMalloc(&p->d_idx, std::max<uint64_t>(N, 1) * sizeof(uint32_t)));
     HIPCHK(hipHostMalloc(&p->h_flag, sizeof(uint32_t), hipHostMallocMapped));
@@ -659,109 +636,6 @@ extern "C" int ps_sync(ps_population *p)
     if (!p) return ps_fail(PS_ERR_INVALID, "null handle");
     PSCHK(use_device(p));
     return sync_checked(p);
-}
-
-extern "C" int ps_set_tuning(ps_population *p, const char *key, int64_t value)
-{
-    if (!p || !key) return ps_fail(PS_ERR_INVALID, "null argument");
-    const std::string k(key);
-    if (k == "sweep_blocks_per_cu") {
-        if (value < 1 || value > 8) return ps_fail(PS_ERR_INVALID, "sweep_blocks_per_cu must be 1..8");
-        p->sweep_blocks_per_cu = (uint32_t)value;
-    } else if (k == "sweep_rows") {
-        if (value < 2 || value > 4) return ps_fail(PS_ERR_INVALID, "sweep_rows must be 2..4");
-        p->sweep_rows = (uint32_t)value;
-    } else if (k == "sweep_out_of_place") {
-        if (value < -1 || value > 2) return ps_fail(PS_ERR_INVALID, "sweep_out_of_place must be -1 (choose), 0 (in place), 1 (out of place) or 2 (out of place, nontemporal loads and stores)");
-        p->sweep_oop = (int)value;
-    } else if (k == "hgt_apply_threads") {
-        if (value != 256 && value != 512 && value != 1024) return ps_fail(PS_ERR_INVALID, "hgt_apply_threads must be 256, 512 or 1024");
-        p->hgt_apply_threads = (uint32_t)value;
-    } else if (k == "window_blocks_per_cu") {
-        if (value < 0 || value > 8) return ps_fail(PS_ERR_INVALID, "window_blocks_per_cu must be 0 (choose) or 1..8");
-        p->window_blocks_per_cu = (uint32_t)value;
-    } else if (k == "davg_form") {
-        if (value < 0 || value > 3)
-            return ps_fail(PS_ERR_INVALID, "davg_form must be 0 (choose), 1 (LDS-tile popcount kernels), 2 (matrix cores, one kernel) or 3 (matrix cores, two phases)");
-        p->davg_form = (int)value;
-    } else if (k == "core_davg_form") {
-        if (value < 0 || value > 3)
-            return ps_fail(PS_ERR_INVALID, "core_davg_form must be 0 (choose), 1 (whole matrix), 2 (banded) or 3 (generic)");
-        p->core_davg_form = (int)value;
-    } else if (k == "ld_band") {
-        if (value < 0 || value > 65536) return ps_fail(PS_ERR_INVALID, "ld_band must be 0 (choose)..65536 rows of loci");
-        p->ld_band = (uint32_t)value;
-    } else if (k == "mlst_band") {
-        if (value < 0 || value > 65535) return ps_fail(PS_ERR_INVALID, "mlst_band must be 0 (choose)..65535 loci");
-        p->mlst_band = (uint32_t)value;
-    } else if (k == "gene_team") {
-        if (value != 0 && value != 64 && value != 256) return ps_fail(PS_ERR_INVALID, "gene_team must be 0 (choose), 64 or 256 threads");
-        p->gene_team = (uint32_t)value;
-    } else if (k == "gather_form") {
-        if (value < 0 || value > 2) return ps_fail(PS_ERR_INVALID, "gather_form must be 0 (choose), 1 (source rows staged in LDS) or 2 (bytes loaded from global memory)");
-        p->gather_form = (int)value;
-    } else if (k == "core_davg_band") {
-        if (value < 0 || value > (1ll << 31)) return ps_fail(PS_ERR_INVALID, "core_davg_band must be 0 (choose)..2^31 rows");
-        p->core_davg_band = (uint32_t)value;
-    } else if (k == "davg_plain_division") {
-        p->davg_plain_division = value != 0;
-    } else if (k == "davg_ib") {
-        if (value != 0 && value != 16 && value != 32) return ps_fail(PS_ERR_INVALID, "davg_ib must be 0 (choose), 16 or 32");
-        p->davg_ib = (uint32_t)value;
-    } else if (k == "davg_nb") {
-        if (value < 0 || value > 4 || value == 3) return ps_fail(PS_ERR_INVALID, "davg_nb must be 0 (choose), 1, 2 or (two-phase form only) 4");
-        p->davg_nb = (uint32_t)value;
-    } else if (k == "hgt_mode") {
-        if (value < 0 || value > 2) return ps_fail(PS_ERR_INVALID, "hgt_mode must be 0 (auto), 1 (one atomic per event) or 2 (binned by recipient partition, two passes)");
-        p->hgt_mode = (int)value;
-    } else if (k == "pair_mode") {
-        if (value < 0 || value > 7) return ps_fail(PS_ERR_INVALID, "pair_mode must be 0 (auto), 1 (sampled), 2 (all pairs), 3 (sampled, nibble form even for one-hot matrices), 4 (transposed bit strings, streamed per pair), 5 (all pairs, xor + popcount tiles even for one-hot matrices), 6 (all pairs, i8 matrix cores when the matrix is one-hot; mode 2 takes the FP4 form) or 7 (the FP4 form on three +-1 features per site)");
-        p->pair_mode = (int)value;
-    } else if (k == "pair_ranges") {
-        if (value < 0 || value > 65535) return ps_fail(PS_ERR_INVALID, "pair_ranges must be 0 (choose)..65535");
-        p->pair_ranges = (uint32_t)value;
-    } else if (k == "force_block_sweep") {
-        p->force_block_sweep = value != 0;
-    } else if (k == "force_inline_sweep") {
-        p->force_inline_sweep = value != 0;
-    } else if (k == "hgt_slices") {
-        if (value < 0 || value > 4096) return ps_fail(PS_ERR_INVALID, "hgt_slices must be 0..4096");
-        p->hgt_slices = (uint32_t)value;
-    } else if (k == "block_batch") {
-        if (value != 0 && value != 2 && value != 4) return ps_fail(PS_ERR_INVALID, "block_batch must be 0 (choose), 2 or 4");
-        p->block_batch = (uint32_t)value;
-    } else if (k == "hgt_bin_cap") {
-        if (value < 0 || value > (1 << 30)) return ps_fail(PS_ERR_INVALID, "hgt_bin_cap must be 0 (sized by the rates)..2^30");
-        p->hgt_bin_cap = (uint32_t)value;
-    } else if (k == "hgt_events_per_thread") {
-        if (value < 0 || value > 100000) return ps_fail(PS_ERR_INVALID, "hgt_events_per_thread must be 0 (whole chip)..100000");
-        p->hgt_events_per_thread = (uint32_t)value;
-    } else if (k == "window_sweep") {
-        if (value < -1 || value > 1) return ps_fail(PS_ERR_INVALID, "window_sweep must be -1 (choose), 0 (block sweep) or 1 (window sweep where the parents are sorted)");
-        p->window_sweep = (int)value;
-    } else if (k == "sweep_generations") {
-        if (value < 0 || value > (int64_t)PS_SWEEP_MAX_GENS) return ps_fail(PS_ERR_INVALID, "sweep_generations must be 0 (choose), 1 or 2");
-        p->sweep_generations = (uint32_t)value;
-    } else if (k == "sweep_queue_cap") {
-        if (value < 0 || value > 65536) return ps_fail(PS_ERR_INVALID, "sweep_queue_cap must be 0 (real size)..65536");
-        p->sweep_queue_cap = (uint32_t)value;
-    } else if (k == "hgt_list_in_global") {
-        p->hgt_list_in_global = value != 0;
-    } else if (k == "hgt_bin_list_in_global") {
-        p->hgt_bin_list_in_global = value != 0;
-    } else if (k == "no_block_preload") {
-        p->no_block_preload = value != 0;
-    } else if (k == "block_waves") {
-        if (value != 0 && value != 4 && value != 8 && value != 16) return ps_fail(PS_ERR_INVALID, "block_waves must be 0 (auto), 4, 8 or 16");
-        p->block_waves = (uint32_t)value;
-    } else if (k == "lds_limit") {
-        if (value < 1024 || value > 160 * 1024) return ps_fail(PS_ERR_INVALID, "lds_limit must be 1 KiB..160 KiB");
-        p->lds_limit = (uint32_t)value;
-        p->pairs_cached = 0;          // the cached pair list is sorted / has a thread table depending on the LDS tile
-    } else {
-        return ps_fail(PS_ERR_INVALID, "unknown tuning key %s", key);
-    }
-    return PS_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -1604,7 +1478,7 @@ static int launch_acc_hgt(ps_population *p, uint32_t gen, hipStream_t st, hipEve
         // held ~60 events and the pass was a chain of small dependent reads -- one rank of 8 at cfg4: 4.78 -> 4.63 ms per
         // generation at 1024, cfg5pop 4.22 -> 4.13, cfg4 33.66 -> 33.45, cfg3 unchanged; 512: cfg3 0.68 against 0.64)
         uint32_t donor_blocks = std::min(items, 1024u);
-        if (const char *e = getenv("PANSIM_HGT_DONOR_BLOCKS")) donor_blocks = std::max(1u, std::min(items, (uint32_t)atoi(e)));
+        if (env_given("PANSIM_HGT_DONOR_BLOCKS")) donor_blocks = std::max(1u, std::min(items, (uint32_t)env_int("PANSIM_HGT_DONOR_BLOCKS", 0)));
         // ~1024 apply workgroups, at most 64 slice images (measured: cfg3 64 of 32/64/128, cfg4 5 of 2/3/5)
         // (a donor shard has 1 / K of the events for the same images: fewer slices mean less to zero, publish and reduce --
         // one rank of 8 at cfg4, with a wave per bin in the LDS-image pass: 5 / 3 / 2 / 1 slices 0.43 / 0.41 / 0.40 / 0.40 ms exposed)
@@ -1875,7 +1749,7 @@ static unsigned host_threads_for(uint64_t n)
 {
     if (n < 16384) return 1;
     unsigned hw = std::thread::hardware_concurrency();
-    if (const char *e = getenv("PANSIM_HOST_THREADS")) hw = (unsigned)std::max(1, atoi(e));
+    if (env_given("PANSIM_HOST_THREADS")) hw = (unsigned)std::max(1, (int)env_int("PANSIM_HOST_THREADS", 0));
     return std::max(1u, std::min(std::min(hw, 16u), (unsigned)(n / 8192)));
 }
 template <typename F>
@@ -3676,8 +3550,7 @@ static int sim_create_impl(const ps_sim_params *p, ps_sim *s)
             const double sweep_ms = bytes / 4.2e12 * 1e3;
             ept = std::min((sweep_ms - 0.3) / 1.0e-3 * 0.5, 112.0);
         }
-        s->acc->hgt_events_per_thread = ept >= 16.0 ? (uint32_t)ept : 0u;
-        if (const char *e = getenv("PANSIM_HGT_EVENTS_PER_THREAD")) s->acc->hgt_events_per_thread = (uint32_t)atoi(e);
+        s->acc->hgt_events_per_thread = (uint32_t)env_int("PANSIM_HGT_EVENTS_PER_THREAD", ept >= 16.0 ? (uint32_t)ept : 0u);
     }
     HIPCHK(hipEventCreateWithFlags(&s->ev_hgt, hipEventDisableTiming));
     {
@@ -3688,7 +3561,7 @@ static int sim_create_impl(const ps_sim_params *p, ps_sim *s)
         // 0.15 -- 9e6 -- 1567 / 1653; 0.2 -- 1.2e7 -- 1728 / 1884 generations/s: profiles/r05_sweep_experiments.md 11)
         s->heavy_hgt = (double)N * s->der.n_recombinations_pan_total >= 7.5e6 && parts >= 1 && parts <= 1024;
     }
-    if (const char *e = getenv("PANSIM_HEAVY_HGT")) s->heavy_hgt = atoi(e) != 0;
+    s->heavy_hgt = env_flag("PANSIM_HEAVY_HGT", s->heavy_hgt);
     // Inside the generation loop the sweep shares the GPU with the accessory chain of the next
     // generation: 7 resident workgroups per CU leave that chain 4 wave slots and 20 KB of LDS on
     // every CU (the sweep's rows are assigned dynamically, so lower residency costs no tail).
@@ -3698,7 +3571,7 @@ static int sim_create_impl(const ps_sim_params *p, ps_sim *s)
     // at 6 / 7 / 8; with the bin pass running beside the sweep's tail, 7: 1388 / 1411 / 1386.)
     // A large accessory genome needs more room: the HGT kernel's donor list (2 bytes per gene of the
     // largest compartment) must fit the LDS the sweep leaves (pan_genes 20000: 1463 / 1664 / 1684 at 7 / 6 / 5).
-    if (!getenv("PANSIM_SWEEP_BLOCKS_PER_CU")) {
+    if (!env_given("PANSIM_SWEEP_BLOCKS_PER_CU")) {
         uint64_t max_comp = 0;
         for (int c = 0; c < d.n_comp; c++) max_comp = std::max<uint64_t>(max_comp, d.comp_end[c] - d.comp_begin[c]);
         const uint64_t list_lds = 2 * max_comp;
@@ -3721,8 +3594,7 @@ static int sim_create_impl(const ps_sim_params *p, ps_sim *s)
     HIPCHK(hipHostGetDevicePointer((void **)&s->m_num_genes, s->h_num_genes, 0));
     HIPCHK(hipHostGetDevicePointer((void **)&s->m_logw, s->h_logw, 0));
     HIPCHK(hipHostMalloc(&s->h_avg, N * sizeof(double)));
-    s->device_draw = N >= 4096;
-    if (const char *e = getenv("PANSIM_DEVICE_DRAW")) s->device_draw = atoi(e) != 0;
+    s->device_draw = env_flag("PANSIM_DEVICE_DRAW", N >= 4096);
     HIPCHK(hipHostMalloc(&s->h_cum, N * sizeof(double)));
     HIPCHK(hipMalloc(&s->d_cum, N * sizeof(double)));
     HIPCHK(hipMalloc(&s->d_idx_tsum, ((N + 1023) / 1024 + 1) * sizeof(uint32_t)));
@@ -3736,8 +3608,7 @@ static int sim_create_impl(const ps_sim_params *p, ps_sim *s)
         HIPCHK(hipMemcpy(s->d_log1p, l1p.data(), G * sizeof(double), hipMemcpyHostToDevice));
     }
     // neutral selection: the reduce pass of a binned HGT leaves the gene counts the next generation's host half reads
-    // (PANSIM_FUSE_COUNTS=0: the separate kernel, for A/B runs)
-    if (G && !s->need_logw && !(getenv("PANSIM_FUSE_COUNTS") && atoi(getenv("PANSIM_FUSE_COUNTS")) == 0)) {
+    if (G && !s->need_logw && env_flag("PANSIM_FUSE_COUNTS", true)) {
         s->acc->fuse_counts_out = s->m_num_genes;
         s->acc->fuse_logw_out = s->m_logw;
     }
@@ -3931,7 +3802,7 @@ static int sim_accessory_half(ps_sim *s, uint32_t gen, uint32_t gens, bool light
         HIPCHK(hipEventRecord(s->ev_hgt, sa));       // (recorded again after the LDS-image pass; this one covers an HGT that launches nothing)
         // (measured, not kept as the default: cfg3 exposed 0.092 / 0.094 against 0.087 / 0.092 ms, one rank of 8 at cfg4 0.69 / 0.63 against
         // 0.66 / 0.66 -- what sits between two sweeps is the bin pass finishing late, not the event latency; profiles/r05_sweep_experiments.md 8)
-        static const bool gap_on_core = getenv("PANSIM_GAP_ON_CORE_STREAM") && atoi(getenv("PANSIM_GAP_ON_CORE_STREAM")) != 0;
+        static const bool gap_on_core = env_flag("PANSIM_GAP_ON_CORE_STREAM", false);
         if (gap_on_core && !s->ev_bin) HIPCHK(hipEventCreateWithFlags(&s->ev_bin, hipEventDisableTiming));
         PSCHK(launch_acc_hgt(acc, gen, sa, prev >= 0 ? s->ev_core[prev] : nullptr, s->ev_hgt, gap_on_core ? sc : nullptr, s->ev_bin));
         HIPCHK(hipStreamWaitEvent(sc, s->ev_hgt, 0));      // (a no-op when the event was recorded on sc itself)
@@ -3945,8 +3816,8 @@ static int sim_accessory_half(ps_sim *s, uint32_t gen, uint32_t gens, bool light
     {
         const bool sharded_rows = acc->exchange && acc->donor_cnt != 0;
         const bool big_davg = acc->d.G > 0 && N >= 2 && (sharded_rows || N > 8192 || acc->davg_form >= 2) && acc->davg_form != 1;
-        static const bool off = getenv("PANSIM_DAVG_AHEAD") && atoi(getenv("PANSIM_DAVG_AHEAD")) == 0;
-        if (!off && p.competition_strength > 0.0 && big_davg && (heavy_hgt || p.HGT_rate <= 0.0) && (int64_t)gen + 1 != (int64_t)p.n_gen) {      // (not behind the run's last generation)
+        static const bool ahead = env_flag("PANSIM_DAVG_AHEAD", true);
+        if (ahead && p.competition_strength > 0.0 && big_davg && (heavy_hgt || p.HGT_rate <= 0.0) && (int64_t)gen + 1 != (int64_t)p.n_gen) {      // (not behind the run's last generation)
             PSCHK(sim_average_distance(s));
             s->avg_prefetched = true;
             s->avg_epoch = acc->edit_epoch;
@@ -4037,13 +3908,11 @@ static int sim_generations(ps_sim *s, uint32_t first, uint32_t gens, uint32_t de
 // workgroup's worth of wave slots, registers and LDS per CU free (6 workgroups per CU instead of 7)
 static void sim_exchange_schedule(ps_sim *s)
 {
-    const char *e = getenv("PANSIM_EXCHANGE_BESIDE_SWEEP");
-    const bool on = e && atoi(e) != 0 && s->acc->exchange != nullptr;
-    s->acc->exchange_beside_sweep = on;
+    s->acc->exchange_beside_sweep = env_flag("PANSIM_EXCHANGE_BESIDE_SWEEP", false) && s->acc->exchange != nullptr;
     // A donor-sharded run has a longer chain between two sweeps (LDS-image pass, reduce, exchange, merge): the window sweep
     // leaves it more of every CU -- 5 workgroups per CU instead of 6 (round 6, one rank of 8 at cfg4: the sweep 3.60 against
     // 3.56 ms, the period 3.93 against 4.05 ms; profiles/r06_d_ab_cfg4_shard8.json)
-    if (s->acc->exchange != nullptr && s->core->window_blocks_per_cu == 0 && !getenv("PANSIM_WINDOW_BPC")) s->core->window_blocks_per_cu = 5;
+    if (s->acc->exchange != nullptr && s->core->window_blocks_per_cu == 0 && !env_given("PANSIM_WINDOW_BPC")) s->core->window_blocks_per_cu = 5;
 }
 
 extern "C" int ps_sim_set_exchange(ps_sim *s, ps_exchange_fn fn, void *ctx)
@@ -4119,13 +3988,13 @@ static int emulated_exchange(void *ctx, void *d_words, uint64_t n_words, void *h
         HIPCHK(hipGetDevice(&dev));
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;
         s->emu_clock_khz = (uint32_t)khz;
-        const char *e = getenv("PANSIM_EMU_XGMI_GBPS");
+        const char *e = env_str("PANSIM_EMU_XGMI_GBPS");
         if (e && atof(e) > 0.0) s->emu_link_gbps = atof(e);
-        e = getenv("PANSIM_EMU_COLL_LATENCY_US");
+        e = env_str("PANSIM_EMU_COLL_LATENCY_US");
         if (e && atof(e) >= 0.0) s->emu_latency_us = atof(e);
     }
     const uint64_t part = bytes / (uint64_t)s->emu_shards * (uint64_t)(s->emu_shards - 1);
-    static const bool ring = getenv("PANSIM_EMU_RING") && atoi(getenv("PANSIM_EMU_RING")) != 0;
+    static const bool ring = env_flag("PANSIM_EMU_RING", false);
     const double slice = (double)bytes / (double)s->emu_shards;
     const double a2a_us = s->emu_latency_us + slice / (s->emu_link_gbps * 1e3);             // direct: one slice per link, all links at once
     const double gather_us = ring ? s->emu_latency_us + (double)part / (s->emu_link_gbps * 1e3) : a2a_us;
@@ -4682,9 +4551,8 @@ extern "C" int ps_multi_create(const ps_sim_params *p, int n_shards, const int *
             }
         }
     (void)hipGetLastError();
-    // HGT donors sharded over the shards (each generates 1/K of the events, the deltas are ORed across the devices);
-    // PANSIM_MULTI_REPLICATED_HGT=1 keeps round 2's form (every shard generates every event, no exchange)
-    if (n_shards > 1 && peers_ok && !getenv("PANSIM_MULTI_REPLICATED_HGT") && (uint64_t)n_shards <= p->pop_size) {
+    // HGT donors sharded over the shards (each generates 1/K of the events, the deltas are ORed across the devices)
+    if (n_shards > 1 && peers_ok && !env_given("PANSIM_MULTI_REPLICATED_HGT") && (uint64_t)n_shards <= p->pop_size) {
         m->delta.assign((size_t)n_shards, nullptr);
         m->ev_ready.assign((size_t)n_shards, nullptr);
         m->ev_read.assign((size_t)n_shards, nullptr);
@@ -4694,7 +4562,7 @@ extern "C" int ps_multi_create(const ps_sim_params *p, int n_shards, const int *
         m->copy_stream.assign((size_t)n_shards, nullptr);
         m->landing.assign((size_t)n_shards, nullptr);
         m->landing_cap.assign((size_t)n_shards, 0);
-        if (const char *e = getenv("PANSIM_MULTI_EXCHANGE")) m->sliced = strcmp(e, "or") != 0;
+        if (const char *e = env_str("PANSIM_MULTI_EXCHANGE")) m->sliced = strcmp(e, "or") != 0;
         m->ctx.resize((size_t)n_shards);
         int rc = PS_OK;
         for (int k = 0; k < n_shards && rc == PS_OK; k++) {
@@ -4718,7 +4586,7 @@ extern "C" int ps_multi_create(const ps_sim_params *p, int n_shards, const int *
         }
         m->donor_sharded = true;
     }
-    if (n_shards > 1 && !getenv("PANSIM_MULTI_OWN_WEIGHTS")) {
+    if (n_shards > 1 && !env_given("PANSIM_MULTI_OWN_WEIGHTS")) {
         if (m->ctx.empty()) {
             m->ctx.resize((size_t)n_shards);
             for (int k = 0; k < n_shards; k++) m->ctx[(size_t)k] = multi_ctx{ m, (size_t)k };

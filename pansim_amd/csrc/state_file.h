@@ -197,10 +197,8 @@ extern "C" int ps_state_info(const char *path, ps_sim_params *params_out, ps_sta
 static uint64_t state_chunk_rows(uint64_t L, uint64_t row_file_bytes, uint32_t cpr)
 {
     uint64_t rows = std::max<uint64_t>(1, (64ull << 20) / row_file_bytes);
-    if (const char *e = getenv("PANSIM_STATE_CHUNK_ROWS")) {
-        const long long v = atoll(e);
-        if (v >= 1) rows = (uint64_t)v;
-    }
+    const long long v = env_int("PANSIM_STATE_CHUNK_ROWS", 0);
+    if (v >= 1) rows = (uint64_t)v;
     rows = std::min<uint64_t>(rows, std::max<uint64_t>(1, (1ull << 30) / row_file_bytes));
     rows = std::min<uint64_t>(rows, ((1ull << 31) - 1) / cpr);
     return std::max<uint64_t>(1, std::min(rows, L));

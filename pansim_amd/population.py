@@ -1215,3 +1215,9 @@ class Population:
     def set_tuning(self, key, value):
         """launch tuning / test hooks of ps_set_tuning (no reference counterpart)"""
         check(self._lib.ps_set_tuning(self._h, key.encode(), int(value)))
+
+    def get_tuning(self, key):
+        """the value of a ps_set_tuning switch as it is now (ps_get_tuning)"""
+        value = C.c_int64(0)
+        check(self._lib.ps_get_tuning(self._h, key.encode(), C.byref(value)))
+        return int(value.value)

@@ -48,7 +48,7 @@ def test_every_new_symbol_is_exported_and_declared(pa):
     for cls in (pa.Population, pa.Simulation, pa.MultiSimulation):
         for method in ("tree_gene_likelihood", "tree_gene_ancestral", "tree_gene_fit", "tree_gene_timing"):
             assert callable(getattr(cls, method))
-    assert 'k == "gene_team"' in open(os.path.join(os.path.dirname(pa.LIB_PATH), "csrc", "pansim_capi.hip")).read() and '"gene_team"' in hdr
+    assert b"gene_team" in [pa.load().ps_tuning_key(k) for k in range(64)] and '"gene_team"' in hdr
 
 
 # --------------------------------------------------------------------------------------------------------- brute force
